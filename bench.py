@@ -1,25 +1,28 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json metric on MI355X: entities culled / s (+ skinned verts / s and the north-star frame as `also`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-stdout carries ONE compact JSON line (<= 4 KB: the contract keys + `roofline` + `cpu_baseline` + a handful of scalars under `also`),
-printed last. Everything else - the roofline legs, the side measurements (tools/bench_extras.py), the CPU thread sweep - goes to
-bench_extra.json (repo root and gpurun_out/) and to stderr. The one-rank exchange-path probe only runs with --exchange-probe.
+stdout carries ONE compact JSON line (<= 4 KB), printed last. A plain run does only what that line's headline figure needs: it builds
+the scene, runs the W warm-up steps, times the K steps and prints the contract keys + `config`. --dump-outputs DIR writes what the last
+timed step computed to DIR/*.npy (see dump_outputs). --full adds everything else the bench measures or checks: the visible ids against
+the reference's digests, the roofline legs (`roofline`), the CPU baseline (`cpu_baseline`), the side measurements (tools/bench_extras.py,
+a handful of scalars under `also`) and, for N > 1, the exchange checks and the config-4 / config-5 frames. A --full run writes its whole
+record to bench_extra.json and to stderr. The one-rank exchange-path probe only runs with --full --exchange-probe.
 
 Workload at N=1: BASELINE config 2 ("10M static entities, 1 frustum, 1xMI355X cull + compaction"), sparse variant (cube
 [-15000,15000]^3, ~1 M occupied cells), camera = the reference player's default viewport (fov 60 deg, 1920x1080, near 0.1, far 10000,
 SURVEY.md 8d). One step = one cull of every resident entity INCLUDING the compaction into one packed, contiguous record
 [8 per-type counts | ids] left in HBM (k_cull_tile + k_cull_pack). `value` is an EFFECTIVE rate (the default camera rejects ~95 % of the
-tiles by their boxes); `roofline` describes k_cull_tile on the every-sphere-is-fetched-and-tested scene, cache-cold. The ids the timed
-camera produces are checked against the reference's sha256 (tests/golden/). For N>1 (one process per GPU) a step is cull + the native
+tiles by their boxes); `roofline` describes k_cull_tile on the every-sphere-is-fetched-and-tested scene, cache-cold. With --full the ids
+the timed camera produces are checked against the reference's sha256 (tests/golden/). For N>1 (one process per GPU) a step is cull + the native
 exchange (lmx_exchange_*: one ncclAllGather of [counts | ids] per rank). --scaling weak (default): every rank owns its own 10 M
 entities; --scaling strong: BASELINE config 4 - ONE 10 M scene partitioned over the ranks by cell hash.
 
-Timing: W untimed warm-up steps, then repetitions of EXACTLY K steps, each repetition bracketed by barrier + device synchronize on both
-sides and reduced MAX over ranks; `ms_per_step` is the median repetition (K = 20 steps of 15 us are 0.3 ms: one repetition alone is
-noise), `config.timed_steps` says how many steps were timed in all. value = entities resident on all ranks x frusta / ms_per_step.
+Timing: W untimed warm-up steps, then EXACTLY K timed steps, bracketed by barrier + device synchronize on both sides and reduced MAX
+over ranks; `ms_per_step` is their time / K (--min-timed-steps M: repetitions of K steps until M were timed, `ms_per_step` the median
+repetition), `config.timed_steps` says how many steps were timed in all. value = entities resident on all ranks x frusta / ms_per_step.
 Inputs are resident in HBM before the timed region starts; the frustum (256 B) is a kernel argument.
 """
 import argparse
@@ -68,6 +71,46 @@ def check_ids(res, scene, camera="default", frustum=0):
     if got != want:
         raise SystemExit(f"bench: visible ids of {scene}/{camera} differ from the reference's ({got} != {want})")
     return "reference"
+
+
+# ---- --dump-outputs: what the last timed step computed, for comparing two builds output for output ------------------------------
+DUMP_LIMIT = 60_000_000  # bytes of all .npy files together (headers included)
+
+
+def read_record(lib, d_record, record_words):
+    """(counts[8], ids) of the packed record lmx_cull_pack_device left in device memory - [8 per-type counts | ids, types back to back] -
+    copied to the host with the HIP runtime the library itself runs on. Only the used part is read, and never past the record's words."""
+    import ctypes as C
+
+    copy = lib.hipMemcpy
+    copy.restype, copy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    device_to_host = 2  # hipMemcpyDeviceToHost
+    counts = np.zeros(8, np.uint32)
+    if copy(counts.ctypes.data, d_record, counts.nbytes, device_to_host) != 0:
+        raise RuntimeError("hipMemcpy of the record's counts failed")
+    n = int(counts.sum())
+    if n > record_words - len(counts):
+        raise RuntimeError(f"the record's counts say {n} ids, it holds {record_words - len(counts)}")
+    ids = np.zeros(n, np.int32)
+    if n and copy(ids.ctypes.data, d_record + counts.nbytes, ids.nbytes, device_to_host) != 0:
+        raise RuntimeError("hipMemcpy of the record's ids failed")
+    return counts, ids
+
+
+def dump_outputs(out_dir, records, log):
+    """records: [(prefix, counts[8], ids of type 0 first)] -> out_dir/<prefix>counts.npy and <prefix>ids.npy, float64 (exact for every
+    id). Within a type the ids are sorted: their order there is unspecified, as in the reference. A list too long for DUMP_LIMIT is cut
+    to a fixed sample (seed 0, positions in ascending order), the same for the same list length."""
+    os.makedirs(out_dir, exist_ok=True)
+    keep = (DUMP_LIMIT - 512 * len(records)) // 8 // len(records) - 8  # ids per record
+    for prefix, counts, ids in records:
+        ends = np.minimum(np.cumsum(counts.astype(np.int64)), len(ids))
+        ids = np.concatenate([np.sort(part) for part in np.split(ids, ends[:-1])])
+        if len(ids) > keep:
+            ids = ids[np.sort(np.random.default_rng(0).choice(len(ids), keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{prefix}counts.npy"), counts.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{prefix}ids.npy"), ids.astype(np.float64))
+        log(f"outputs: {out_dir}/{prefix}counts.npy, {prefix}ids.npy ({len(ids)} of {int(counts.sum())} ids)")
 
 
 # ---- the device under the bench: torch.cuda for streams / events / buffers on a GPU; nothing at all on the simulated device ----------
@@ -172,6 +215,9 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the id checks, roofline legs, CPU baseline, side measurements and N > 1 frames (the --no-* / --headline-only options below trim this run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (float64, <= 64 MB in all)")
     ap.add_argument("--entities", type=int, default=10_000_000, help="entities per GPU")
     ap.add_argument("--variant", choices=["sparse", "dense"], default="sparse")
     ap.add_argument("--camera", choices=["default", "all_visible"], default="default",
@@ -191,7 +237,7 @@ def main(argv=None):
     ap.add_argument("--no-config5-frame", action="store_true", help="N > 1: skip BASELINE config 5's frame (8 cascade frusta in one pass + ONE collective, lmx_exchange_cull_many)")
     ap.add_argument("--exchange-probe", action="store_true", help="after everything else, besides the default one-rank exchange step: the same with the side-stream gather -> bench_extra.json")
     ap.add_argument("--no-exchange-step", action="store_true", help="skip the N > 1 step with a world of ONE rank (a child process; `also.exchange_step_one_rank_ms`)")
-    ap.add_argument("--min-timed-steps", type=int, default=200, help="repeat the K-step timed region until at least this many steps were timed")
+    ap.add_argument("--min-timed-steps", type=int, default=0, help="repeat the K-step timed region until at least this many steps were timed (default: K steps, once)")
     ap.add_argument("--selftest-hostsim", action="store_true", help="TEST MODE (CPU, tests/test_bench_contract.py): run this file's code path against tests/hostsim's build of the library with tiny scenes")
     args = ap.parse_args(argv)
 
@@ -279,8 +325,6 @@ def main(argv=None):
     def timed_repeated(fn, steps):
         """repetitions of exactly `steps` steps until --min-timed-steps were timed: (median ms per step, all repetitions)"""
         reps = max(1, -(-args.min_timed_steps // max(steps, 1)))
-        if selftest:
-            reps = 2
         all_ms = [timed(fn, steps) for _ in range(reps)]
         return float(np.median(all_ms)), all_ms
 
@@ -303,7 +347,7 @@ def main(argv=None):
     log(f"[rank {rank}] scene {args.variant}: {N} entities, {stats['cells']} cells, {stats['chunks']} chunks, build {time.time() - t0:.1f}s")
     frustum = api.viewport_frustum()  # default player viewport at the origin
     baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         baseline = CpuBaseline(scenes, sc, frustum, log, quick=selftest)  # builds the CPU-side scene on a background thread while the GPU legs run
     # Process warm-up, outside every timed region: the HIP runtime pays a one-time ~50 ms stall around the 850th kernel launch of a
     # process (tools/hip_queue_stall_probe.py). Without this it lands in whichever timed loop crosses that count.
@@ -349,16 +393,68 @@ def main(argv=None):
     for _ in range(args.warmup):
         step()
     gather_probe = None
-    if use_dist and exchange_info["mode"] != "p2p":
+    if args.full and use_dist and exchange_info["mode"] != "p2p":
         # one all-gather of the record THIS step ships, timed over 32 gathers (a collective: every rank is here), outside the timed region
         gather_probe = xchg.timeGather(1)
         for _ in range(max(2, min(args.warmup, 5))):
             step()
     ms_per_step, reps_ms = timed_repeated(step, args.steps)  # (the closing synchronize of `timed` also drains the side stream's last gathers)
     value = (N if strong else N * world) * n_frusta / (ms_per_step * 1e-3)
+    if args.dump_outputs:  # before anything else runs on view 0 / the exchange slots: the record the last timed step left
+        if use_dist:
+            xchg.wait(slot_c.value)
+            records = [(f"rank{r}_", *xchg.read(slot_c.value, r)) for r in range(world)] if rank == 0 else []
+        else:
+            records = [("", *read_record(lib, rec_p.value, rec_n.value))]
+        if records:
+            dump_outputs(args.dump_outputs, records, log)
+
+    result = {
+        "metric": "entities_culled_per_sec",
+        "value": value,
+        "unit": "entities/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic" if not selftest else "SELFTEST on the simulated device: not a measurement",
+        "config": {
+            "workload": f"BASELINE config 2: {N} static entities per GPU ({args.variant}, cube +-{half:g}), 1 frustum (fov 60, 16:9, near 0.1, far 10000), cull + compaction",
+            "entities_per_gpu": N,
+            "frusta": n_frusta,
+            "cells_per_gpu": stats["cells"],
+            "sharding": (("one scene partitioned by cell hash" if strong else "own entities per rank") + ", native RCCL all-gather of visible ids") if use_dist else "single GPU",
+            "timed_steps": args.steps * len(reps_ms),
+            "repetitions": len(reps_ms),
+            "ms_per_step_is": "median over the repetitions of (K steps between barrier + synchronize, MAX over ranks) / K",
+            "ms_per_step_min_max": [min(reps_ms), max(reps_ms)],
+        },
+    }
+    result["value_is"] = ("EFFECTIVE rate of the BASELINE config-2 camera: resident entities / wall time of one cull incl. compaction (k_cull_tile + k_cull_pack); ~95 % of the "
+                          "tiles are rejected by their boxes and never fetched, so value x 20 B is NOT a memory rate - `value_streaming` and `roofline` are")
+    if use_dist:
+        result["config"]["exchange_mode"] = exchange_info["mode"]
+        result["config"]["exchange_gather_us_first_frame"] = exchange_info["gather_us"]  # what `auto` decided on: the first frame's record
+        result["config"]["exchange_mode_why"] = exchange_info["why"]
+    if args.ranks_share_gpu:
+        result["config"]["TEST_MODE"] = "--ranks-share-gpu: all ranks on cuda:0, gloo + shared-memory collective (tests/cpp/loopback_rccl.cpp); timings are meaningless"
+    if not args.full:
+        log(f"[rank {rank}] headline: {ms_per_step * 1e3:.2f} us per step ({args.steps} steps)")
+        if use_dist:
+            xchg.close()
+        if rank == 0:
+            print(compact_line(result), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return 0
+
     ms_cull_only = ms_host_list = None
     if not use_dist:
-        ms_cull_only = timed(lambda: cs.cull(frustum), max(args.steps, 2 if selftest else args.min_timed_steps))  # rounds 1 / 2's step: the cull kernel alone
+        ms_cull_only = timed(lambda: cs.cull(frustum), max(args.steps, 2 if selftest else 200))  # rounds 1 / 2's step: the cull kernel alone
         # SURVEY.md 8d (i), second form: the list on the HOST - what the CullingSystem adapter does per view: cull + lmx_cull_map_all
         # (packed record copied into the library's pinned buffer; ONE host wait), PCIe included. Never `value`.
         ids_p, cnt8 = C.POINTER(C.c_int32)(), (C.c_uint32 * 8)()
@@ -536,35 +632,8 @@ def main(argv=None):
         "legs": legs,
     }
 
-    result = {
-        "metric": "entities_culled_per_sec",
-        "value": value,
-        "unit": "entities/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic" if not selftest else "SELFTEST on the simulated device: not a measurement",
-        "config": {
-            "workload": f"BASELINE config 2: {N} static entities per GPU ({args.variant}, cube +-{half:g}), 1 frustum (fov 60, 16:9, near 0.1, far 10000), cull + compaction",
-            "entities_per_gpu": N,
-            "frusta": n_frusta,
-            "cells_per_gpu": stats["cells"],
-            "visible_per_gpu": visible,
-            "sharding": (("one scene partitioned by cell hash" if strong else "own entities per rank") + ", native RCCL all-gather of visible ids") if use_dist else "single GPU",
-            "timed_steps": args.steps * len(reps_ms),
-            "repetitions": len(reps_ms),
-            "ms_per_step_is": "median over the repetitions of (K steps between barrier + synchronize, MAX over ranks) / K",
-            "ms_per_step_min_max": [min(reps_ms), max(reps_ms)],
-        },
-        "roofline": roofline,
-    }
-    result["value_is"] = ("EFFECTIVE rate of the BASELINE config-2 camera: resident entities / wall time of one cull incl. compaction (k_cull_tile + k_cull_pack); ~95 % of the "
-                          "tiles are rejected by their boxes and never fetched, so value x 20 B is NOT a memory rate - `value_streaming` and `roofline` are")
+    result["config"]["visible_per_gpu"] = visible
+    result["roofline"] = roofline
     if ms_cull_only is not None:
         result["value_cull_only"] = N * world / (ms_cull_only * 1e-3)
         result["ms_per_step_cull_only"] = ms_cull_only
@@ -576,16 +645,11 @@ def main(argv=None):
     result["config"]["visible_ids"] = ids_checked  # 'reference': sha256 of the sorted ids == the reference CullingSystemImpl's on the same seeded scene
     result["config"].update(dist_info)
     if use_dist:
-        result["config"]["exchange_mode"] = exchange_info["mode"]
-        result["config"]["exchange_gather_us_first_frame"] = exchange_info["gather_us"]  # what `auto` decided on: the first frame's record
-        result["config"]["exchange_mode_why"] = exchange_info["why"]
         if gather_probe is not None:
             result["config"]["exchange_gather_us"] = round(gather_probe[0], 2)  # one gather of the record the timed step ships, 32 back to back on the side stream
             result["config"]["exchange_gather_record_bytes"] = 4 * gather_probe[1]
         result["config"].update(headline_exchange)
         result["config"]["xgmi_curve"] = "ONE point; before this run NO 1/2/4/8 xGMI curve existed (the builder's boxes have one GPU): the driver computes scaling from its own runs"
-    if args.ranks_share_gpu:
-        result["config"]["TEST_MODE"] = "--ranks-share-gpu: all ranks on cuda:0, gloo + shared-memory collective (tests/cpp/loopback_rccl.cpp); timings are meaningless"
     if rank == 0 and world == 1:
         if not args.no_extras and not args.headline_only:
             result["extra"] = {}
@@ -802,6 +866,9 @@ def compact_line(result):
             line["config"][frame] = {k: f[k] for k in ("ms_per_frame_max_over_ranks", "frames_per_sec", "skinned_verts_per_sec_all_ranks", "entity_frustum_tests_per_sec_all_ranks", "error") if k in f}
             if isinstance(f.get("exchange"), dict):  # config 5's frame: what its 8-sub-record exchange ships
                 line["config"][frame]["exchange"] = {k: f["exchange"][k] for k in ("mode", "bytes_shipped_per_peer", "bytes_used_this_rank", "shipped_over_used", "gather_us_of_this_record", "overflow_mask") if k in f["exchange"]}
+    if "roofline" not in result:  # a plain run: the headline and its config, nothing else was measured
+        s = json.dumps(line, separators=(",", ":"))
+        return s if len(s) <= LINE_LIMIT else json.dumps(dict(line, config={"workload": _short(cfg.get("workload", ""), 120)}), separators=(",", ":"))
     line["roofline"] = {k: _short(result["roofline"].get(k), 160) for k in ROOFLINE_KEYS}
     if "cpu_baseline" in result:
         line["cpu_baseline"] = {k: _short(result["cpu_baseline"][k], 340) for k in CPU_KEYS if k in result["cpu_baseline"]}
@@ -868,7 +935,7 @@ def exchange_path_one_rank(args, log, timeout_s=150.0, extra_env=None):
     """`bench.py --force-collective --headline-only` as a child: ms per step / entities per second of the exchange path with one rank."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--force-collective", "--headline-only", "--no-cpu-baseline", "--no-live-traffic", "--no-extras",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--force-collective", "--headline-only", "--no-cpu-baseline", "--no-live-traffic", "--no-extras",
            "--steps", str(max(args.steps, 500)), "--warmup", str(args.warmup), "--entities", str(args.entities), "--variant", args.variant]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29600 + os.getpid() % 300 + (1 if extra_env else 0)), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     env.update(extra_env or {})

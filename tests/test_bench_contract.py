@@ -1,5 +1,5 @@
 """The bench line's contract (keys the driver and the judge read), checked on the committed output of the round's last full run
-(profiles/rNN/bench_full_run.json = stdout of `python bench.py` on an MI355X): no GPU needed."""
+(profiles/rNN/bench_full_run.json = stdout of a full run, `python bench.py --full`, on an MI355X): no GPU needed."""
 import glob
 import subprocess
 import sys
@@ -74,7 +74,7 @@ def test_bench_main_prints_one_compact_line_on_the_simulated_device():
 
     lib = hostsim_build.build()
     env = dict(os.environ, LMX_HOSTSIM="1", LMX_LIB_PATH=lib)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--selftest-hostsim", "--steps", "3", "--warmup", "1"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--selftest-hostsim", "--full", "--steps", "3", "--warmup", "1"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     out = p.stdout.decode()
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
@@ -86,6 +86,43 @@ def test_bench_main_prints_one_compact_line_on_the_simulated_device():
     full = json.load(open(os.path.join(ROOT, "bench_extra.json")))
     assert "legs" in full["roofline"] and "extra" in full and "error" not in full["extra"], full.get("extra", {}).get("error")
     assert max(len(l) for l in p.stderr.decode(errors="replace").splitlines()) < 4000  # stderr stays line-oriented too
+
+
+def test_plain_bench_run_times_k_steps_and_dumps_the_last_steps_record(tmp_path, oracle_port):
+    """A plain run (no --full) on the simulated device: exactly --steps timed steps, the headline and its config on the line and nothing
+    measured besides; --dump-outputs writes the record of the last timed step - the same in two runs, and the oracle's ids for the scene."""
+    import numpy as np
+
+    from lumixengine_amd import api, scenes
+    from tests.hostsim import build as hostsim_build
+
+    env = dict(os.environ, LMX_HOSTSIM="1", LMX_LIB_PATH=hostsim_build.build())
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--selftest-hostsim", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out_dir)],
+                           cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
+        lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1 and len(lines[0].encode()) <= 4096
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["config"]["timed_steps"] == 5 and d["config"]["repetitions"] == 1
+        assert abs(d["value"] - d["config"]["entities_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert not {"roofline", "cpu_baseline", "also"} & set(d) and "visible_ids" not in d["config"]
+        assert sorted(os.listdir(out_dir)) == ["counts.npy", "ids.npy"]
+        counts, ids = np.load(out_dir / "counts.npy"), np.load(out_dir / "ids.npy")
+        assert counts.dtype == ids.dtype == np.float64 and counts.shape == (8,) and len(ids) == counts.sum() > 0
+        dumps.append((counts, ids, d["config"]["entities_per_gpu"]))
+    assert all(np.array_equal(a, b) for a, b in zip(dumps[0], dumps[1]))
+    counts, ids, n = dumps[0]
+    sc = scenes.cull_scene(n, 2000.0, seed=2)  # bench.py --selftest-hostsim's scene and camera
+    ocs = oracle_port.culling_system()
+    ocs.add_bulk(sc["entity"], sc["type"], sc["pos"], sc["radius"])
+    want_ids, want_types, _ = ocs.cull(api.viewport_frustum())
+    assert np.array_equal(counts, np.bincount(want_types, minlength=8))
+    assert np.array_equal(ids, np.concatenate([np.sort(want_ids[want_types == t]) for t in range(8)]))
 
 
 def test_compact_line_holds_its_limit_whatever_the_legs_return():

@@ -85,10 +85,9 @@ def test_emulated_cull_threaded_layout_build(emul_lib, oracle_port):
         H.assert_same_visible(got[f], H.sorted_by_type(ids, types), H.CAMERAS[f][0])
 
 
-DEMO_MAPS = sorted(__import__("glob").glob("/root/reference/demo/maps/*/*.unv"))
+DEMO_MAPS = sorted(__import__("glob").glob(os.path.join(G, "demo_maps", "*.unv")))  # the reference's demo/maps/*/*.unv
 
 
-@pytest.mark.skipif(not DEMO_MAPS, reason="no reference tree on this machine")
 def test_emulated_cull_on_the_reference_demo_scenes(emul_lib, oracle_port):
     """Entity placements as real scenes have them (the worlds the reference ships: stacks of boxes, rows of characters, a few huge
     ground planes - not uniform noise): every entity that carries a model becomes a sphere around its serialized world position

@@ -25,7 +25,7 @@ def run_bench(extra, port, launcher="torchrun"):
         env.pop(k, None)
     # "torchrun": the driver's multi-GPU launch line; "self": plain `python bench.py --gpus 2` - bench.py starts its ranks itself
     front = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)] if launcher == "torchrun" else [sys.executable]
-    cmd = front + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--ranks-share-gpu", "--entities", "1000000",
+    cmd = front + [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--ranks-share-gpu", "--entities", "1000000",
                    "--skinned-instances", "2000", "--no-cpu-baseline", "--no-live-traffic", "--big-entities", "0"] + extra
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("{")]
@@ -60,7 +60,7 @@ def test_bench_weak_two_ranks(launcher):
     c4 = r["config"]["config4_frame"]  # the strong-scaling frame of BASELINE config 4 rides along the weak run
     assert "error" not in c4 and c4["scaling"] == "strong" and c4["skinned_instances_this_rank"] == 1000 and c4["frames_per_sec"] > 0
     assert 0 < c4["visible_total"] <= 1_000_000
-    c5 = r["config"]["config5_frame"]  # BASELINE config 5's frame (8 cascades, ONE collective) is part of the default --gpus N path
+    c5 = r["config"]["config5_frame"]  # BASELINE config 5's frame (8 cascades, ONE collective) is part of the --full --gpus N path
     assert "error" not in c5 and c5["own_sub_records_equal_local_cull"] is True and c5["ms_per_frame_max_over_ranks"] > 0
     assert len(c5["visible_per_rank_and_frustum"]) == 2 and len(c5["visible_per_rank_and_frustum"][0]) == 8
     e5 = c5["exchange"]  # per-frustum capacities: the 8-sub-record frame ships at most 1.3x what its fullest rank uses (4.6x with one capacity for all)

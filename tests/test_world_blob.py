@@ -16,16 +16,16 @@ from tests import helpers as H
 G = os.path.join(os.path.dirname(__file__), "golden")
 
 
-DEMO_MAPS = sorted(__import__("glob").glob("/root/reference/demo/maps/*/*.unv"))  # worlds written by the reference's own editor / engine
+DEMO_MAPS = sorted(__import__("glob").glob(os.path.join(G, "demo_maps", "*.unv")))  # the reference's demo/maps/*/*.unv: worlds written by its own editor / engine
 
 
-@pytest.mark.skipif(not DEMO_MAPS, reason="no reference tree on this machine")
 def test_reference_demo_maps(oracle_port):
     """Every serialized world the reference ships (demo/maps/*/*.unv, RenderModuleVersion 16 and 18, eight modules each) through the
     product's host-side readers: the World part (entities, names, hierarchy) and the "renderer" module's payload. Checks that only
     real files can give: the renderer's sections are consumed to the very byte where the next module's header ("animation") starts;
     a child's stored world transform is its parent's composed with its stored local one; bone attachments point at entities that
     exist and at parents that carry a model."""
+    assert len(DEMO_MAPS) == 12
     seen_attachment = False
     for path in DEMO_MAPS:
         data = open(path, "rb").read()

@@ -4,11 +4,11 @@
 WHAT=${1:-all}
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
 	S=$(date +%s)
-	timeout 900 python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_stderr_legs_and_extras.txt"; echo "bench rc=$? seconds=$(( $(date +%s) - S ))" | tee "$OUT/bench_rc.txt"
+	timeout 900 python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_stderr_legs_and_extras.txt"; echo "bench rc=$? seconds=$(( $(date +%s) - S ))" | tee "$OUT/bench_rc.txt"
 	cp bench_extra.json "$OUT/bench_extra.json" 2>/dev/null
 fi
 if [ "$WHAT" = stats ] || [ "$WHAT" = all ]; then
-	prof bench_headline python "$ROOT/bench.py" --headline-only --no-extras --no-cpu-baseline
+	prof bench_headline python "$ROOT/bench.py" --full --headline-only --no-extras --no-cpu-baseline
 	grep -h '^{' "$OUT/bench_headline.log" > "$OUT/bench_headline_under_rocprof.json" 2>/dev/null
 	prof cull_all_test_cold $W --workload cull_all_test --steps 40 --cold read
 	prof cull_all_test_100m $W --workload cull_all_test --steps 12 --entities 100000000
