@@ -236,3 +236,64 @@ def array_digest(*arrays):
     for a in arrays:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()
+
+
+# ---- the several-frusta cull pre-test: how close a scene's (sphere, plane) pairs sit to its decision edge ----------------------------------
+CELL_SIZE = np.float32(300.0)
+_ANCHOR = (0, 4, 1, 0, 0, 2)  # getRelative's corner per plane NEAR FAR LEFT RIGHT TOP BOTTOM (geometry.cpp:121-149)
+
+
+def cell_relative(pos: np.ndarray):
+    """(cell-relative sphere centres as float32 (n, 3), cell origins as float64 (n, 3)): CellIndices (lmx_math.h cell_of - the double
+    position times the float 1 / 300, truncated toward zero; NaN and out-of-range give INT32_MIN) and Vec3(pos - cell origin)."""
+    pos = np.asarray(pos, np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = pos * np.float64(np.float32(1.0) / CELL_SIZE)
+        ok = (v > -2147483649.0) & (v < 2147483648.0)
+        idx = np.where(ok, np.trunc(np.where(ok, v, 0.0)), -2147483648.0)
+        origin = idx * np.float64(CELL_SIZE)
+        rel = (pos - origin).astype(np.float32)
+    return rel, origin
+
+
+def relative_planes(frusta: np.ndarray, cell_origin: np.ndarray):
+    """(nx, ny, nz) float32 (F, 6) and the cell-relative plane distances d float32 (n, F, 6) of ShiftedFrustum::getRelative
+    (lmx_math.h relative_plane_d): d = -((qx nx + qy ny) + qz nz) with q = the plane's corner + Vec3(frustum origin - cell origin)."""
+    nx, ny, nz = (np.ascontiguousarray(frusta[k][:, :6]).astype(np.float32) for k in ("xs", "ys", "zs"))
+    pts = frusta["points"].astype(np.float32)[:, list(_ANCHOR), :]  # (F, 6, 3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        off = (frusta["origin"][None, :, :] - np.asarray(cell_origin, np.float64)[:, None, :]).astype(np.float32)  # (n, F, 3)
+        q = pts[None, :, :, :] + off[:, :, None, :]
+        d = -((q[..., 0] * nx + q[..., 1] * ny) + q[..., 2] * nz)
+    return (nx, ny, nz), d.astype(np.float32)
+
+
+def pretest_band(pos: np.ndarray, radius: np.ndarray, frusta: np.ndarray):
+    """Where the matrix-pipe pre-test of the several-frusta cull (cull_kernels.hip, "sphere x plane pre-test") leaves every
+    (sphere, frustum, plane) triple of ONE call - `frusta` are the frusta of one pass. Returns a dict of
+      T      float32 (n, F, 6): the reference's fl(fl(fl(fl(x nx) + fl(y ny)) + fl(z nz)) + d) + r on the cell-relative centre (culled iff < 0)
+      eps    float32 (n, F):    the kernel's decision threshold eps = G' x 1.5 x 2^-14 + 2^-120, G' = (|x| + |y| + |z|) n1 + |r| in fp32,
+                                n1 = the call's largest |n|_1 x 1.000001 (inf, i.e. no pre-test, when a plane coefficient is not finite)
+      ratio  float64 (n, F, 6): T / eps, signed; |ratio| > 1 means the pre-test decides the pair from its bf16 estimate alone
+    """
+    f32 = np.float32
+    rel, origin = cell_relative(pos)
+    r = np.asarray(radius, f32)
+    (nx, ny, nz), d = relative_planes(frusta, origin)
+    with np.errstate(invalid="ignore", over="ignore"):
+        x, y, z = (rel[:, k][:, None, None] for k in range(3))
+        t = ((x * nx[None] + y * ny[None]) + z * nz[None]) + d
+        T = (t + r[:, None, None]).astype(f32)
+        n1v = (np.abs(nx) + np.abs(ny)) + np.abs(nz)
+        finite = bool(np.all(n1v <= f32(3.0e38)))
+        n1s = (f32(n1v.max()) * f32(1.000001)) * f32(134217728.0) if finite else f32(np.inf)
+        gs = ((np.abs(rel[:, 0]) + np.abs(rel[:, 1])) + np.abs(rel[:, 2])) * n1s + np.abs(r) * f32(134217728.0)
+        eps = (gs * f32(6.821210263296962e-13) + f32(7.52316384526264e-37)).astype(f32)
+        ratio = T.astype(np.float64) / np.broadcast_to(eps.astype(np.float64)[:, None, None], T.shape)
+    return {"T": T, "eps": np.broadcast_to(eps[:, None], (len(r), len(frusta))).copy(), "ratio": ratio}
+
+
+def pretest_pair_ratio(band: dict) -> np.ndarray:
+    """(n, F) float64: the ratio of the plane that decides each (sphere, frustum) pair - the smallest T of its six (NaN where one is NaN)."""
+    k = np.nanargmin(np.where(np.isnan(band["T"]), np.inf, band["T"]), axis=2)
+    return np.take_along_axis(band["ratio"], k[..., None], 2)[..., 0]

@@ -22,6 +22,8 @@
 //   HOSTSIM_RACE=1      ThreadSanitizer build only: kernel-level race detection (below)
 //   HOSTSIM_STACK_KB=n  stack of one lane (default 128, 512 under AddressSanitizer)
 //   HOSTSIM_DEBUG=1     ThreadSanitizer build only: one line per block
+//   HOSTSIM_MFMA_SKEW=s v_mfma_f32_32x32x16_bf16 errs by s u of its magnitude sum towards (and across) zero instead of rounding the
+//                       exact sum once: the worst case of an accumulation error bound of s u (include/hip/hip_runtime.h)
 #include <hip/hip_runtime.h>
 
 #include <sys/mman.h>
@@ -502,6 +504,14 @@ double now_ms() {
 } // namespace
 
 void note_launch_error(hipError_t e) { t_last_error = e; }
+
+double mfma_skew() { // HOSTSIM_MFMA_SKEW, read once
+	static const double s = [] {
+		const char* v = getenv("HOSTSIM_MFMA_SKEW");
+		return v && *v ? atof(v) * 0x1p-24 : 0.0;
+	}();
+	return s;
+}
 
 __attribute__((noinline, convergent)) const WaveSnapshot* wave_exchange(uint64_t value) {
 	Worker* w = t_worker;

@@ -353,6 +353,10 @@ static __forceinline__ f32x16 mfma_f32_32x32x2f32(float a, float b, f32x16 c) {
 // v_mfma_f32_32x32x16_bf16: A[i = lane & 31][k = 8 (lane >> 5) + e], B[k = 8 (lane >> 5) + e][j = lane & 31] (element e of the 8-vector), the C / D
 // map of the f32 form. Modelled as the exact sum C + sum a b rounded once; the hardware's accumulation differs from that by up to ~4.5 u of
 // the magnitude sum (tools/mfma_contract_probe.hip) - code built on it must not depend on the last bits, and the cull pre-test does not.
+// HOSTSIM_MFMA_SKEW = s (hostsim_runtime.cpp) models the worst accumulation an error bound of s u allows instead: the exact sum plus
+// s 2^-24 (|C| + sum |a b|), pushed against the exact sum's sign (upwards when it is 0) - towards zero and across it. Sums whose magnitude
+// is not finite are left alone (the bound is relative to a finite magnitude).
+double mfma_skew(); // s x 2^-24; 0 when the variable is not set
 template <typename V8> static __forceinline__ f32x16 mfma_f32_32x32x16_bf16(V8 a, V8 b, f32x16 c) {
 	static_assert(sizeof(V8) == 16, "eight bf16 per lane");
 	uint64_t w[4];
@@ -364,14 +368,18 @@ template <typename V8> static __forceinline__ f32x16 mfma_f32_32x32x16_bf16(V8 a
 		for (int l = 0; l < 64; ++l) memcpy((part < 2 ? av[l] : bv[l]) + 4 * (part & 1), &s->val[l], 8);
 	}
 	const uint32_t l = lane(), col = l & 31u;
+	const double skew = mfma_skew();
 	f32x16 d;
 	for (int r = 0; r < 16; ++r) {
 		const uint32_t row = (uint32_t)(r & 3) + 8u * (uint32_t)(r >> 2) + 4u * (l >> 5);
-		double acc = c[r];
+		double acc = c[r], mag = __builtin_fabs((double)c[r]);
 		for (int k = 0; k < 16; ++k) {
 			const uint32_t ab = (uint32_t)av[row + 32 * (k >> 3)][k & 7] << 16, bb = (uint32_t)bv[col + 32 * (k >> 3)][k & 7] << 16;
-			acc += (double)from_bits<float>(ab) * (double)from_bits<float>(bb);
+			const double p = (double)from_bits<float>(ab) * (double)from_bits<float>(bb);
+			acc += p;
+			mag += __builtin_fabs(p);
 		}
+		if (skew != 0.0 && __builtin_isfinite(mag)) acc += (acc > 0.0 ? -skew : skew) * mag;
 		d[r] = (float)acc;
 	}
 	return d;

@@ -846,3 +846,259 @@ def test_cull_fuzz(oracle_port, seed):
 
     st = fuzz_cull.run(seed, 300, oracle_port)
     assert st["culls"] > 30
+
+
+# ---- the several-frusta pre-test at its decision edge -------------------------------------------------------------------------------
+# k_cull_tile with 2..8 frusta decides a (sphere, frustum) pair from a bf16 v_mfma_f32_32x32x16_bf16 estimate of its six plane expressions
+# whenever the estimate's minimum clears eps = 1.5 x 2^-14 G' + 2^-120, and leaves it to the exact loop otherwise (cull_kernels.hip,
+# "sphere x plane pre-test"). The scenes below put every sphere at a chosen multiple of ITS OWN eps from one plane of one frustum, so that
+# most of the pairs the pre-test decides sit at 1..4 eps - where a bound that is too small shows - and tests/helpers.pretest_band proves it.
+# tests/test_hostsim.py::test_pretest_band_under_adversarial_mfma runs them against a simulated MFMA that errs by as much as the bound allows.
+
+def _split_worst(v, rng):
+    """float32 values within 2^-7 of `v` whose two-term bf16 split (v1 = bf16(v), v2 = bf16(v - v1), round to nearest) leaves the most
+    out: |v - v1| just under half a bf16 ulp (|v2| ~ 2^-8 x 2^e, e = the binade of v) and |v - v1 - v2| = 63 fp32 ulps, just under half of
+    v2's own bf16 ulp (~2^-17 x 2^e) - the largest remainders the split can leave. v2 and the remainder point either way at random, so the
+    omitted terms of a product add up in some pairs and cancel in others."""
+    v = np.asarray(v, np.float32)
+    bits = v.view(np.uint32)
+    exp_bits = bits & np.uint32(0x7F800000)
+    v1 = (bits & np.uint32(0xFFFF0000)).view(np.float32)  # the top 7 mantissa bits, truncated: |v1| <= |v| < |v1| + bf16 ulp
+    a = rng.integers(1, 5, v.shape).astype(np.int64)
+    # 2^15 fp32 ulps = half a bf16 ulp; v2 = bf16 of the offset: 2^15 - 128 a (remainder -63 ulps) or 2^15 - 128 (a + 1) (remainder +63)
+    units = (1 << 15) - 128 * a - np.where(rng.random(v.shape) < 0.5, 63, 65)
+    ulp = (exp_bits.astype(np.int64) - (23 << 23)).clip(1 << 23).astype(np.uint32).view(np.float32).astype(np.float64)  # 2^(e - 23)
+    down = (rng.random(v.shape) < 0.5) & ((bits & np.uint32(0x007F0000)) != 0)  # (below v1 only where that stays in the binade)
+    mag = np.abs(v1).astype(np.float64) + np.where(down, -1.0, 1.0) * units * ulp
+    out = (np.sign(v).astype(np.float64) * mag).astype(np.float32)
+    return np.where(np.isfinite(v) & (exp_bits > np.uint32(24 << 23)) & (v != 0), out, v)
+
+
+def _finish_planes(fr):
+    """ds as setPlanesFromPoints forms it from the (edited) normals; EXTRA0 / EXTRA1 repeat NEAR (the reference tests all eight)."""
+    pts = fr["points"][:, list(H._ANCHOR), :]
+    fr["ds"][:, :6] = -((pts[..., 0] * fr["xs"][:, :6] + pts[..., 1] * fr["ys"][:, :6]) + pts[..., 2] * fr["zs"][:, :6])
+    for key in ("xs", "ys", "zs", "ds"):
+        fr[key][:, 6] = fr[key][:, 0]
+        fr[key][:, 7] = fr[key][:, 0]
+    return fr
+
+
+def _band_frusta(n):
+    """n perspective frusta that differ by a few units and a few milliradians (a cell that straddles a plane of one straddles the same
+    plane of all: every tile of the band scene is MIXED for every frustum, so every tile runs the pre-test when n >= 3). The odd frusta's
+    plane normals are moved to the split's worst case; EXTRA0 / EXTRA1 repeat NEAR and ds follows the normals as setPlanesFromPoints forms it."""
+    out = []
+    for f in range(n):
+        out.append(api.viewport_frustum(pos=(37.5 + 1.25 * f, 12.25 - 0.5 * f, -61.0 + 0.75 * f), rot=H.quat_from_yaw_pitch(0.6 + 0.004 * f, -0.25 + 0.003 * f),
+                                        fov=float(np.deg2rad(60.0)), near=1.0, far=1400.0))
+    fr = np.concatenate(out)
+    rng = np.random.default_rng(100 + n)
+    for f in range(1, n, 2):
+        for key in ("xs", "ys", "zs"):
+            fr[key][f, :6] = _split_worst(fr[key][f, :6], rng)
+    return _finish_planes(fr)
+
+
+def _axis_frusta(n):
+    """n ortho boxes within a few milliradians of the axes, in the positive octant. Every plane is scaled so that its dominant normal
+    component sits at the bottom of the binade [1, 2) and then moved to the split's worst case: with the call's n1 ~ 1.01, the omitted
+    terms of a centre whose coordinate along that axis is ~256 reach ~2^-16 G' and more - what a threshold a few times too small misses
+    (the generic frusta's n1 ~ 1.4 and diagonal normals keep them below 2^-16 G' / 2)."""
+    fr = np.concatenate([api.viewport_frustum(is_ortho=True, ortho_size=1200.0, w=1024, h=1024, near=0.0, far=2400.0,
+                                              pos=(4500.0 + 1.5 * f, 3000.0 - 0.75 * f, 6000.0 + f), rot=H.quat_from_yaw_pitch(0.002 + 0.0007 * f, 0.0015 - 0.0004 * f))
+                         for f in range(n)])
+    rng = np.random.default_rng(200 + n)
+    lead = np.max(np.abs(np.stack([fr["xs"][:, :6], fr["ys"][:, :6], fr["zs"][:, :6]])), axis=0)
+    scale = (np.float32(1.0039) / lead).astype(np.float32)
+    for key in ("xs", "ys", "zs"):
+        fr[key][:, :6] = _split_worst(fr[key][:, :6] * scale, rng)
+    return _finish_planes(fr)
+
+
+def _band_scene(fr, n, seed, axis=False):
+    """n spheres, each tangent - up to a signed margin T chosen relative to its own eps - to one plane of one frustum of `fr`: |T| / eps
+    log-uniform over [2^-8, 2^8], both signs, 3 % exact zeros (t + r == 0 does not cull). Half the centres have split-worst-case
+    cell-relative coordinates; about a third are big spheres centred next to their cell's origin; `axis` (the frusta of _axis_frusta):
+    a quarter more sit at the bottom of a binade along the plane's axis. Returns (scene dict, the targeted frustum and plane of every sphere)."""
+    rng = np.random.default_rng(seed)
+    nf = len(fr)
+    f_of = rng.integers(0, nf, n)
+    k_of = rng.choice(6, n, p=[0.04, 0.192, 0.192, 0.192, 0.192, 0.192])  # (the near face is a unit across)
+    nrm = np.stack([fr["xs"][f_of, k_of], fr["ys"][f_of, k_of], fr["zs"][f_of, k_of]], 1).astype(np.float64)
+    anchor = fr["points"][f_of, np.array(H._ANCHOR)[k_of]].astype(np.float64)
+    w = rng.dirichlet(np.full(8, 0.7), n)
+    inner = np.einsum("nj,njc->nc", w, fr["points"][f_of].astype(np.float64))  # a point of the frustum (relative to its origin)
+    nn = (nrm * nrm).sum(1)
+    on_plane = inner - nrm * (((inner - anchor) * nrm).sum(1) / nn)[:, None]
+    rho = np.exp(rng.uniform(np.log(4.0), np.log(60.0), n))
+    pos = fr["origin"][f_of] + on_plane - nrm * (rho / np.sqrt(nn))[:, None]  # outside the plane by rho
+    # 40 %: a big sphere (r 40..295) whose centre sits next to its cell's origin, so that |d| ~ r ~ G': there the MFMA's own error term,
+    # relative to |d| + sum |a b| ~ 2 G', is largest against eps (a centre far into its cell has (|x| + |y| + |z|) n1 >> sum |x_i n_i|)
+    corner = rng.random(n) < 0.4
+    far = fr["origin"][f_of] + on_plane - nrm * (rng.uniform(60.0, 280.0, n) / np.sqrt(nn))[:, None]
+    base = H.cell_relative(far)[1]
+    step = np.where(far < 0, -300.0, 300.0)
+    lattice = np.where(np.abs(far - base) > 150.0, base + step, base)  # the nearest point of the cell lattice, per axis
+    near_corner = lattice + np.where(far < 0, -1.0, 1.0) * rng.uniform(0.5, 12.0, (n, 3))
+    gap = -H.pretest_band(near_corner, np.zeros(n, np.float32), fr)["T"][np.arange(n), f_of, k_of]
+    corner &= (gap > 40.0) & (gap < 295.0)
+    pos = np.where(corner[:, None], near_corner, pos)
+    adv = rng.random(n) < 0.5
+    if axis:
+        # half of the rest: the coordinate along the plane's dominant axis at 256..262 (the bottom of its binade), the other two at 0.5..2,
+        # i.e. (|x| + |y| + |z|) n1 ~ |x_a n_a|, split worst case: the omitted terms up to 2 x 2^-16 G' against eps = 6 x 2^-16 G'
+        pick = ~corner & (rng.random(n) < 0.5)
+        ax = np.argmax(np.abs(nrm), axis=1)
+        cell = H.cell_relative(far)[1]
+        rel = np.where(np.arange(3)[None, :] == ax[:, None], rng.uniform(256.2, 262.0, (n, 3)), rng.uniform(0.5, 2.0, (n, 3)))
+        cand = cell + np.where(cell < 0, -1.0, 1.0) * rel
+        gap = -H.pretest_band(cand, np.zeros(n, np.float32), fr)["T"][np.arange(n), f_of, k_of]
+        pick &= (gap > 1.0) & (gap < 295.0)
+        pos = np.where(pick[:, None], cand, pos)
+        adv |= pick
+    rel, origin = H.cell_relative(pos)
+    moved = origin + _split_worst(rel, rng).astype(np.float64)
+    same_cell = np.all(H.cell_relative(moved)[1] == origin, axis=1)
+    pos = np.where((adv & same_cell)[:, None], moved, pos)
+    idx = np.arange(n)
+    S = H.pretest_band(pos, np.zeros(n, np.float32), fr)["T"][idx, f_of, k_of]  # fl(fl(dot) + d): T = fl(S + r)
+    sign = np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    ratio = sign * np.exp2(rng.uniform(-8.0, 8.0, n))
+    zero = rng.random(n) < 0.03
+    radius = (-S).astype(np.float32)
+    for _ in range(2):  # eps depends on |r|: two rounds settle it
+        eps = H.pretest_band(pos, radius, fr)["eps"][idx, f_of].astype(np.float64)
+        radius = np.where(zero, -S, (ratio * eps - S.astype(np.float64)).astype(np.float32)).astype(np.float32)
+    entity = np.arange(n, dtype=np.int32)
+    return {"entity": entity, "type": (entity % 3).astype(np.uint8), "pos": pos, "radius": radius}, (f_of, k_of)
+
+
+def _band_coverage(sc, fr):
+    """Per sign, the (sphere, frustum) pairs the pre-test decides at 1..4 eps - the ratio of the plane with the smallest T."""
+    r = H.pretest_pair_ratio(H.pretest_band(sc["pos"], sc["radius"], fr))
+    return int(((r > 1) & (r <= 4)).sum()), int(((r < -1) & (r >= -4)).sum())
+
+
+def _cull_all_vs_oracle(cs, ocs, fr, what, view=0):
+    cs.setPassWidth(len(fr))
+    res = cs.cull(fr, view=view)
+    seen = 0
+    for f in range(len(fr)):
+        H.assert_same_visible(gpu_visible(res, f), oracle_visible(ocs, fr[f : f + 1]), f"{what}, frustum {f}")
+        seen += len(res.all_ids(f)[0])
+    return seen
+
+
+@pytest.mark.parametrize("n_frusta", list(range(2, 9)))
+def test_cull_pretest_band_ratio(gpu_ctx, oracle_port, monkeypatch, n_frusta):
+    """Every frustum count in ONE pass (2..4: the 8-wave shape, one group of four frusta with absent rows for 2 / 3; 5..8: the 4-wave
+    shape, two groups; 2: the pre-test never runs, fewer than PRETEST_MIN_MIXED frusta are MIXED), with the packed cell keys and with
+    LMX_CULL_WIDE_KEYS=1, id for id against the oracle, for both frustum families. The scenes put thousands of pairs at 1..4 eps on
+    either side of the edge (what an MFMA error beyond the bound's 16 u turns, tests/test_hostsim.py) and thousands within 0.2 eps whose
+    omitted split terms exceed eps / 8 (what a threshold that is too small turns)."""
+    for family, fr in (("generic", _band_frusta(n_frusta)), ("axis", _axis_frusta(n_frusta))):
+        sc, _ = _band_scene(fr, 40_000 + 10_000 * n_frusta, seed=500 + n_frusta, axis=family == "axis")
+        pos_cov, neg_cov = _band_coverage(sc, fr)
+        assert pos_cov >= 2000 and neg_cov >= 2000, (family, pos_cov, neg_cov)
+        ocs = oracle_port.culling_system()
+        ocs.add_bulk(sc["entity"], sc["type"], sc["pos"], sc["radius"])
+        seen = []
+        try:
+            for wide in (False, True):
+                if wide:
+                    monkeypatch.setenv("LMX_CULL_WIDE_KEYS", "1")
+                cs = api.CullingSystem(gpu_ctx)
+                cs.build(sc["entity"], sc["type"], sc["pos"], sc["radius"])
+                assert cs.layoutInfo()["cell_key_bytes"] == (16 if wide else 8)
+                seen.append(_cull_all_vs_oracle(cs, ocs, fr, f"{family} frusta, {n_frusta} of them, wide keys {wide}"))
+                cs.setPassWidth(0)
+        finally:
+            monkeypatch.delenv("LMX_CULL_WIDE_KEYS", raising=False)
+        assert seen[0] == seen[1] and 0.2 * len(sc["entity"]) < seen[0] < 0.95 * n_frusta * len(sc["entity"]), (family, seen)
+
+
+def _on_plane_centres(fr, sc, f_of, k_of, count, rng):
+    """Centres whose reference expression for their plane is EXACTLY zero: t = fl(fl(fl(fl(x nx) + fl(y ny)) + fl(z nz)) + d) == 0, found
+    by moving a band centre onto its plane and searching y and z over +-48 fp32 ulps of the cell-relative position."""
+    pick = rng.choice(len(f_of), 600, replace=False)
+    f, k = f_of[pick], k_of[pick]
+    nrm = np.stack([fr["xs"][f, k], fr["ys"][f, k], fr["zs"][f, k]], 1).astype(np.float64)
+    S = H.pretest_band(sc["pos"][pick], np.zeros(len(pick), np.float32), fr)["T"][np.arange(len(pick)), f, k].astype(np.float64)
+    rel, origin = H.cell_relative(sc["pos"][pick] - nrm * (S / (nrm * nrm).sum(1))[:, None])
+    d = H.relative_planes(fr, origin)[1][np.arange(len(pick)), f, k]
+    steps = np.arange(-48, 49, dtype=np.int32)
+    yy = (rel[:, 1].view(np.int32)[:, None] + steps).view(np.float32)[:, :, None]
+    zz = (rel[:, 2].view(np.int32)[:, None] + steps).view(np.float32)[:, None, :]
+    nx, ny, nz = (fr[key][f, k].astype(np.float32)[:, None, None] for key in ("xs", "ys", "zs"))
+    t = ((rel[:, 0][:, None, None] * nx + yy * ny) + zz * nz) + d[:, None, None]
+    out = []
+    for i in np.flatnonzero((t == 0).any(axis=(1, 2))):
+        a, b = np.argwhere(t[i] == 0)[0]
+        p = origin[i] + np.array([rel[i, 0], yy[i, a, 0], zz[i, 0, b]], np.float64)
+        if H.pretest_band(p[None], np.zeros(1, np.float32), fr[f[i] : f[i] + 1])["T"][0, 0, k[i]] == 0:  # (same cell, same expression)
+            out.append(p)
+    assert len(out) >= count, len(out)
+    return np.array(out[:count])
+
+
+def test_cull_pretest_band_edges(gpu_ctx, oracle_port):
+    """Non-finite and degenerate spheres INSIDE pre-tested tiles (cells of band spheres with all eight frusta MIXED): radii of +inf, NaN, 0,
+    -0.0, small negatives, 1e-40 (subnormal) and 3e38 (G' and eps infinite), centres exactly on a plane with r = 0 (t + r == 0: visible);
+    then the same scene with frustum 7's LEFT plane NaN (pretest_n1s = inf: the pre-test is off for the whole call), with frustum 3's
+    planes scaled by 2^20 (eps of every frustum 2^20 wider) and with frustum 5's scaled by 2^-20 (its pairs all undecided)."""
+    rng = np.random.default_rng(41)
+    fr = _band_frusta(8)
+    sc, (f_of, k_of) = _band_scene(fr, 60_000, seed=41)
+    er = H.edge_case_scene()["radius"]
+    radii = [er[np.isposinf(er)][0], er[np.isnan(er)][0], er[er == 0][0], er[er < 0][0], np.float32(-0.0), np.float32(-1e-3), np.float32(1e-40), np.float32(3e38)]
+    hosts = rng.choice(len(f_of), 40 * len(radii), replace=False)
+    pos = [sc["pos"][hosts], _on_plane_centres(fr, sc, f_of, k_of, 40, rng)]
+    rad = [np.repeat(np.array(radii, np.float32), 40), np.zeros(40, np.float32)]
+    pos = np.concatenate([sc["pos"]] + pos)
+    radius = np.concatenate([sc["radius"]] + rad)
+    entity = np.arange(len(radius), dtype=np.int32)
+    types = (entity % 3).astype(np.uint8)
+    assert _band_coverage({"pos": pos, "radius": radius}, fr)[0] >= 2000
+    cs = api.CullingSystem(gpu_ctx)
+    cs.build(entity, types, pos, radius)
+    ocs = oracle_port.culling_system()
+    ocs.add_bulk(entity, types, pos, radius)
+    try:
+        seen = _cull_all_vs_oracle(cs, ocs, fr, "edge radii")
+        assert seen > 0.2 * len(entity)
+        nan_fr = fr.copy()
+        nan_fr["xs"][7, 2] = np.nan
+        assert np.all(np.isinf(H.pretest_band(pos[:10], radius[:10], nan_fr)["eps"]))
+        _cull_all_vs_oracle(cs, ocs, nan_fr, "frustum 7 with a NaN plane", view=1)
+        for f, scale in ((3, 2.0**20), (5, 2.0**-20)):
+            sfr = fr.copy()
+            for key in ("xs", "ys", "zs", "ds"):
+                sfr[key][f] *= np.float32(scale)
+            _cull_all_vs_oracle(cs, ocs, sfr, f"frustum {f} scaled by {scale}", view=2)
+    finally:
+        cs.setPassWidth(0)
+
+
+def test_cull_pretest_band_slots(oracle_port):
+    """The sort-key tables in slot order (LMX_KEYS_OPT_SLOT_ORDER) make every cull also write the static-set slot of each visible id:
+    the separately compiled SLOTS instantiations of k_cull_tile, both shapes (3 and 8 frusta) on band scenes, ids against the oracle."""
+    ctx = api.Context(0)
+    try:
+        for n_frusta in (3, 8):
+            fr = _band_frusta(n_frusta)
+            sc, _ = _band_scene(fr, 60_000, seed=700 + n_frusta)
+            n = len(sc["entity"])
+            ks = scenes.keys_scene(n, sc["type"], seed=13)
+            sk = api.SortKeys(ctx)
+            sk.setOption(api.KEYS_OPT_SLOT_ORDER, 1)
+            sk.setModels(ks["models"], ks["mesh_types"])
+            sk.setInstances(ks["model"], ks["material_offset"], ks["mesh_materials"], ks["lod"], ks["flags"], ks["dirty"], ks["pose_frame"])
+            cs = api.CullingSystem(ctx)
+            cs.build(sc["entity"], sc["type"], sc["pos"], sc["radius"])
+            ocs = oracle_port.culling_system()
+            ocs.add_bulk(sc["entity"], sc["type"], sc["pos"], sc["radius"])
+            assert _cull_all_vs_oracle(cs, ocs, fr, f"slots, {n_frusta} frusta") > 0.2 * n
+            cs.setPassWidth(0)
+    finally:
+        ctx.close()

@@ -136,3 +136,49 @@ def test_kernels_are_race_free_on_the_simulated_device(tmp_path):
     for f in glob.glob(log + ".*"):
         reports += open(f, errors="replace").read()
     assert "ThreadSanitizer: data race" not in reports, reports[:6000]
+
+
+# the largest MFMA accumulation error (in u = 2^-24 of |C| + sum |a b|) that the pre-test's bound still covers: see the test below
+PRETEST_SKEW_BOUND = 373
+
+
+def _band_outcomes(skew, select, tmp_path):
+    """{test name: passed?} of `pytest -m gpu --hostsim -k select` with HOSTSIM_MFMA_SKEW=skew."""
+    import xml.etree.ElementTree as ET
+
+    xml = str(tmp_path / f"skew_{skew}.xml")
+    env = dict(os.environ, HOSTSIM_MFMA_SKEW=str(skew))
+    env.pop("LMX_LIB_PATH", None)
+    cmd = [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_cull.py"), "-m", "gpu", "--hostsim", "-q", "-n", "4", "-p", "no:cacheprovider",
+           "-k", select, f"--junitxml={xml}"]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
+    assert os.path.exists(xml), (r.stdout + r.stderr)[-4000:]
+    out = {}
+    for case in ET.parse(xml).getroot().iter("testcase"):
+        if case.find("skipped") is None:
+            out[case.get("name")] = case.find("failure") is None and case.find("error") is None
+    assert out, (r.stdout + r.stderr)[-4000:]
+    return out
+
+
+def test_pretest_band_under_adversarial_mfma(tmp_path):
+    """The several-frusta cull's pre-test (cull_kernels.hip, "sphere x plane pre-test") against a simulated v_mfma_f32_32x32x16_bf16 that
+    errs by s u x (|C| + sum |a b|) towards zero and across it (HOSTSIM_MFMA_SKEW, tests/hostsim/include/hip/hip_runtime.h).
+
+    Where the bound stops holding: the pre-test decides a pair when |u'| > eps >= 1.5 x 2^-14 G (G' >= G), and its sign is the exact one
+    when |u - u'| < |u'|. With an accumulation error of s u, |u - u'| <= (5 + s) u M + 3.01 x 2^-16 G x 1.01 (five roundings of the
+    reference's own expression, the instruction, the terms the bf16 split leaves out), M = |d_k| + sum |a b| <= 2 G + |T| <= 2 G + 2 |u'|.
+    The right-hand side grows more slowly in |u'| than |u'| itself, so the tightest case is |u'| = eps:
+        (5 + s) u (2 + 2 x 9.16e-5) G < (9.155e-5 - 4.64e-5) G  <=>  5 + s < 4.515e-5 / (1.192e-7 x 1.0001) = 378.7  <=>  s <= 373.
+    So (the comment's own 16 u is the assumption; 4.5 u is what the hardware has shown):
+      * s = 16 and s = 373 (PRETEST_SKEW_BOUND): every band / pre-test test passes;
+      * s = 4096 (a bound 11 times too small): the scenes' pairs at 1..4 eps with M ~ 2 G' turn, so every band case with 3..8 frusta FAILS -
+        they sit at the decision edge and the pre-test decided them - while 2 frusta (the pre-test never runs: PRETEST_MIN_MIXED = 3) pass.
+    The tile decisions do not depend on the machine, so this is also the evidence that the same tests on the MI355X reach the pre-test."""
+    for skew in (16, PRETEST_SKEW_BOUND):
+        got = _band_outcomes(skew, "band or pretest", tmp_path)
+        assert len(got) >= 11 and all(got.values()), (skew, sorted(k for k, ok in got.items() if not ok))
+    got = _band_outcomes(4096, "pretest_band_ratio", tmp_path)
+    failed = sorted(k for k, ok in got.items() if not ok)
+    want = [f"test_cull_pretest_band_ratio[{n}]" for n in range(3, 9)]
+    assert failed == want and got["test_cull_pretest_band_ratio[2]"], f"at s = 4096 failed: {failed}, expected exactly {want}"
