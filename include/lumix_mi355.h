@@ -575,6 +575,98 @@ LMX_API int lmx_render_blob_read_bone_attachments(const void* data, size_t size,
  * `paths` (0xffffffff: none), for e < n_slots (>= n_model_instance_slots); paths: the file's path table, model_paths_size bytes. */
 LMX_API int lmx_render_blob_read_model_instances(const void* data, size_t size, uint32_t n_slots, uint8_t* flags, uint32_t* path_offset, char* paths,
 	uint32_t paths_cap);
+/* InstancedModel::InstanceData (renderer/render_module.h:233-238), 32 B: the serialized record and the layout of an emitted bin record
+ * (instancing.hlsl InstanceData: rot.xyz | lod or cross-fade weight | pos | scale). */
+typedef struct LmxImInstance {
+	float rot[3];
+	float lod;
+	float pos[3];
+	float scale;
+} LmxImInstance;
+/* One instanced model of the payload (deserializeInstancedModels, render_module.cpp:702-723): entity, model path (offset into the
+ * NUL-separated path block), records [first_instance, first_instance + instance_count) of the instance array. */
+typedef struct LmxBlobInstancedModel {
+	int32_t entity;
+	uint32_t path_offset;
+	uint32_t first_instance, instance_count;
+} LmxBlobInstancedModel;
+/* The instanced-model section: cap_models entries, cap_instances records (all models' instances back to back, file order), the models'
+ * paths NUL-separated in `paths` (*paths_size bytes used). Any capacity too small: LMX_ERR_CAPACITY with the needed sizes in the out
+ * counters (n_models, n_instances, paths_size; each may be NULL). */
+LMX_API int lmx_render_blob_read_instanced_models(const void* data, size_t size, uint32_t cap_models, LmxBlobInstancedModel* models, uint32_t cap_instances,
+	LmxImInstance* instances, uint32_t paths_cap, char* paths, uint32_t* n_models, uint32_t* n_instances, uint32_t* paths_size);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Instanced models: InstancedModel (renderer/render_module.h:228-257), the component behind foliage / grass / scattered props.
+ * lmx_im_set_instances is RenderModuleImpl::initInstancedModelGPUData (render_module.cpp:1285-1365): grid AABB, 4 x 4 XZ cells, stable
+ * scatter into cell order - on the device. lmx_im_run is PipelineImpl::encodeInstancedModels (pipeline.cpp:2449-2660) with the compute
+ * shader data/shaders/instancing.hlsl for EVERY model of the system in two launches: per-block cell verdicts (visible / near / far),
+ * LOD update (cross-fade in visible cells, snap in near-but-invisible cells, nothing in shadow views), sphere test, binned compaction
+ * and the indirect draw arguments. Deviations from the reference: bins are laid out as the model's base + exclusive prefix
+ * of its own bin counts, records inside a bin in ascending sorted instance order (the reference's order comes from atomics); every
+ * registered model owns mesh_count indirect slots (a prefix of mesh counts) and a model that is skipped gets instance_count = 0 there.
+ * An LmxInstancedModels object uses its context's device and stream; destroy it before the context.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct LmxInstancedModels LmxInstancedModels;
+enum {
+	LMX_IM_CELLS = 16,      /* InstancedModel::Grid::cells[4 * 4] */
+	LMX_IM_MAX_MESHES = 31, /* encodeInstancedModels: ASSERT(mesh_count < lengthOf(indices_count) == 32) */
+	LMX_IM_MAX_MODELS = 4096
+};
+/* InstancedModel::Grid::Cell (render_module.h:241-245), 32 B; from_instance is relative to the model's instance array */
+typedef struct LmxImCell {
+	float min[3], max[3];
+	uint32_t from_instance, instance_count;
+} LmxImCell;
+typedef struct LmxImGrid {
+	float min[3], max[3];            /* Grid::aabb */
+	uint32_t placed, unplaced;       /* instances some cell accepts / none does (these follow the cells, input order) */
+	LmxImCell cells[LMX_IM_CELLS];
+} LmxImGrid;
+/* The per-view values encodeInstancedModels reads: view.cp.pos, Renderer::getLODMultiplier, the frame's time delta, cp.is_shadow */
+typedef struct LmxImView {
+	double camera_pos[3];
+	float lod_multiplier;
+	float time_delta;
+	uint32_t is_shadow;
+	uint32_t _pad;
+} LmxImView;
+/* Indirect (instancing.hlsl), 20 B: one per mesh */
+typedef struct LmxImIndirect {
+	uint32_t vertex_count, instance_count, first_index, base_vertex, base_instance;
+} LmxImIndirect;
+/* What a run emitted for one model: records of LOD bin b at [bin_offset[b], bin_offset[b] + bin_count[b]) of the view's record array */
+typedef struct LmxImCounts {
+	uint32_t bin_count[4];
+	uint32_t bin_offset[4];
+	uint32_t indirect_offset, mesh_count; /* the model's slots of the view's indirect array */
+	uint32_t instances, unplaced;
+} LmxImCounts;
+LMX_API int lmx_im_create(LmxContext* ctx, LmxInstancedModels** out);
+LMX_API void lmx_im_destroy(LmxInstancedModels* im);
+/* Model of instanced model `model` (ids are dense: model == the current count appends one): Model::getLODDistances (squared), getLODIndices
+ * (model.h:173-179, 5 entries), getOriginBoundingRadius and Mesh::indices_count of its mesh_count <= LMX_IM_MAX_MESHES meshes
+ * (LMX_ERR_CAPACITY above). Changing a model's mesh count renumbers the indirect slots of the models behind it. */
+LMX_API int lmx_im_set_model(LmxInstancedModels* im, uint32_t model, const float lod_distances[4], const LmxLodIndices lod_indices[5], float origin_radius,
+	uint32_t mesh_count, const uint32_t* indices_count);
+/* RenderModule::endInstancedModelEditing -> initInstancedModelGPUData: upload the model's instances and build its grid on the device
+ * (the stored order becomes the grid order, as in the reference). */
+LMX_API int lmx_im_set_instances(LmxInstancedModels* im, uint32_t model, uint32_t n, const LmxImInstance* instances);
+/* World::getTransform(entity).pos of models [0, n_models), fp64 xyz */
+LMX_API int lmx_im_set_origins(LmxInstancedModels* im, uint32_t n_models, const double* pos_xyz);
+/* encodeInstancedModels(view) for every model: results stay in slot view_slot < LMX_MAX_VIEWS until the next run on that slot; the LOD
+ * state is shared by all views (non-shadow views update it in place, as the reference's instance buffer). Asynchronous. */
+LMX_API int lmx_im_run(LmxInstancedModels* im, uint32_t view_slot, const LmxImView* view, const LmxShiftedFrustum* frustum);
+/* Read-outs (synchronize the stream): the grid, the instances in grid order with the LODs the device holds, per-model counts of a slot
+ * (cap_models >= the model count), the slot's bin records (*out_n = records emitted) and indirect records (*out_n = sum of mesh counts). */
+LMX_API int lmx_im_read_grid(LmxInstancedModels* im, uint32_t model, LmxImGrid* out);
+LMX_API int lmx_im_read_instances(LmxInstancedModels* im, uint32_t model, LmxImInstance* out, uint32_t cap);
+LMX_API int lmx_im_counts(LmxInstancedModels* im, uint32_t view_slot, LmxImCounts* out, uint32_t cap_models);
+LMX_API int lmx_im_read_records(LmxInstancedModels* im, uint32_t view_slot, LmxImInstance* out, uint32_t cap, uint32_t* out_n);
+LMX_API int lmx_im_read_indirect(LmxInstancedModels* im, uint32_t view_slot, LmxImIndirect* out, uint32_t cap, uint32_t* out_n);
+/* Device pointers of a slot for a GPU consumer (stream-ordered after lmx_im_run, valid until the next set_* call): bin records
+ * (LmxImInstance layout, 32 B), indirect records (LmxImIndirect) and per-model LmxImCounts. */
+LMX_API int lmx_im_device_outputs(LmxInstancedModels* im, uint32_t view_slot, const void** d_records, const void** d_indirect, const void** d_counts);
 
 LMX_API const char* lmx_version(void);
 

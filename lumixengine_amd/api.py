@@ -214,6 +214,19 @@ SYMBOLS = {
     "lmx_render_blob_info": (_ci, [_vp, _sz, _vp]),
     "lmx_render_blob_read_bone_attachments": (_ci, [_vp, _sz, _u32, _vp]),
     "lmx_render_blob_read_model_instances": (_ci, [_vp, _sz, _u32, _vp, _vp, _vp, _u32]),
+    "lmx_render_blob_read_instanced_models": (_ci, [_vp, _sz, _u32, _vp, _u32, _vp, _u32, _vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "lmx_im_create": (_ci, [_vp, C.POINTER(_vp)]),
+    "lmx_im_destroy": (None, [_vp]),
+    "lmx_im_set_model": (_ci, [_vp, _u32, _vp, _vp, _f32, _u32, _vp]),
+    "lmx_im_set_instances": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_im_set_origins": (_ci, [_vp, _u32, _vp]),
+    "lmx_im_run": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_im_read_grid": (_ci, [_vp, _u32, _vp]),
+    "lmx_im_read_instances": (_ci, [_vp, _u32, _vp, _u32]),
+    "lmx_im_counts": (_ci, [_vp, _u32, _vp, _u32]),
+    "lmx_im_read_records": (_ci, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_im_read_indirect": (_ci, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_im_device_outputs": (_ci, [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "lmx_version": (C.c_char_p, []),
 }
 
@@ -766,6 +779,131 @@ def render_blob_read(data: bytes):
         if flags[e] & 4:
             models[e] = None if off[e] == 0xFFFFFFFF else table[off[e] : table.index(b"\0", off[e])].decode()
     return {k: int(info[k][0]) for k in RENDER_BLOB_INFO.names}, att, models
+
+
+IM_INSTANCE = np.dtype([("rot", "<f4", 3), ("lod", "<f4"), ("pos", "<f4", 3), ("scale", "<f4")])  # LmxImInstance = InstancedModel::InstanceData
+BLOB_INSTANCED_MODEL = np.dtype([("entity", "<i4"), ("path_offset", "<u4"), ("first_instance", "<u4"), ("instance_count", "<u4")])
+IM_CELL = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("from_instance", "<u4"), ("instance_count", "<u4")])
+IM_GRID = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("placed", "<u4"), ("unplaced", "<u4"), ("cells", IM_CELL, 16)])
+IM_VIEW = np.dtype([("camera_pos", "<f8", 3), ("lod_multiplier", "<f4"), ("time_delta", "<f4"), ("is_shadow", "<u4"), ("_pad", "<u4")])
+IM_INDIRECT = np.dtype([("vertex_count", "<u4"), ("instance_count", "<u4"), ("first_index", "<u4"), ("base_vertex", "<u4"), ("base_instance", "<u4")])
+IM_COUNTS = np.dtype([("bin_count", "<u4", 4), ("bin_offset", "<u4", 4), ("indirect_offset", "<u4"), ("mesh_count", "<u4"), ("instances", "<u4"), ("unplaced", "<u4")])
+IM_MAX_MESHES = 31
+
+
+def render_blob_read_instanced_models(data: bytes):
+    """The instanced-model section of a World blob's renderer payload (render_module.cpp:702-723): [{entity, path, instances IM_INSTANCE[n]}]. Host only."""
+    lib = load_library()
+    buf = np.frombuffer(data, np.uint8)
+    nm, ni, npath = _u32(0), _u32(0), _u32(0)
+    rc = lib.lmx_render_blob_read_instanced_models(_ptr(buf), len(buf), 0, None, 0, None, 0, None, C.byref(nm), C.byref(ni), C.byref(npath))
+    if rc not in (0, 5):
+        raise LumixError(rc, "no readable renderer payload in this World blob")
+    models = np.zeros(max(nm.value, 1), BLOB_INSTANCED_MODEL)
+    inst = np.zeros(max(ni.value, 1), IM_INSTANCE)
+    paths = np.zeros(max(npath.value, 1), np.uint8)
+    rc = lib.lmx_render_blob_read_instanced_models(_ptr(buf), len(buf), len(models), _ptr(models), len(inst), _ptr(inst), len(paths), _ptr(paths), None, None, None)
+    if rc != 0:
+        raise LumixError(rc, "instanced model records truncated")
+    table = paths.tobytes()
+    out = []
+    for m in models[: nm.value]:
+        o = int(m["path_offset"])
+        f, n = int(m["first_instance"]), int(m["instance_count"])
+        out.append({"entity": int(m["entity"]), "path": table[o : table.index(b"\0", o)].decode(), "instances": inst[f : f + n].copy()})
+    return out
+
+
+def im_view(camera_pos=(0, 0, 0), lod_multiplier=1.0, time_delta=1 / 60, is_shadow=False) -> np.ndarray:
+    """LmxImView: what encodeInstancedModels reads of a view (pipeline.cpp:2449-2660)."""
+    v = np.zeros(1, IM_VIEW)
+    v["camera_pos"], v["lod_multiplier"], v["time_delta"], v["is_shadow"] = camera_pos, lod_multiplier, time_delta, int(is_shadow)
+    return v
+
+
+class InstancedModels:
+    """InstancedModel grids + encodeInstancedModels on the device (lmx_im_*). Model ids are dense: addModel appends."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(self.lib.lmx_im_create(ctx.h, C.byref(h)))
+        self.h = h
+        self.n_models = 0
+        self.n = []
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lmx_im_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setModel(self, model: int, lod_distances, lod_indices, origin_radius: float, indices_count):
+        ld = np.ascontiguousarray(lod_distances, np.float32).reshape(4)
+        li = np.ascontiguousarray(np.asarray(lod_indices, np.int32).reshape(5, 2))
+        ic = np.ascontiguousarray(indices_count, np.uint32)
+        self.ctx.check(self.lib.lmx_im_set_model(self.h, model, _ptr(ld), _ptr(li), float(origin_radius), len(ic), _ptr(ic) if len(ic) else None))
+        if model == self.n_models:
+            self.n_models += 1
+            self.n.append(0)
+
+    def addModel(self, lod_distances, lod_indices, origin_radius: float, indices_count) -> int:
+        self.setModel(self.n_models, lod_distances, lod_indices, origin_radius, indices_count)
+        return self.n_models - 1
+
+    def setInstances(self, model: int, instances):
+        inst = np.ascontiguousarray(instances, IM_INSTANCE)
+        self.ctx.check(self.lib.lmx_im_set_instances(self.h, model, len(inst), _ptr(inst) if len(inst) else None))
+        if model < len(self.n):
+            self.n[model] = len(inst)
+
+    def setOrigins(self, pos_xyz):
+        pos = np.ascontiguousarray(pos_xyz, np.float64).reshape(-1, 3)
+        self.ctx.check(self.lib.lmx_im_set_origins(self.h, len(pos), _ptr(pos)))
+
+    def run(self, view, frustum: np.ndarray, view_slot: int = 0):
+        view = np.ascontiguousarray(view, IM_VIEW)
+        fr = np.ascontiguousarray(frustum, SHIFTED_FRUSTUM)
+        self.ctx.check(self.lib.lmx_im_run(self.h, view_slot, _ptr(view), _ptr(fr)))
+
+    def readGrid(self, model: int) -> np.ndarray:
+        g = np.zeros(1, IM_GRID)
+        self.ctx.check(self.lib.lmx_im_read_grid(self.h, model, _ptr(g)))
+        return g[0]
+
+    def readInstances(self, model: int) -> np.ndarray:
+        out = np.zeros(max(self.n[model], 1), IM_INSTANCE)
+        self.ctx.check(self.lib.lmx_im_read_instances(self.h, model, _ptr(out), len(out)))
+        return out[: self.n[model]]
+
+    def counts(self, view_slot: int = 0) -> np.ndarray:
+        out = np.zeros(max(self.n_models, 1), IM_COUNTS)
+        self.ctx.check(self.lib.lmx_im_counts(self.h, view_slot, _ptr(out), len(out)))
+        return out[: self.n_models]
+
+    def readRecords(self, view_slot: int = 0) -> np.ndarray:
+        n = _u32(0)
+        cap = max(int(self.counts(view_slot)["bin_count"].sum()), 1)
+        out = np.zeros(cap, IM_INSTANCE)
+        self.ctx.check(self.lib.lmx_im_read_records(self.h, view_slot, _ptr(out), cap, C.byref(n)))
+        return out[: n.value]
+
+    def readIndirect(self, view_slot: int = 0) -> np.ndarray:
+        n = _u32(0)
+        out = np.zeros(32 * max(self.n_models, 1), IM_INDIRECT)
+        self.ctx.check(self.lib.lmx_im_read_indirect(self.h, view_slot, _ptr(out), len(out), C.byref(n)))
+        return out[: n.value]
+
+    def deviceOutputs(self, view_slot: int = 0):
+        r, i, c = _vp(), _vp(), _vp()
+        self.ctx.check(self.lib.lmx_im_device_outputs(self.h, view_slot, C.byref(r), C.byref(i), C.byref(c)))
+        return r.value, i.value, c.value
 
 
 def keys_view(camera_pos=(0, 0, 0), lod_ref_point=None, lod_multiplier=1.0, time_delta=1 / 60, frame_number=1, is_shadow=False,

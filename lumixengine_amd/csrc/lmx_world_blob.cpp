@@ -150,7 +150,7 @@ constexpr int32_t RENDER_VERSION_MIN = 16, RENDER_VERSION_LATEST = 18; // Render
 
 struct RenderParsed {
 	LmxRenderBlobInfo info;
-	size_t paths_at = 0, instances_at = 0, attachments_at = 0;
+	size_t paths_at = 0, instances_at = 0, attachments_at = 0, instanced_at = 0;
 };
 
 // true when `at` is where a module payload may end: the end of the blob or the header of another module of the file's module list
@@ -277,6 +277,7 @@ int parse_renderer(const void* data, size_t size, Parsed& p, RenderParsed& out) 
 	}
 	if (version <= 16 && s.read<uint32_t>() != 0) return LMX_ERR_INVALID_ARGUMENT; // deserializeFurs (:725-729): the count must be 0
 	info.n_instanced_models = s.read<uint32_t>(); // (:703-723) entity, model path, instances (32 B each)
+	out.instanced_at = s.pos;
 	for (uint32_t i = 0; i < info.n_instanced_models && !s.overflow; ++i) {
 		s.skip(4);
 		s.skip_string();
@@ -362,6 +363,50 @@ int lmx_render_blob_read_model_instances(const void* data, size_t size, uint32_t
 		} else {
 			s.skip_string();
 		}
+	}
+	return s.overflow ? LMX_ERR_INVALID_ARGUMENT : LMX_OK;
+}
+
+int lmx_render_blob_read_instanced_models(const void* data, size_t size, uint32_t cap_models, LmxBlobInstancedModel* models, uint32_t cap_instances,
+	LmxImInstance* instances, uint32_t paths_cap, char* paths, uint32_t* n_models, uint32_t* n_instances, uint32_t* paths_size) {
+	Parsed p;
+	RenderParsed r;
+	if (int rc = parse_renderer(data, size, p, r)) return rc;
+	// deserializeInstancedModels (render_module.cpp:702-723): entity, path (NUL-terminated), u32 count, count raw InstanceData records
+	Reader s{p.blob.data(), p.blob.size(), r.instanced_at};
+	uint32_t n_inst = 0, n_path = 0;
+	for (uint32_t i = 0; i < r.info.n_instanced_models && !s.overflow; ++i) {
+		s.skip(4);
+		const size_t from = s.pos;
+		s.skip_string();
+		n_path += (uint32_t)(s.pos - from);
+		const uint32_t cnt = s.read<uint32_t>();
+		n_inst += cnt;
+		s.skip((size_t)cnt * 32);
+	}
+	if (s.overflow) return LMX_ERR_INVALID_ARGUMENT;
+	if (n_models) *n_models = r.info.n_instanced_models;
+	if (n_instances) *n_instances = n_inst;
+	if (paths_size) *paths_size = n_path;
+	if (cap_models < r.info.n_instanced_models || cap_instances < n_inst || paths_cap < n_path) return LMX_ERR_CAPACITY;
+	if ((r.info.n_instanced_models && !models) || (n_inst && !instances) || (n_path && !paths)) return LMX_ERR_INVALID_ARGUMENT;
+	s.pos = r.instanced_at;
+	uint32_t at_inst = 0, at_path = 0;
+	for (uint32_t i = 0; i < r.info.n_instanced_models; ++i) {
+		LmxBlobInstancedModel& m = models[i];
+		m.entity = s.read<int32_t>();
+		const size_t from = s.pos;
+		s.skip_string();
+		const uint32_t len = (uint32_t)(s.pos - from);
+		memcpy(paths + at_path, p.blob.data() + from, len);
+		m.path_offset = at_path;
+		at_path += len;
+		const uint32_t cnt = s.read<uint32_t>();
+		m.first_instance = at_inst;
+		m.instance_count = cnt;
+		if (cnt) memcpy(instances + at_inst, p.blob.data() + s.pos, (size_t)cnt * sizeof(LmxImInstance));
+		s.skip((size_t)cnt * 32);
+		at_inst += cnt;
 	}
 	return s.overflow ? LMX_ERR_INVALID_ARGUMENT : LMX_OK;
 }
