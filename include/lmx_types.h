@@ -155,6 +155,48 @@ typedef struct LmxKeysView {
 	uint8_t bucket_depth_sorted[256]; /* buckets[b].sort == BucketDesc::DEPTH */
 } LmxKeysView;
 
+/* ---- createCommands outputs (renderer/pipeline.cpp:2747-3320) ---- */
+
+/* Kind of a run = DrawCommandTypes of its first pair; a MESH run whose head carries ModelInstance::MOVED is LMX_RUN_MOVED_MESH. */
+enum {
+	LMX_RUN_MESH = 0,          /* 48 B records: rot[4], lpos[3], lod_d, scale[3], material_index (:3098-3117) */
+	LMX_RUN_AUTOINSTANCED = 1, /* no records of its own: the group's 48 B records lie in the group buffer (:3992-4010) */
+	LMX_RUN_SKINNED = 2,       /* 92 B (:3146-3181) */
+	LMX_RUN_DECAL = 3,         /* 52 B, front part / back part (:3202-3227) */
+	LMX_RUN_CURVE_DECAL = 4,   /* 68 B (:3263-3290) */
+	LMX_RUN_MOVED_MESH = 32    /* 96 B (:3053-3080); outside the 5 bits of a pair type, so no unhandled type can collide with it */
+};
+
+/* One run = one draw call of createCommands, in pair order. sizeof == 48. */
+typedef struct LmxDrawRun {
+	uint32_t kind;        /* LMX_RUN_* (a pair type lmx_keys_run never emits: that type, stride 0, one pair) */
+	uint32_t bucket;      /* key >> 56 */
+	uint32_t batch;       /* the slice of the pairs (substream) the run lies in */
+	uint32_t first_pair, pair_count;
+	uint32_t data_offset; /* bytes, 16-aligned: into the instance buffer; AUTOINSTANCED: into the group buffer (48 * offsets[group]) */
+	uint32_t stride;      /* bytes per record */
+	uint32_t head_entity; /* entity of the first pair; AUTOINSTANCED: of the group's first renderable (:3010-3011) */
+	uint32_t mesh_idx;    /* of the first pair / of the group's first renderable */
+	uint32_t front_count; /* decal runs: records [0, front_count) do not intersect the near plane, the rest do; else pair_count */
+	uint32_t group;       /* AUTOINSTANCED: group index (mesh sort key) */
+	uint32_t total_count; /* AUTOINSTANCED: records of the group; else pair_count */
+} LmxDrawRun;
+
+/* The per-view state createCommands reads: view.cp.pos, view.cp.frustum, buckets[b].sort == BucketDesc::DEPTH */
+typedef struct LmxDrawView {
+	double camera_pos[3];
+	LmxShiftedFrustum frustum;
+	uint8_t bucket_depth_sorted[256];
+} LmxDrawView;
+
+typedef struct LmxDrawCounts {
+	uint32_t pairs;          /* pairs walked */
+	uint32_t runs;
+	uint32_t instance_bytes; /* bytes of the instance buffer in use (slices are 16-byte aligned) */
+	uint32_t group_records;  /* 48-byte records in the group buffer (= the instancer CSR's total) */
+	uint32_t overflow;       /* != 0: an output buffer was too small (never with library-sized buffers) */
+} LmxDrawCounts;
+
 /* ---- animation sampling inputs (animation/animation.h:86-115, animation.cpp:29-204) ---- */
 
 typedef struct LmxAnimConstTranslation { /* Animation::ConstTranslationTrack */

@@ -79,6 +79,11 @@ KEYS_VIEW = np.dtype(
     align=True,
 )
 KEYS_COUNTS = np.dtype([("pairs", "<u4"), ("instanced", "<u4"), ("groups", "<u4"), ("poses", "<u4"), ("dirty", "<u4"), ("overflow", "<u4")])
+DRAW_RUN = np.dtype([(k, "<u4") for k in ("kind", "bucket", "batch", "first_pair", "pair_count", "data_offset", "stride", "head_entity", "mesh_idx", "front_count",
+                                          "group", "total_count")])  # LmxDrawRun
+DRAW_VIEW = np.dtype([("camera_pos", "<f8", 3), ("frustum", SHIFTED_FRUSTUM), ("bucket_depth_sorted", "u1", 256)], align=True)  # LmxDrawView
+DRAW_COUNTS = np.dtype([("pairs", "<u4"), ("runs", "<u4"), ("instance_bytes", "<u4"), ("group_records", "<u4"), ("overflow", "<u4")])
+RUN_MESH, RUN_AUTOINSTANCED, RUN_SKINNED, RUN_DECAL, RUN_CURVE_DECAL, RUN_MOVED_MESH = 0, 1, 2, 3, 4, 32
 VIEWPORT = np.dtype(
     [("is_ortho", "<i4"), ("fov", "<f4"), ("ortho_size", "<f4"), ("w", "<i4"), ("h", "<i4"), ("pos", "<f8", 3), ("rot", "<f4", 4), ("near_plane", "<f4"), ("far_plane", "<f4")],
     align=True,
@@ -205,6 +210,20 @@ SYMBOLS = {
     "lmx_keys_read_dirty": (_ci, [_vp, _vp, _u32]),
     "lmx_keys_read_state": (_ci, [_vp, _vp, _vp, _u32]),
     "lmx_keys_device_pairs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "lmx_draw_set_meshes": (_ci, [_vp, _vp, _u32]),
+    "lmx_draw_set_material_indices": (_ci, [_vp, _vp, _u32]),
+    "lmx_draw_set_transforms": (_ci, [_vp, _vp, _u32]),
+    "lmx_draw_bind_world": (_ci, [_vp, _ci]),
+    "lmx_draw_set_prev_transforms": (_ci, [_vp, _vp, _u32]),
+    "lmx_draw_set_bones": (_ci, [_vp, _vp, _vp, _u32]),
+    "lmx_draw_set_decals": (_ci, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmx_draw_run": (_ci, [_vp, _vp, _u32]),
+    "lmx_draw_run_pairs": (_ci, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32]),
+    "lmx_draw_counts": (_ci, [_vp, _vp]),
+    "lmx_draw_read_runs": (_ci, [_vp, _vp, _u32]),
+    "lmx_draw_read_instance_data": (_ci, [_vp, _vp, _sz]),
+    "lmx_draw_read_group_data": (_ci, [_vp, _vp, _sz]),
+    "lmx_draw_device_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "lmx_viewport_frustum": (_ci, [_vp, _vp]),
     "lmx_frustum_perspective": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "lmx_frustum_ortho": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
@@ -996,6 +1015,98 @@ class SortKeys:
         lod, frame = np.zeros(self.n_entities, np.float32), np.zeros(self.n_entities, np.uint32)
         self.ctx.check(self.lib.lmx_keys_read_state(self.ctx.h, _ptr(lod), _ptr(frame), self.n_entities))
         return lod, frame
+
+
+def draw_view(camera_pos=(0, 0, 0), frustum=None, bucket_depth_sorted=None) -> np.ndarray:
+    """LmxDrawView: what PipelineImpl::createCommands reads of a view (pipeline.cpp:2758-2761, :2824)."""
+    v = np.zeros(1, DRAW_VIEW)
+    v["camera_pos"] = camera_pos
+    if frustum is not None:
+        v["frustum"] = np.ascontiguousarray(frustum, SHIFTED_FRUSTUM).reshape(-1)[0]
+    if bucket_depth_sorted is not None:
+        v["bucket_depth_sorted"][0, : len(bucket_depth_sorted)] = np.asarray(bucket_depth_sorted, np.uint8)
+    return v
+
+
+class DrawCommands:
+    """PipelineImpl::createCommands (renderer/pipeline.cpp:2747-3320) + the instancer's "fill instance data" block (:3970-4014) on the
+    sorted pairs a SortKeys run left on the device (lmx_draw_*)."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+
+    def setMeshes(self, mesh_lod):
+        a = np.ascontiguousarray(mesh_lod, np.float32)
+        self.ctx.check(self.lib.lmx_draw_set_meshes(self.ctx.h, _ptr(a), len(a)))
+
+    def setMaterialIndices(self, material_index):
+        a = np.ascontiguousarray(material_index, np.uint32)
+        self.ctx.check(self.lib.lmx_draw_set_material_indices(self.ctx.h, _ptr(a), len(a)))
+
+    def setTransforms(self, transforms):
+        a = np.ascontiguousarray(transforms, TRANSFORM)
+        self.ctx.check(self.lib.lmx_draw_set_transforms(self.ctx.h, _ptr(a), len(a)))
+
+    def bindWorld(self, on: bool = True):
+        self.ctx.check(self.lib.lmx_draw_bind_world(self.ctx.h, int(on)))
+
+    def setPrevTransforms(self, transforms):
+        a = np.ascontiguousarray(transforms, TRANSFORM)
+        self.ctx.check(self.lib.lmx_draw_set_prev_transforms(self.ctx.h, _ptr(a), len(a)))
+
+    def setBones(self, handle, offset):
+        h, o = np.ascontiguousarray(handle, np.uint32), np.ascontiguousarray(offset, np.uint32)
+        self.ctx.check(self.lib.lmx_draw_set_bones(self.ctx.h, _ptr(h), _ptr(o), len(h)))
+
+    def setDecals(self, n_entities, half_extents=None, uv_scale=None, material_index=None, curve_half_extents=None, curve_uv_scale=None, curve_bezier=None,
+                  curve_material_index=None):
+        a = [None if x is None else np.ascontiguousarray(x, t) for x, t in ((half_extents, np.float32), (uv_scale, np.float32), (material_index, np.uint32),
+                                                                             (curve_half_extents, np.float32), (curve_uv_scale, np.float32),
+                                                                             (curve_bezier, np.float32), (curve_material_index, np.uint32))]
+        self.ctx.check(self.lib.lmx_draw_set_decals(self.ctx.h, n_entities, *[None if x is None else _ptr(x) for x in a]))
+
+    def run(self, view, n_batches: int = 1):
+        view = np.ascontiguousarray(view, DRAW_VIEW)
+        self.ctx.check(self.lib.lmx_draw_run(self.ctx.h, _ptr(view), n_batches))
+
+    def runPairs(self, view, keys, values, n_batches: int = 1, group_offsets=None, group_values=None):
+        """group_offsets (n_groups + 1 entries) / group_values: the instancer CSR to encode with the pairs; None: no instancer."""
+        view = np.ascontiguousarray(view, DRAW_VIEW)
+        k, v = np.ascontiguousarray(keys, np.uint64), np.ascontiguousarray(values, np.uint64)
+        n_groups = 0 if group_offsets is None else len(group_offsets) - 1
+        go = None if n_groups <= 0 else np.ascontiguousarray(group_offsets, np.uint32)
+        gv = None if n_groups <= 0 else np.ascontiguousarray(group_values, np.uint64)
+        self.ctx.check(self.lib.lmx_draw_run_pairs(self.ctx.h, _ptr(view), n_batches, _ptr(k) if len(k) else None, _ptr(v) if len(k) else None, len(k),
+                                                   _ptr(go), _ptr(gv) if gv is not None and len(gv) else None, max(n_groups, 0)))
+
+    def counts(self) -> dict:
+        c = np.zeros(1, DRAW_COUNTS)
+        self.ctx.check(self.lib.lmx_draw_counts(self.ctx.h, _ptr(c)))
+        return {k: int(c[k][0]) for k in DRAW_COUNTS.names}
+
+    def readRuns(self) -> np.ndarray:
+        n = self.counts()["runs"]
+        out = np.zeros(max(n, 1), DRAW_RUN)
+        self.ctx.check(self.lib.lmx_draw_read_runs(self.ctx.h, _ptr(out), len(out)))
+        return out[:n]
+
+    def readInstanceData(self) -> np.ndarray:
+        n = self.counts()["instance_bytes"]
+        out = np.zeros(max(n, 1), np.uint8)
+        self.ctx.check(self.lib.lmx_draw_read_instance_data(self.ctx.h, _ptr(out), len(out)))
+        return out[:n]
+
+    def readGroupData(self) -> np.ndarray:
+        n = self.counts()["group_records"] * 48
+        out = np.zeros(max(n, 1), np.uint8)
+        self.ctx.check(self.lib.lmx_draw_read_group_data(self.ctx.h, _ptr(out), len(out)))
+        return out[:n]
+
+    def deviceOutputs(self):
+        r, i, g, c = _vp(), _vp(), _vp(), _vp()
+        self.ctx.check(self.lib.lmx_draw_device_outputs(self.ctx.h, C.byref(r), C.byref(i), C.byref(g), C.byref(c)))
+        return r.value, i.value, g.value, c.value
 
 
 SKIN_FUSED, SKIN_EXACT, SKIN_DQS = 0, 1, 2

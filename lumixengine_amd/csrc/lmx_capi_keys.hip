@@ -483,6 +483,8 @@ int lmx_keys_sort(LmxContext* ctx) {
 		LMX_HIP(ctx, hipMemcpyAsync(ks.d_values.p, ks.d_values_alt.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
 	}
 	ks.sorted = true;
+	ks.n_sorted = n;
+	ks.n_sorted_recs = c[KEYS_N_RECS];
 	return LMX_OK;
 }
 

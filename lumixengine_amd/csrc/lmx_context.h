@@ -454,6 +454,28 @@ struct KeysState {
 	}
 	DevBuf<uint32_t> d_mm_count, d_mm_off;
 	DevBuf<char> d_scan_temp;
+	uint32_t n_sorted = 0, n_sorted_recs = 0; // pairs / instancer renderables of the run lmx_keys_sort last sorted (lmx_draw_run)
+};
+
+// createCommands (lmx_capi_draw.hip): the tables the records need beyond the sort-key tables, scratch and outputs of the last run
+struct DrawState {
+	DevBuf<float> d_mesh_lod;
+	DevBuf<uint32_t> d_material_index, d_bones_handle, d_bones_offset;
+	DevBuf<LmxTransform> d_tr, d_prev;
+	DevBuf<DrawDecalRec> d_decals;
+	DevBuf<DrawCurveRec> d_curves;
+	uint32_t n_meshes = 0, n_material_index = 0, n_tr = 0, n_prev = 0, n_bones = 0, n_decals = 0, n_curves = 0;
+	bool have_decals = false, have_curves = false, use_world = false;
+	DevBuf<uint64_t> d_keys, d_values, d_group_values; // lmx_draw_run_pairs: the caller's pairs and instancer CSR
+	DevBuf<uint32_t> d_group_offset;
+	DevBuf<uint8_t> d_flags, d_tile_fn, d_tile_in;
+	DevBuf<uint32_t> d_words;          // seven arrays of n + 1 words (DrawDevice scratch)
+	DevBuf<char> d_scan_temp;
+	DevBuf<LmxDrawRun> d_runs;
+	DevBuf<uint8_t> d_instance_data, d_group_data;
+	DevBuf<uint32_t> d_counts;
+	bool ran = false;
+	uint32_t n = 0, n_group_values = 0; // of the last run
 };
 
 // animation sampling (lmx_capi_anim.hip): Animation resources flattened into concatenated tables, one Animable per skin instance
@@ -506,6 +528,7 @@ struct LmxContext {
 	lmx::WorldState world;
 	lmx::SkinState skin;
 	lmx::KeysState keys;
+	lmx::DrawState draw;
 	lmx::AnimState anim;
 };
 

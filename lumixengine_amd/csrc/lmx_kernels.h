@@ -344,6 +344,52 @@ hipError_t launch_keys_mirror_carry(hipStream_t s, const PatchId* patches, uint3
 uint32_t keys_mesh_grid_cap(); // the largest grid of k_keys_mesh = the rows a block-ranks table needs
 hipError_t launch_keys(hipStream_t s, const KeysDevice& d, const KeysViewDevice& view, const KeysShardList& meshes, const KeysShardList& decals, const KeysShardList& curves);
 
+// ---- createCommands (draw_kernels.hip): runs + instance records from the sorted pairs, the instancer groups' records ----
+struct DrawDecalRec { float half_extents[3]; float uv_scale[2]; uint32_t material_index; uint32_t pad[2]; };               // 32 B
+struct DrawCurveRec { float half_extents[3]; float uv_scale[2]; float bezier[4]; uint32_t material_index; uint32_t pad[2]; }; // 48 B
+struct DrawViewDevice {
+	double cam[3];
+	double origin[3];       // ShiftedFrustum::origin
+	float nx, ny, nz, nd;   // the NEAR plane (intersectNearPlane, core/geometry.cpp:38-46)
+	uint32_t depth_sorted[8]; // bit b: buckets[b].sort == BucketDesc::DEPTH
+};
+struct DrawDevice {
+	// inputs: the sorted pairs, the instancer CSR
+	const uint64_t *keys, *values;
+	uint32_t n, step;          // pairs; pairs per batch = ceil(n / n_batches)
+	const uint32_t* group_offset; // [n_groups + 1], nullptr: no instancer
+	const uint64_t* group_values;
+	uint32_t n_groups, n_group_values;
+	// tables by entity index (every one may be shorter than the entity ids met: what an entity lacks reads as zero)
+	const KeysInstance* inst; uint32_t n_entities;
+	const LmxKeysModel* models; uint32_t n_models;
+	const float* mesh_lod; uint32_t n_meshes;
+	const uint32_t* material_index; uint32_t n_mesh_materials;
+	const LmxTransform* tr; uint32_t n_tr;       // uploaded transforms, or (tr == nullptr) the world hierarchy in place:
+	const double *wpx, *wpy, *wpz; const float4* wrot; const float *wsx, *wsy, *wsz; const int32_t* slot_of_entity; uint32_t n_world;
+	const LmxTransform* prev; uint32_t n_prev;
+	const uint32_t *bones_handle, *bones_offset; uint32_t n_bones;
+	const DrawDecalRec* decals; uint32_t n_decals;
+	const DrawCurveRec* curves; uint32_t n_curves;
+	// scratch
+	uint8_t* flags;        // [n] DRAW_F_*
+	uint8_t *tile_fn, *tile_in; // [tiles]
+	uint32_t *head, *run_of;   // [n + 1] head flag, its exclusive sum (run_of[n] = runs)
+	uint32_t *front, *front_sum; // [n + 1] decal runs: the pair goes to the front part; exclusive sum
+	uint32_t *run_start;   // [n + 1] first pair of run r; run_start[runs] = n
+	uint32_t *run_bytes, *run_offset; // [n + 1] 16-byte aligned slice sizes (zero behind the last run), exclusive sum
+	// outputs
+	LmxDrawRun* runs;
+	uint8_t* instance_data;
+	uint8_t* group_data;
+	uint32_t* counts;      // {runs, instance bytes, pairs, group records}
+};
+constexpr uint32_t DRAW_TILE = 256;
+hipError_t launch_draw_flags(hipStream_t s, const DrawDevice& d, const DrawViewDevice& v);   // flags + tile functions + tile scan + head flags
+hipError_t launch_draw_runs(hipStream_t s, const DrawDevice& d, const DrawViewDevice& v);    // (behind the sum of head) run starts, near-plane bits, slice sizes
+hipError_t launch_draw_encode(hipStream_t s, const DrawDevice& d, const DrawViewDevice& v);  // (behind the sums of front / run_bytes) run + instance records
+hipError_t launch_draw_groups(hipStream_t s, const DrawDevice& d, const DrawViewDevice& v);  // the "fill instance data" block
+
 // Pose::computeAbsolute + computeSkinMatrices (+ optional dual-quaternion palette), one wave per PoseGroup
 hipError_t launch_pose_palette(hipStream_t s, const SkinInstance* inst, const PoseGroup* groups, const uint32_t n_groups[3] /* by capacity 4, 2, 1 */,
 	const float* rel_pos, const float4* rel_rot, float* pose_pos, float4* pose_rot, const uint32_t* level_items, const uint16_t* level_off,

@@ -242,6 +242,22 @@ def keys_scene(n_entities: int, types: np.ndarray, seed: int = 11, n_models: int
             "bucket_depth_sorted": bucket_depth_sorted, "max_sort_key": max_sort_key}
 
 
+def draw_tables(ks: dict, n_entities: int, seed: int = 17, extent: float = 3000.0):
+    """What createCommands reads beyond keys_scene(): Mesh::lod per mesh, MeshMaterial::material_index per mesh material, previous-frame
+    transforms, bones slices, decal / curve-decal payloads (by entity index)."""
+    rng = np.random.default_rng(seed)
+    n_meshes, n_mm = len(ks["mesh_types"]), len(ks["mesh_materials"])
+    prev = random_transforms(rng, n_entities, extent)
+    return {"mesh_lod": rng.integers(0, 4, size=n_meshes).astype(np.float32), "material_index": rng.integers(0, 1 << 16, size=n_mm).astype(np.uint32),
+            "prev": prev, "bones_handle": rng.integers(1, 1 << 20, size=n_entities).astype(np.uint32),
+            "bones_offset": (rng.integers(0, 1 << 16, size=n_entities) * 64).astype(np.uint32),
+            "half_extents": rng.uniform(0.1, 30.0, size=(n_entities, 3)).astype(np.float32), "uv_scale": rng.uniform(0.5, 4.0, size=(n_entities, 2)).astype(np.float32),
+            "decal_material": rng.integers(0, 1 << 16, size=n_entities).astype(np.uint32),
+            "curve_half_extents": rng.uniform(0.1, 30.0, size=(n_entities, 3)).astype(np.float32),
+            "curve_uv_scale": rng.uniform(0.5, 4.0, size=(n_entities, 2)).astype(np.float32), "curve_bezier": rng.uniform(-5.0, 5.0, size=(n_entities, 4)).astype(np.float32),
+            "curve_material": rng.integers(0, 1 << 16, size=n_entities).astype(np.uint32)}
+
+
 def animation(n_bones: int = 64, frame_count: int = 30, fps: float = 30.0, seed: int = 21, root_motion: bool = True, bone_limit: int | None = None):
     """A compressed animation in the layout AnimationSampler reads (animation/animation.h:86-115): per bone a constant or a
     bit-packed translation track (or none) and a constant or bit-packed rotation track (3 channels + sign bit, the largest
