@@ -43,14 +43,7 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 	if ((uint64_t)n * 96 + 16 > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "%u pairs: the instance buffer's offsets are 32 bits", n);
 	if ((uint64_t)n_group_values * 48 + 16 > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "%u instanced renderables: the group buffer's offsets are 32 bits", n_group_values);
 	if (ds.use_world && ctx->world.slot_of_entity.empty()) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
-	if (ks.inst_dirty) { // as lmx_keys_run: the host mirror of the per-entity records changed
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, ks.d_inst.reserve(std::max<size_t>(ks.inst.size(), 1)));
-		if (!ks.inst.empty()) LMX_HIP(ctx, hipMemcpyAsync(ks.d_inst.p, ks.inst.data(), ks.inst.size() * sizeof(KeysInstance), hipMemcpyHostToDevice, ctx->stream));
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		ks.inst_dirty = false;
-		ks.inst_uploaded = ks.inst.size();
-	}
+	if (int rc = keys_upload_instances(ctx)) return rc; // as lmx_keys_run
 	// ModelInstance::lod of the sorted set's entities lives in the slot-ordered mirror: hand it to the entity-indexed records the encode
 	// reads (what lmx_keys_read_state does; the mirror stays valid)
 	if (ks.mirror_valid)

@@ -68,6 +68,18 @@ int keys_before_layout_change(LmxContext* ctx) {
 	return LMX_OK;
 }
 
+// The host mirror of the per-entity records goes up if it changed (tables or positions): lod / Pose::frame restart from the uploaded values.
+int keys_upload_instances(LmxContext* ctx) {
+	KeysState& ks = ctx->keys;
+	if (!ks.inst_dirty) return LMX_OK;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload(ctx, ks.d_inst, ks.inst.data(), ks.inst.size())) return rc;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	ks.inst_dirty = false;
+	ks.inst_uploaded = ks.inst.size();
+	return LMX_OK;
+}
+
 // These id patches are about to turn slots into tombstones (removal, move to the overflow set): the state follows the entity.
 int keys_before_tombstones(LmxContext* ctx, const PatchId* d_patches, uint32_t n) {
 	KeysState& ks = ctx->keys;
@@ -330,13 +342,7 @@ int lmx_keys_run(LmxContext* ctx, uint32_t view, uint32_t frustum, const LmxKeys
 	LMX_HIP(ctx, ks.d_poses.reserve(std::max<size_t>(mesh_cap, 1)));
 	LMX_HIP(ctx, ks.d_dirty_list.reserve(std::max<size_t>(mesh_cap, 1)));
 
-	if (ks.inst_dirty) { // the host mirror changed (tables or positions): lod / Pose::frame restart from the uploaded values
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		if (int rc = upload(ctx, ks.d_inst, ks.inst.data(), ks.inst.size())) return rc;
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		ks.inst_dirty = false;
-		ks.inst_uploaded = ks.inst.size();
-	}
+	if (int rc = keys_upload_instances(ctx)) return rc;
 	// slot order: from now on the culls also emit the static-set slot of every visible id; a view culled before that (or with the
 	// option off) is walked through the entity-indexed tables
 	CullState& cs = ctx->cull;

@@ -34,6 +34,14 @@ template <typename T> struct DevBuf {
 	DevBuf() = default;
 	DevBuf(const DevBuf&) = delete;
 	DevBuf& operator=(const DevBuf&) = delete;
+	DevBuf(DevBuf&& o) noexcept { swap(o); }
+	DevBuf& operator=(DevBuf&& o) noexcept {
+		if (this != &o) {
+			release();
+			swap(o);
+		}
+		return *this;
+	}
 	void swap(DevBuf& o) {
 		std::swap(p, o.p);
 		std::swap(cap, o.cap);
@@ -116,7 +124,7 @@ struct DynRec {
 	double pos[3];
 	float radius;
 	int32_t entity;
-	uint32_t slot;  // device slot, DYN_NO_SLOT until the next rebuild_dynamic when the type's region was full
+	uint32_t slot;  // device slot, DYN_NO_SLOT until the next rebuild_dynamic_on when the type's region was full
 	uint8_t type;
 	bool bound;     // refreshed on the device by lmx_world_propagate (never folded back into the static set)
 };
@@ -133,6 +141,11 @@ struct PatchStaging {
 	PatchStaging() = default;
 	PatchStaging(const PatchStaging&) = delete;
 	PatchStaging& operator=(const PatchStaging&) = delete;
+	PatchStaging(PatchStaging&& o) noexcept { swap(o); }
+	PatchStaging& operator=(PatchStaging&& o) noexcept { // (the halves this one held go with `o`)
+		swap(o);
+		return *this;
+	}
 	void swap(PatchStaging& o) {
 		for (int i = 0; i < 2; ++i) {
 			std::swap(host[i], o.host[i]);
@@ -152,7 +165,8 @@ struct PatchStaging {
 
 // One complete copy of the culling sets: host mirror + device layout of the static set, the dynamic set, the pending patch queues.
 // A context has ONE live set (CullState derives from it); with LMX_CULL_OPT_ASYNC_COMPACTION a second, shadow set exists that a worker
-// thread re-sorts in the background (lmx_capi_cull.hip, "asynchronous compaction") and that trades places with the live one in O(1).
+// thread re-sorts in the background (lmx_capi_cull_async.hip) and that trades places with the live one in O(1): the struct is movable
+// as a whole (vectors and device buffers move their storage), so a member added here takes part in the swap without further ado.
 struct CullSet {
 	// ---- static set: host mirror (one CullRec per entity) + sorted device layout -------------------------------
 	std::vector<CullRec> recs;
@@ -198,60 +212,9 @@ struct CullSet {
 	std::vector<uint32_t> q_sphere_at; // static slot -> index into q_sphere, ~0u = no pending record (a hash map here cost 0.7 us per set)
 	std::vector<uint32_t> q_dyn_at;                     // dynamic slot -> index into q_dyn, or ~0u
 	PatchStaging staging;
-	// everything above trades places with `o` (O(1): vectors and device buffers swap their storage)
-	void swap_with(CullSet& o) {
-		recs.swap(o.recs);
-		ent_to_rec.swap(o.ent_to_rec);
-		rec_slot.swap(o.rec_slot);
-		std::swap(structure_dirty, o.structure_dirty);
-		std::swap(built, o.built);
-		std::swap(n_tombstones, o.n_tombstones);
-		spheres.swap(o.spheres);
-		ids.swap(o.ids);
-		hdr.swap(o.hdr);
-		for (int k = 0; k < 3; ++k) {
-			tile_cells[k].swap(o.tile_cells[k]);
-			tile_tab[k].swap(o.tile_tab[k]);
-			tile_box[k].swap(o.tile_box[k]);
-			std::swap(tile_cap[k], o.tile_cap[k]);
-			std::swap(max_tile_cells[k], o.max_tile_cells[k]);
-			std::swap(scene_lo[k], o.scene_lo[k]);
-			std::swap(scene_hi[k], o.scene_hi[k]);
-		}
-		std::swap(keys_packed, o.keys_packed);
-		std::swap(n_padded, o.n_padded);
-		std::swap(n_cells, o.n_cells);
-		std::swap(n_dead_cells, o.n_dead_cells);
-		block_live.swap(o.block_live);
-		std::swap(big_tile_fraction, o.big_tile_fraction);
-		std::swap(tt, o.tt);
-		dyn.swap(o.dyn);
-		ent_to_dyn.swap(o.ent_to_dyn);
-		std::swap(n_unbound, o.n_unbound);
-		std::swap(dyn_layout_dirty, o.dyn_layout_dirty);
-		std::swap(dyn_mirror_stale, o.dyn_mirror_stale);
-		dyn_px.swap(o.dyn_px);
-		dyn_py.swap(o.dyn_py);
-		dyn_pz.swap(o.dyn_pz);
-		dyn_radius.swap(o.dyn_radius);
-		dyn_ids.swap(o.dyn_ids);
-		std::swap(dyn_padded, o.dyn_padded);
-		std::swap(dyn_tt, o.dyn_tt);
-		for (int t = 0; t < MAX_TYPES; ++t) {
-			std::swap(dyn_next[t], o.dyn_next[t]);
-			dyn_free[t].swap(o.dyn_free[t]);
-		}
-		std::swap(dyn_generation, o.dyn_generation);
-		q_sphere.swap(o.q_sphere);
-		q_id.swap(o.q_id);
-		q_dyn.swap(o.q_dyn);
-		q_sphere_at.swap(o.q_sphere_at);
-		q_dyn_at.swap(o.q_dyn_at);
-		staging.swap(o.staging);
-	}
 };
 
-struct CullAsync; // lmx_capi_cull.hip
+struct CullAsync; // lmx_cull_host.h
 
 struct CullState : CullSet {
 	// ---- output shards ----------------------------------------------------------------------------------------
@@ -270,7 +233,7 @@ struct CullState : CullSet {
 	uint32_t compaction_min = 1u << 16; // overflow entities / tombstones tolerated before a compaction is considered at all (LMX_CULL_OPT_COMPACTION_MIN)
 	bool map_zero_copy = true;   // LMX_CULL_OPT_MAP_ZERO_COPY: small host records are written by the pack kernel straight into pinned host memory
 	uint32_t map_zero_copy_max = 1u << 20; // ... for views whose lists held at most this many ids last frame
-	CullAsync* async = nullptr;  // LMX_CULL_OPT_ASYNC_COMPACTION: shadow set + worker thread (owned; lmx_capi_cull.hip)
+	CullAsync* async = nullptr;  // LMX_CULL_OPT_ASYNC_COMPACTION: shadow set + worker thread (owned; lmx_capi_cull_async.hip). Raw: a unique_ptr to the incomplete type would need an out-of-line constructor AND destructor of CullState
 	bool emit_slots = false;     // culls also write the static-set slot of every visible id (switched on by the sort-key tables' slot-ordered mirror)
 	uint64_t layout_generation = 0; // a process-wide unique number per build of the static layout (consumers that mirror it by slot compare)
 	uint32_t max_shards = LAYOUT_MAX_SHARDS; // output shards per type of the static set
@@ -536,15 +499,16 @@ namespace lmx {
 
 int fail(LmxContext* ctx, int code, const char* fmt, ...); // records the message, returns `code`
 extern thread_local std::string* t_fail_sink; // non-null on a library-owned thread: fail() writes there instead of LmxContext::error
-void cull_async_shutdown(LmxContext* ctx);   // lmx_capi_cull.hip: stop the asynchronous compaction's worker (context teardown)
+void cull_async_shutdown(LmxContext* ctx);   // lmx_capi_cull_async.hip: stop the asynchronous compaction's worker (context teardown)
 int keys_before_layout_change(LmxContext* ctx); // lmx_capi_keys.hip: the slot-ordered mirror of the sort-key tables hands its state back (the static layout is about to change)
 int keys_before_tombstones(LmxContext* ctx, const PatchId* d_patches, uint32_t n); // ... for the slots of these id patches (device-visible records; enqueued BEFORE the patch kernel)
+int keys_upload_instances(LmxContext* ctx); // ... the host mirror of the per-entity records goes up if it changed (lmx_keys_run, the draw pass)
 void prof_drain(LmxContext* ctx);
 int cull_flush(LmxContext* ctx);          // lmx_capi_cull.hip: make the device copy of the culling sets current
-int cull_dyn_sync_mirror(LmxContext* ctx); // dyn[] <- device when lmx_world_propagate refreshed it
-bool cull_make_dynamic(LmxContext* ctx, int32_t entity); // move an entity to the dynamic set and mark it as bound to the hierarchy
+int cull_dyn_sync_mirror(LmxContext* ctx); // lmx_capi_cull.hip: dyn[] <- device when lmx_world_propagate refreshed it
+bool cull_make_dynamic(LmxContext* ctx, int32_t entity); // lmx_capi_cull_set.hip: move an entity to the dynamic set and mark it as bound to the hierarchy
 void cull_unbind(LmxContext* ctx, int32_t entity);       // the entity is no longer refreshed by lmx_world_propagate
-int cull_view_finalize(LmxContext* ctx, CullView& v);    // per-type totals of the view's result
+int cull_view_finalize(LmxContext* ctx, CullView& v);    // lmx_capi_cull_results.hip: per-type totals of the view's result
 int cull_view_consolidate(LmxContext* ctx, CullView& v); // + one contiguous id list per (frustum, type)
 
 #define LMX_HIP(ctx, expr)                                                                                             \
