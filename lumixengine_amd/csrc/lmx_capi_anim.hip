@@ -7,28 +7,22 @@ using namespace lmx;
 
 namespace {
 
-template <typename T> int upload_vec(LmxContext* ctx, DevBuf<T>& buf, const std::vector<T>& v) {
-	LMX_HIP(ctx, buf.reserve(std::max<size_t>(v.size(), 1)));
-	if (!v.empty()) LMX_HIP(ctx, hipMemcpy(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-	return LMX_OK;
-}
-
 int anim_upload_tables(LmxContext* ctx) {
 	AnimState& an = ctx->anim;
 	if (!an.tables_dirty) return LMX_OK;
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (int rc = upload_vec(ctx, an.d_anims, an.anims)) return rc;
-	if (int rc = upload_vec(ctx, an.d_src, an.src)) return rc;
-	if (int rc = upload_vec(ctx, an.d_ct, an.ct)) return rc;
-	if (int rc = upload_vec(ctx, an.d_tt, an.tt)) return rc;
-	if (int rc = upload_vec(ctx, an.d_cr, an.cr)) return rc;
-	if (int rc = upload_vec(ctx, an.d_rt, an.rt)) return rc;
-	if (int rc = upload_vec(ctx, an.d_tstream, an.tstream)) return rc;
-	if (int rc = upload_vec(ctx, an.d_rstream, an.rstream)) return rc;
-	if (int rc = upload_vec(ctx, an.d_root_t, an.root_t)) return rc;
-	if (int rc = upload_vec(ctx, an.d_root_r, an.root_r)) return rc;
-	if (int rc = upload_vec(ctx, an.d_rel_pos, an.rel_pos)) return rc;
-	if (int rc = upload_vec(ctx, an.d_rel_rot, an.rel_rot)) return rc;
+	LMX_HIP(ctx, upload_blocking(an.d_anims, an.anims));
+	LMX_HIP(ctx, upload_blocking(an.d_src, an.src));
+	LMX_HIP(ctx, upload_blocking(an.d_ct, an.ct));
+	LMX_HIP(ctx, upload_blocking(an.d_tt, an.tt));
+	LMX_HIP(ctx, upload_blocking(an.d_cr, an.cr));
+	LMX_HIP(ctx, upload_blocking(an.d_rt, an.rt));
+	LMX_HIP(ctx, upload_blocking(an.d_tstream, an.tstream));
+	LMX_HIP(ctx, upload_blocking(an.d_rstream, an.rstream));
+	LMX_HIP(ctx, upload_blocking(an.d_root_t, an.root_t));
+	LMX_HIP(ctx, upload_blocking(an.d_root_r, an.root_r));
+	LMX_HIP(ctx, upload_blocking(an.d_rel_pos, an.rel_pos));
+	LMX_HIP(ctx, upload_blocking(an.d_rel_rot, an.rel_rot));
 	an.tables_dirty = false;
 	return LMX_OK;
 }
@@ -144,10 +138,8 @@ int lmx_anim_set_animables(LmxContext* ctx, uint32_t n_instances, const uint32_t
 	LMX_HIP(ctx, an.d_anim_of.reserve(std::max<size_t>(n_instances, 1)));
 	LMX_HIP(ctx, an.d_time_of.reserve(std::max<size_t>(n_instances, 1)));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (n_instances) {
-		LMX_HIP(ctx, hipMemcpy(an.d_anim_of.p, animation, (size_t)n_instances * sizeof(uint32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(an.d_time_of.p, time, (size_t)n_instances * sizeof(uint32_t), hipMemcpyHostToDevice));
-	}
+	LMX_HIP(ctx, upload_blocking(an.d_anim_of.p, animation, n_instances));
+	LMX_HIP(ctx, upload_blocking(an.d_time_of.p, time, n_instances));
 	an.n_animables = n_instances;
 	return LMX_OK;
 }
@@ -202,8 +194,8 @@ int lmx_anim_eval_blend_stacks(LmxContext* ctx, uint32_t n_instances, const uint
 	LMX_HIP(ctx, an.d_samples.reserve(std::max<size_t>(n_samples, 1)));
 	// the caller's arrays are pageable: the copies below complete before this returns, and the stream orders them against the
 	// previous frame's kernel that still reads the same device buffers
-	LMX_HIP(ctx, hipMemcpyAsync(an.d_first_sample.p, first_sample, ((size_t)n_instances + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-	if (n_samples) LMX_HIP(ctx, hipMemcpyAsync(an.d_samples.p, samples, (size_t)n_samples * sizeof(LmxBlendSample), hipMemcpyHostToDevice, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(an.d_first_sample.p, first_sample, (size_t)n_instances + 1, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(an.d_samples.p, samples, n_samples, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	AnimTables t;
 	t.src = an.d_src.p; t.const_translations = an.d_ct.p; t.translations = an.d_tt.p; t.const_rotations = an.d_cr.p; t.rotations = an.d_rt.p;
@@ -222,7 +214,7 @@ int lmx_anim_read_times(LmxContext* ctx, uint32_t* time, uint32_t n_instances) {
 	LMX_CHECK_CTX(ctx);
 	AnimState& an = ctx->anim;
 	if (n_instances != an.n_animables || (n_instances && !time)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "expected %u animables", an.n_animables);
-	if (n_instances) LMX_HIP(ctx, hipMemcpyAsync(time, an.d_time_of.p, (size_t)n_instances * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(time, an.d_time_of.p, n_instances, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -234,8 +226,8 @@ int lmx_anim_read_pose(LmxContext* ctx, uint32_t instance, float* out_pos, float
 	const SkinInstance& in = sk.inst[instance];
 	if (cap_bones < in.n_bones) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bones", in.n_bones);
 	if (sk.pose_is_absolute || !sk.poses_uploaded || sk.borrowed_pos) return fail(ctx, LMX_ERR_NOT_BUILT, "the pose buffers do not hold a relative pose (call after lmx_anim_update, before lmx_skin_run)");
-	if (out_pos) LMX_HIP(ctx, hipMemcpyAsync(out_pos, sk.d_pose_pos.p + (size_t)in.bone_offset * 3, (size_t)in.n_bones * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-	if (out_rot) LMX_HIP(ctx, hipMemcpyAsync(out_rot, sk.d_pose_rot.p + in.bone_offset, (size_t)in.n_bones * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out_pos, sk.d_pose_pos.p + (size_t)in.bone_offset * 3, (size_t)in.n_bones * 3, ctx->stream));
+	LMX_HIP(ctx, read_back((float4*)out_rot, sk.d_pose_rot.p + in.bone_offset, in.n_bones, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }

@@ -317,11 +317,9 @@ int recompute_out_layout(LmxContext* ctx) {
 	LMX_HIP(ctx, cs.d_win_base.reserve(std::max<size_t>(cs.n_shards, 1)));
 	LMX_HIP(ctx, cs.d_shard_type.reserve(std::max<size_t>(cs.n_shards, 1)));
 	LMX_HIP(ctx, cs.d_type_start.reserve(MAX_TYPES));
-	if (cs.n_shards) {
-		LMX_HIP(ctx, hipMemcpy(cs.d_win_base.p, cs.win_base.data(), cs.n_shards * sizeof(uint32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(cs.d_shard_type.p, cs.shard_type.data(), cs.n_shards, hipMemcpyHostToDevice));
-	}
-	LMX_HIP(ctx, hipMemcpy(cs.d_type_start.p, cs.type_start, sizeof(cs.type_start), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(cs.d_win_base.p, cs.win_base));
+	LMX_HIP(ctx, upload_blocking(cs.d_shard_type.p, cs.shard_type));
+	LMX_HIP(ctx, upload_blocking(cs.d_type_start.p, cs.type_start, MAX_TYPES));
 	for (int k = 0; k < 3; ++k) { // every tile's shard and window start, per tile size (k_cull_tile reads one 8-byte entry instead of deriving them)
 		const uint32_t tile = TILE_ALIGN >> k;
 		std::vector<uint2> tab(cs.n_padded / tile);
@@ -331,8 +329,7 @@ int recompute_out_layout(LmxContext* ctx) {
 				tab[e / tile] = make_uint2(shard, cs.win_base[shard]);
 			}
 		}
-		LMX_HIP(ctx, cs.d_tile_out[k].reserve(std::max<size_t>(tab.size(), 1)));
-		if (!tab.empty()) LMX_HIP(ctx, hipMemcpy(cs.d_tile_out[k].p, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(cs.d_tile_out[k], tab));
 	}
 	for (CullView& v : cs.views) {
 		v.valid = v.finalized = v.consolidated = false;

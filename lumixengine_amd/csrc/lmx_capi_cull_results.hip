@@ -48,7 +48,7 @@ int lmx_cull_counts(LmxContext* ctx, uint32_t view, uint32_t* counts) {
 	if (!v.valid) return fail(ctx, LMX_ERR_NOT_BUILT, "view %u holds no cull result", view);
 	if (int rc = cull_view_finalize(ctx, v)) return rc;
 	uint32_t all[MAX_FRUSTA * MAX_TYPES];
-	LMX_HIP(ctx, hipMemcpyAsync(all, v.totals_ptr(), sizeof(uint32_t) * v.n_frusta * MAX_TYPES, hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(all, v.totals_ptr(), (size_t)v.n_frusta * MAX_TYPES, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	memcpy(counts, all, sizeof(uint32_t) * v.n_frusta * MAX_TYPES);
 	return LMX_OK;
@@ -62,14 +62,13 @@ int lmx_cull_read(LmxContext* ctx, uint32_t view, uint32_t frustum, uint8_t type
 	if (frustum >= v.n_frusta || type >= MAX_TYPES) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "frustum %u / type %u out of range", frustum, type);
 	if (int rc = cull_view_consolidate(ctx, v)) return rc;
 	uint32_t c = 0;
-	LMX_HIP(ctx, hipMemcpyAsync(&c, v.totals_ptr() + frustum * MAX_TYPES + type, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(&c, v.totals_ptr() + frustum * MAX_TYPES + type, 1, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	if (out_count) *out_count = c;
 	if (c > v.out_cap[type]) return fail(ctx, LMX_ERR_HIP, "corrupt count %u > %u", c, v.out_cap[type]);
 	if (!out_ids || c == 0) return LMX_OK;
 	if (c > cap) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u ids, got %u", c, cap);
-	LMX_HIP(ctx, hipMemcpyAsync(out_ids, v.cons_ptr() + (size_t)frustum * v.out_stride + v.out_start[type], (size_t)c * sizeof(int32_t),
-		hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out_ids, v.cons_ptr() + (size_t)frustum * v.out_stride + v.out_start[type], c, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -82,7 +81,7 @@ int lmx_cull_read_all(LmxContext* ctx, uint32_t view, uint32_t frustum, int32_t*
 	if (!v.valid) return fail(ctx, LMX_ERR_NOT_BUILT, "view %u holds no cull result", view);
 	if (frustum >= v.n_frusta) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "frustum %u out of range", frustum);
 	if (int rc = cull_view_consolidate(ctx, v)) return rc;
-	LMX_HIP(ctx, hipMemcpyAsync(out_counts, v.totals_ptr() + frustum * MAX_TYPES, sizeof(uint32_t) * MAX_TYPES, hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out_counts, v.totals_ptr() + frustum * MAX_TYPES, MAX_TYPES, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	size_t total = 0;
 	for (int t = 0; t < MAX_TYPES; ++t) {
@@ -94,8 +93,7 @@ int lmx_cull_read_all(LmxContext* ctx, uint32_t view, uint32_t frustum, int32_t*
 	size_t at = 0;
 	for (int t = 0; t < MAX_TYPES; ++t) {
 		if (!out_counts[t]) continue;
-		LMX_HIP(ctx, hipMemcpyAsync(out_ids + at, v.cons_ptr() + (size_t)frustum * v.out_stride + v.out_start[t], (size_t)out_counts[t] * sizeof(int32_t),
-			hipMemcpyDeviceToHost, ctx->stream));
+		LMX_HIP(ctx, read_back(out_ids + at, v.cons_ptr() + (size_t)frustum * v.out_stride + v.out_start[t], out_counts[t], ctx->stream));
 		at += out_counts[t];
 	}
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -12,14 +12,6 @@ using namespace lmx;
 
 namespace {
 
-template <typename T> int upload(LmxContext* ctx, DevBuf<T>& buf, const T* src, size_t n) {
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, buf.reserve(std::max<size_t>(n, 1)));
-	if (n) LMX_HIP(ctx, hipMemcpyAsync(buf.p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
-}
-
 // The temporary storage of the three sums (all over `n` words) is sized once, in front of the launch sequence.
 int scan_reserve(LmxContext* ctx, size_t n, size_t* temp) {
 	*temp = 0;
@@ -114,7 +106,7 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 		LMX_HIP(ctx, launch_draw_encode(ctx->stream, d, v));
 	} else {
 		const uint32_t zero[4] = {0, 0, 0, n_group_values};
-		LMX_HIP(ctx, hipMemcpyAsync(ds.d_counts.p, zero, sizeof(zero), hipMemcpyHostToDevice, ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ds.d_counts.p, zero, 4, ctx->stream));
 		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	}
 	LMX_HIP(ctx, launch_draw_groups(ctx->stream, d, v));
@@ -125,7 +117,7 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 int host_counts(LmxContext* ctx, uint32_t c[4]) {
 	DrawState& ds = ctx->draw;
 	if (!ds.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_run has not run");
-	LMX_HIP(ctx, hipMemcpyAsync(c, ds.d_counts.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(c, ds.d_counts.p, 4, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -137,7 +129,9 @@ extern "C" {
 int lmx_draw_set_meshes(LmxContext* ctx, const float* mesh_lod, uint32_t n_meshes) {
 	LMX_CHECK_CTX(ctx);
 	if (n_meshes && !mesh_lod) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null mesh table");
-	if (int rc = upload(ctx, ctx->draw.d_mesh_lod, mesh_lod, n_meshes)) return rc;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_mesh_lod, mesh_lod, n_meshes, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->draw.n_meshes = n_meshes;
 	return LMX_OK;
 }
@@ -145,7 +139,9 @@ int lmx_draw_set_meshes(LmxContext* ctx, const float* mesh_lod, uint32_t n_meshe
 int lmx_draw_set_material_indices(LmxContext* ctx, const uint32_t* material_index, uint32_t n_mesh_materials) {
 	LMX_CHECK_CTX(ctx);
 	if (n_mesh_materials && !material_index) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null material-index table");
-	if (int rc = upload(ctx, ctx->draw.d_material_index, material_index, n_mesh_materials)) return rc;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_material_index, material_index, n_mesh_materials, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->draw.n_material_index = n_mesh_materials;
 	return LMX_OK;
 }
@@ -153,7 +149,9 @@ int lmx_draw_set_material_indices(LmxContext* ctx, const uint32_t* material_inde
 int lmx_draw_set_transforms(LmxContext* ctx, const LmxTransform* transforms, uint32_t n_entities) {
 	LMX_CHECK_CTX(ctx);
 	if (n_entities && !transforms) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null transforms");
-	if (int rc = upload(ctx, ctx->draw.d_tr, transforms, n_entities)) return rc;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_tr, transforms, n_entities, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->draw.n_tr = n_entities;
 	return LMX_OK;
 }
@@ -167,7 +165,9 @@ int lmx_draw_bind_world(LmxContext* ctx, int enable) {
 int lmx_draw_set_prev_transforms(LmxContext* ctx, const LmxTransform* transforms, uint32_t n_entities) {
 	LMX_CHECK_CTX(ctx);
 	if (n_entities && !transforms) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null transforms");
-	if (int rc = upload(ctx, ctx->draw.d_prev, transforms, n_entities)) return rc;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_prev, transforms, n_entities, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->draw.n_prev = n_entities;
 	return LMX_OK;
 }
@@ -175,8 +175,12 @@ int lmx_draw_set_prev_transforms(LmxContext* ctx, const LmxTransform* transforms
 int lmx_draw_set_bones(LmxContext* ctx, const uint32_t* handle, const uint32_t* offset, uint32_t n_entities) {
 	LMX_CHECK_CTX(ctx);
 	if (n_entities && (!handle || !offset)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null bones table");
-	if (int rc = upload(ctx, ctx->draw.d_bones_handle, handle, n_entities)) return rc;
-	if (int rc = upload(ctx, ctx->draw.d_bones_offset, offset, n_entities)) return rc;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_bones_handle, handle, n_entities, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_bones_offset, offset, n_entities, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->draw.n_bones = n_entities;
 	return LMX_OK;
 }
@@ -197,7 +201,9 @@ int lmx_draw_set_decals(LmxContext* ctx, uint32_t n_entities, const float* half_
 			memcpy(r[e].uv_scale, uv_scale + 2 * (size_t)e, 8);
 			r[e].material_index = material_index[e];
 		}
-		if (int rc = upload(ctx, ds.d_decals, r.data(), n_entities)) return rc;
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ds.d_decals, r.data(), n_entities, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		ds.n_decals = n_entities;
 		ds.have_decals = true;
 	}
@@ -210,7 +216,9 @@ int lmx_draw_set_decals(LmxContext* ctx, uint32_t n_entities, const float* half_
 			memcpy(r[e].bezier, curve_bezier + 4 * (size_t)e, 16);
 			r[e].material_index = curve_material_index[e];
 		}
-		if (int rc = upload(ctx, ds.d_curves, r.data(), n_entities)) return rc;
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ds.d_curves, r.data(), n_entities, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		ds.n_curves = n_entities;
 		ds.have_curves = true;
 	}
@@ -241,11 +249,19 @@ int lmx_draw_run_pairs(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batc
 		if (n_group_values && !group_values) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null group values");
 	}
 	DrawState& ds = ctx->draw;
-	if (int rc = upload(ctx, ds.d_keys, keys, n)) return rc;
-	if (int rc = upload(ctx, ds.d_values, values, n)) return rc;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ds.d_keys, keys, n, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ds.d_values, values, n, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	if (n_groups) {
-		if (int rc = upload(ctx, ds.d_group_offset, group_offsets, (size_t)n_groups + 1)) return rc;
-		if (int rc = upload(ctx, ds.d_group_values, group_values, n_group_values)) return rc;
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ds.d_group_offset, group_offsets, (size_t)n_groups + 1, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ds.d_group_values, group_values, n_group_values, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	}
 	return draw_pass(ctx, view, n_batches, ds.d_keys.p, ds.d_values.p, n, ds.d_group_offset.p, ds.d_group_values.p, n_groups, n_group_values);
 }
@@ -264,7 +280,7 @@ int lmx_draw_read_runs(LmxContext* ctx, LmxDrawRun* runs, uint32_t cap) {
 	uint32_t c[4];
 	if (int rc = host_counts(ctx, c)) return rc;
 	if (cap < c[0]) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u runs", c[0]);
-	if (c[0] && runs) LMX_HIP(ctx, hipMemcpyAsync(runs, ctx->draw.d_runs.p, (size_t)c[0] * sizeof(LmxDrawRun), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(runs, ctx->draw.d_runs.p, c[0], ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -274,7 +290,7 @@ int lmx_draw_read_instance_data(LmxContext* ctx, void* out, size_t cap_bytes) {
 	uint32_t c[4];
 	if (int rc = host_counts(ctx, c)) return rc;
 	if (cap_bytes < c[1]) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bytes", c[1]);
-	if (c[1] && out) LMX_HIP(ctx, hipMemcpyAsync(out, ctx->draw.d_instance_data.p, c[1], hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back((uint8_t*)out, ctx->draw.d_instance_data.p, c[1], ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -285,7 +301,7 @@ int lmx_draw_read_group_data(LmxContext* ctx, void* out, size_t cap_bytes) {
 	if (int rc = host_counts(ctx, c)) return rc;
 	const size_t bytes = (size_t)c[3] * 48;
 	if (cap_bytes < bytes) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu bytes", bytes);
-	if (bytes && out) LMX_HIP(ctx, hipMemcpyAsync(out, ctx->draw.d_group_data.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back((uint8_t*)out, ctx->draw.d_group_data.p, bytes, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }

@@ -89,9 +89,9 @@ int im_upload_tables(LmxInstancedModels* im) {
 		LMX_HIP(ctx, im->d_model_tot.reserve(8 * (size_t)std::max<uint32_t>(nm, 1)));
 		LMX_HIP(ctx, hipMemset(im->d_model_tot.p, 0, im->d_model_tot.cap * sizeof(uint32_t)));
 	}
-	if (nm) LMX_HIP(ctx, hipMemcpy(im->d_models.p, im->table.data(), nm * sizeof(ImModelDev), hipMemcpyHostToDevice));
-	if (im->n_tiles) LMX_HIP(ctx, hipMemcpy(im->d_tile_model.p, im->tile_model.data(), im->n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
-	if (im->n_indirect) LMX_HIP(ctx, hipMemcpy(im->d_indices.p, im->indices.data(), im->n_indirect * sizeof(uint32_t), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(im->d_models.p, im->table));
+	LMX_HIP(ctx, upload_blocking(im->d_tile_model.p, im->tile_model));
+	LMX_HIP(ctx, upload_blocking(im->d_indices.p, im->indices));
 	im->dirty = false;
 	return LMX_OK;
 }
@@ -121,9 +121,9 @@ int im_relayout(LmxInstancedModels* im, uint32_t model, uint32_t new_n) {
 	for (uint32_t m = 0; m < nm; ++m) {
 		const uint32_t n = im->models[m].n;
 		if (m == model || !n) continue;
-		LMX_HIP(ctx, hipMemcpy(ps.p + new_first[m], im->d_pos_scale.p + old_first[m], n * sizeof(float4), hipMemcpyDeviceToDevice));
-		LMX_HIP(ctx, hipMemcpy(rot.p + new_first[m], im->d_rot.p + old_first[m], n * sizeof(float4), hipMemcpyDeviceToDevice));
-		LMX_HIP(ctx, hipMemcpy(lod.p + new_first[m], im->d_lod.p + old_first[m], n * sizeof(float), hipMemcpyDeviceToDevice));
+		LMX_HIP(ctx, device_copy_blocking(ps.p + new_first[m], im->d_pos_scale.p + old_first[m], n));
+		LMX_HIP(ctx, device_copy_blocking(rot.p + new_first[m], im->d_rot.p + old_first[m], n));
+		LMX_HIP(ctx, device_copy_blocking(lod.p + new_first[m], im->d_lod.p + old_first[m], n));
 	}
 	im->d_pos_scale.swap(ps);
 	im->d_rot.swap(rot);
@@ -177,7 +177,7 @@ int lmx_im_set_model(LmxInstancedModels* im, uint32_t model, const float lod_dis
 		if (im->d_grids.cap < model + 1) {
 			DevBuf<ImGridDev> grids;
 			LMX_HIP(ctx, grids.reserve(model + 1));
-			if (model) LMX_HIP(ctx, hipMemcpy(grids.p, im->d_grids.p, model * sizeof(ImGridDev), hipMemcpyDeviceToDevice));
+			LMX_HIP(ctx, device_copy_blocking(grids.p, im->d_grids.p, model));
 			im->d_grids.swap(grids);
 		}
 		LMX_HIP(ctx, launch_im_grid_build(ctx->stream, nullptr, 0, im->arrays(), 0, im->d_grids.p + model));
@@ -208,8 +208,7 @@ int lmx_im_set_instances(LmxInstancedModels* im, uint32_t model, uint32_t n, con
 	im->dirty = true;
 	invalidate_slots(im);
 	if (int rc = im_upload_tables(im)) return rc;
-	LMX_HIP(ctx, im->d_stage.reserve(std::max<uint32_t>(n, 1)));
-	if (n) LMX_HIP(ctx, hipMemcpy(im->d_stage.p, instances, (size_t)n * sizeof(LmxImInstance), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(im->d_stage, instances, n));
 	LMX_HIP(ctx, launch_im_grid_build(ctx->stream, im->d_stage.p, n, im->arrays(), im->table[model].first, im->d_grids.p + model));
 	return LMX_OK;
 }

@@ -8,16 +8,6 @@
 
 using namespace lmx;
 
-namespace {
-
-template <typename T> int upload(LmxContext* ctx, DevBuf<T>& buf, const T* src, size_t n) {
-	LMX_HIP(ctx, buf.reserve(std::max<size_t>(n, 1)));
-	if (n) LMX_HIP(ctx, hipMemcpyAsync(buf.p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-	return LMX_OK;
-}
-
-} // namespace
-
 namespace lmx {
 
 // (Re)build the slot-ordered mirror for the culling system's current static layout, if it is not current already.
@@ -73,7 +63,7 @@ int keys_upload_instances(LmxContext* ctx) {
 	KeysState& ks = ctx->keys;
 	if (!ks.inst_dirty) return LMX_OK;
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (int rc = upload(ctx, ks.d_inst, ks.inst.data(), ks.inst.size())) return rc;
+	LMX_HIP(ctx, upload_on_stream(ks.d_inst, ks.inst, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ks.inst_dirty = false;
 	ks.inst_uploaded = ks.inst.size();
@@ -112,8 +102,8 @@ int lmx_keys_set_models(LmxContext* ctx, const LmxKeysModel* models, uint32_t n_
 	// Checked BEFORE anything is uploaded or assigned: a refused table leaves the previous one in place.
 	if (max_span > 511) return fail(ctx, LMX_ERR_CAPACITY, "a LOD range of %u meshes exceeds the 511 the key kernel's packed scan holds", max_span);
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (int rc = upload(ctx, ks.d_models, models, n_models)) return rc;
-	if (int rc = upload(ctx, ks.d_mesh_types, mesh_types, n_meshes)) return rc;
+	LMX_HIP(ctx, upload_on_stream(ks.d_models, models, n_models, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ks.d_mesh_types, mesh_types, n_meshes, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ks.mirror_valid = false; // (mesh counts may have changed; set_instances follows)
 	ks.models.assign(models, models + n_models);
@@ -149,7 +139,7 @@ int lmx_keys_set_instances(LmxContext* ctx, uint32_t n_entities, const int32_t* 
 		for (uint32_t k = 0; k < m.mesh_count; ++k) dev_mm[material_offset[e] + k]._pad[0] = ks.mesh_types[m.first_mesh + k];
 	}
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (int rc = upload(ctx, ks.d_mesh_materials, dev_mm.data(), n_mesh_materials)) return rc;
+	LMX_HIP(ctx, upload_on_stream(ks.d_mesh_materials, dev_mm, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	// one 64-byte record per entity (positions of an earlier lmx_keys_set_positions are kept)
 	ks.inst.resize(n_entities);
@@ -181,12 +171,12 @@ int lmx_keys_set_decals(LmxContext* ctx, uint32_t n_entities, const uint32_t* de
 	ks.have_decals = decal_sort_key != nullptr;
 	ks.have_curves = curve_sort_key != nullptr;
 	if (ks.have_decals) {
-		if (int rc = upload(ctx, ks.d_decal_key, decal_sort_key, n_entities)) return rc;
-		if (int rc = upload(ctx, ks.d_decal_layer, decal_layer, n_entities)) return rc;
+		LMX_HIP(ctx, upload_on_stream(ks.d_decal_key, decal_sort_key, n_entities, ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ks.d_decal_layer, decal_layer, n_entities, ctx->stream));
 	}
 	if (ks.have_curves) {
-		if (int rc = upload(ctx, ks.d_curve_key, curve_sort_key, n_entities)) return rc;
-		if (int rc = upload(ctx, ks.d_curve_layer, curve_layer, n_entities)) return rc;
+		LMX_HIP(ctx, upload_on_stream(ks.d_curve_key, curve_sort_key, n_entities, ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ks.d_curve_layer, curve_layer, n_entities, ctx->stream));
 	}
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	if (!ks.have_instances) ks.n_entities = n_entities;
@@ -455,7 +445,7 @@ int lmx_keys_run(LmxContext* ctx, uint32_t view, uint32_t frustum, const LmxKeys
 static int keys_host_counters(LmxContext* ctx, uint32_t* c) {
 	KeysState& ks = ctx->keys;
 	if (!ks.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_keys_run has not run");
-	LMX_HIP(ctx, hipMemcpyAsync(c, ks.d_groups.p + ks.counters_at, KEYS_COUNTERS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(c, ks.d_groups.p + ks.counters_at, KEYS_COUNTERS, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -485,8 +475,8 @@ int lmx_keys_sort(LmxContext* ctx) {
 		LMX_HIP(ctx, ks.d_sort_temp.reserve(temp));
 		ProfScope ps(ctx, LMX_K_SORT_KEYS);
 		LMX_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ks.d_sort_temp.p, temp, ks.d_keys.p, ks.d_keys_alt.p, ks.d_values.p, ks.d_values_alt.p, (int)n, 0, 64, ctx->stream));
-		LMX_HIP(ctx, hipMemcpyAsync(ks.d_keys.p, ks.d_keys_alt.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-		LMX_HIP(ctx, hipMemcpyAsync(ks.d_values.p, ks.d_values_alt.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+		LMX_HIP(ctx, device_copy_on_stream(ks.d_keys.p, ks.d_keys_alt.p, n, ctx->stream));
+		LMX_HIP(ctx, device_copy_on_stream(ks.d_values.p, ks.d_values_alt.p, n, ctx->stream));
 	}
 	ks.sorted = true;
 	ks.n_sorted = n;
@@ -502,8 +492,8 @@ int lmx_keys_read_pairs(LmxContext* ctx, uint64_t* keys, uint64_t* values, uint3
 	if (c[KEYS_OVERFLOW]) return fail(ctx, LMX_ERR_CAPACITY, "sort-key output overflowed (code %u)", c[KEYS_OVERFLOW]);
 	const uint32_t n = c[KEYS_N_PAIRS];
 	if (cap < n) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u pairs", n);
-	if (n && keys) LMX_HIP(ctx, hipMemcpyAsync(keys, ks.d_keys.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-	if (n && values) LMX_HIP(ctx, hipMemcpyAsync(values, ks.d_values.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(keys, ks.d_keys.p, n, ctx->stream));
+	LMX_HIP(ctx, read_back(values, ks.d_values.p, n, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -516,8 +506,8 @@ int lmx_keys_read_instancer(LmxContext* ctx, uint32_t* offsets, uint64_t* values
 	if (c[KEYS_OVERFLOW]) return fail(ctx, LMX_ERR_CAPACITY, "sort-key output overflowed (code %u)", c[KEYS_OVERFLOW]);
 	const uint32_t n = c[KEYS_N_RECS];
 	if (values && cap_values < n) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u instanced renderables", n);
-	if (offsets) LMX_HIP(ctx, hipMemcpyAsync(offsets, ks.d_groups.p + ks.offsets_at, (size_t)(ks.max_sort_key + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-	if (values && n) LMX_HIP(ctx, hipMemcpyAsync(values, ks.d_group_values.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(offsets, ks.d_groups.p + ks.offsets_at, (size_t)ks.max_sort_key + 2, ctx->stream));
+	LMX_HIP(ctx, read_back(values, ks.d_group_values.p, n, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -528,7 +518,7 @@ static int keys_read_list(LmxContext* ctx, int which, const int32_t* src, int32_
 	if (c[KEYS_OVERFLOW]) return fail(ctx, LMX_ERR_CAPACITY, "sort-key output overflowed (code %u)", c[KEYS_OVERFLOW]);
 	const uint32_t n = c[which];
 	if (cap < n) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u entities", n);
-	if (n && entities) LMX_HIP(ctx, hipMemcpyAsync(entities, src, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(entities, src, n, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }

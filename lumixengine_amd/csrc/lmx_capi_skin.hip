@@ -121,24 +121,24 @@ static int skin_upload_static(LmxContext* ctx) {
 		LMX_HIP(ctx, sk.d_inv_pos.reserve(nb * 3));
 		LMX_HIP(ctx, sk.d_inv_rot.reserve(nb));
 		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, hipMemcpy(sk.d_parents.p, sk.parents.data(), nb * sizeof(int16_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(sk.d_inv_pos.p, sk.inv_pos.data(), nb * 3 * sizeof(float), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(sk.d_inv_rot.p, sk.inv_rot.data(), nb * sizeof(float4), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(sk.d_parents.p, sk.parents));
+		LMX_HIP(ctx, upload_blocking(sk.d_inv_pos.p, sk.inv_pos));
+		LMX_HIP(ctx, upload_blocking(sk.d_inv_rot.p, sk.inv_rot));
 		// (+ 256: k_pose_palette's lanes read a model's item list 64 words at a time, up to one bone count past its end - never used, never out of the buffer)
 		LMX_HIP(ctx, sk.d_level_items.reserve(sk.level_items.size() + 256));
 		LMX_HIP(ctx, sk.d_level_off.reserve(std::max<size_t>(sk.level_off.size(), 1)));
-		if (!sk.level_items.empty()) LMX_HIP(ctx, hipMemcpy(sk.d_level_items.p, sk.level_items.data(), sk.level_items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(sk.d_level_off.p, sk.level_off.data(), sk.level_off.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(sk.d_level_items.p, sk.level_items));
+		LMX_HIP(ctx, upload_blocking(sk.d_level_off.p, sk.level_off));
 		sk.models_dirty = false;
 	}
 	if (sk.meshes_dirty) {
 		LMX_HIP(ctx, sk.d_mesh.reserve(std::max<size_t>(sk.mesh.size(), 1)));
 		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, hipMemcpy(sk.d_mesh.p, sk.mesh.data(), sk.mesh.size() * sizeof(float4), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(sk.d_mesh.p, sk.mesh));
 		LMX_HIP(ctx, sk.d_mesh_local.reserve(std::max<size_t>(sk.mesh_local.size(), 1)));
 		LMX_HIP(ctx, sk.d_tile_bones.reserve(std::max<size_t>(sk.tile_bones.size(), 1)));
-		LMX_HIP(ctx, hipMemcpy(sk.d_mesh_local.p, sk.mesh_local.data(), sk.mesh_local.size() * sizeof(float4), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(sk.d_tile_bones.p, sk.tile_bones.data(), sk.tile_bones.size(), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(sk.d_mesh_local.p, sk.mesh_local));
+		LMX_HIP(ctx, upload_blocking(sk.d_tile_bones.p, sk.tile_bones));
 		sk.meshes_dirty = false;
 	}
 	return LMX_OK;
@@ -247,13 +247,12 @@ int lmx_skin_set_instances(LmxContext* ctx, uint32_t n, const uint32_t* model, c
 	LMX_HIP(ctx, sk.d_palette.reserve(std::max<size_t>(bones * 3, 1)));
 	LMX_HIP(ctx, sk.d_out.reserve(std::max<size_t>(verts * 3, 1)));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (n) LMX_HIP(ctx, hipMemcpy(sk.d_inst.p, sk.inst.data(), (size_t)n * sizeof(SkinInstance), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(sk.d_inst.p, sk.inst));
 	LMX_HIP(ctx, sk.d_chunks.reserve(std::max<size_t>(sk.chunks.size(), 1)));
 	LMX_HIP(ctx, sk.d_solo.reserve(std::max<size_t>(sk.solo.size(), 1)));
-	if (!sk.chunks.empty()) LMX_HIP(ctx, hipMemcpy(sk.d_chunks.p, sk.chunks.data(), sk.chunks.size() * sizeof(SkinChunk), hipMemcpyHostToDevice));
-	if (!sk.solo.empty()) LMX_HIP(ctx, hipMemcpy(sk.d_solo.p, sk.solo.data(), sk.solo.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	LMX_HIP(ctx, sk.d_groups.reserve(std::max<size_t>(sk.groups.size(), 1)));
-	if (n) LMX_HIP(ctx, hipMemcpy(sk.d_groups.p, sk.groups.data(), sk.groups.size() * sizeof(PoseGroup), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(sk.d_chunks.p, sk.chunks));
+	LMX_HIP(ctx, upload_blocking(sk.d_solo.p, sk.solo));
+	LMX_HIP(ctx, upload_blocking(sk.d_groups, sk.groups));
 	return LMX_OK;
 }
 
@@ -264,8 +263,8 @@ int lmx_skin_upload_poses(LmxContext* ctx, const float* positions, const float* 
 	if (!n_bones_total) return LMX_OK;
 	if (!positions || !rotations) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null input array");
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, hipMemcpy(sk.d_pose_pos.p, positions, n_bones_total * 3 * sizeof(float), hipMemcpyHostToDevice));
-	LMX_HIP(ctx, hipMemcpy(sk.d_pose_rot.p, rotations, n_bones_total * sizeof(float4), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(sk.d_pose_pos.p, positions, n_bones_total * 3));
+	LMX_HIP(ctx, upload_blocking(sk.d_pose_rot.p, (const float4*)rotations, n_bones_total));
 	sk.poses_uploaded = true;
 	sk.pose_is_absolute = false;
 	return LMX_OK;
@@ -277,8 +276,8 @@ int lmx_skin_upload_poses_device(LmxContext* ctx, const void* d_positions, const
 	if (n_bones_total != sk.bones_total) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "expected %zu bones over all instances, got %zu", sk.bones_total, n_bones_total);
 	if (!n_bones_total) return LMX_OK;
 	if (!d_positions || !d_rotations) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null device pointer");
-	LMX_HIP(ctx, hipMemcpyAsync(sk.d_pose_pos.p, d_positions, n_bones_total * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-	LMX_HIP(ctx, hipMemcpyAsync(sk.d_pose_rot.p, d_rotations, n_bones_total * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+	LMX_HIP(ctx, device_copy_on_stream(sk.d_pose_pos.p, (const float*)d_positions, n_bones_total * 3, ctx->stream));
+	LMX_HIP(ctx, device_copy_on_stream(sk.d_pose_rot.p, (const float4*)d_rotations, n_bones_total, ctx->stream));
 	sk.poses_uploaded = true;
 	sk.pose_is_absolute = false;
 	return LMX_OK;
@@ -313,8 +312,8 @@ int lmx_skin_blend_poses(LmxContext* ctx, const float* positions, const float* r
 	if (!(weight == weight)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "weight is NaN");
 	LMX_HIP(ctx, sk.d_blend_pos.reserve(n_bones_total * 3));
 	LMX_HIP(ctx, sk.d_blend_rot.reserve(n_bones_total));
-	LMX_HIP(ctx, hipMemcpyAsync(sk.d_blend_pos.p, positions, n_bones_total * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-	LMX_HIP(ctx, hipMemcpyAsync(sk.d_blend_rot.p, rotations, n_bones_total * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(sk.d_blend_pos.p, positions, n_bones_total * 3, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(sk.d_blend_rot.p, (const float4*)rotations, n_bones_total, ctx->stream));
 	const int rc = skin_blend(ctx, sk.d_blend_pos.p, sk.d_blend_rot.p, n_bones_total, weight);
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the caller's arrays may be pageable: do not return before they are read
 	return rc;
@@ -372,7 +371,7 @@ static int skin_build_multi_chunks(LmxContext* ctx) {
 	}
 	LMX_HIP(ctx, sk.d_multi_chunks.reserve(std::max<size_t>(sk.multi_chunks.size(), 1)));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a launch of the previous frame may still read the old list)
-	if (!sk.multi_chunks.empty()) LMX_HIP(ctx, hipMemcpy(sk.d_multi_chunks.p, sk.multi_chunks.data(), sk.multi_chunks.size() * sizeof(SkinMultiChunk), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(sk.d_multi_chunks.p, sk.multi_chunks));
 	sk.multi_built = sk.multi;
 	return LMX_OK;
 }
@@ -422,7 +421,7 @@ int lmx_skin_read_vertices(LmxContext* ctx, uint32_t instance, float* out_xyz, u
 	if (instance >= sk.inst.size() || !out_xyz) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "bad instance/out");
 	const SkinInstance& in = sk.inst[instance];
 	if (cap_verts < in.n_verts) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u vertices", in.n_verts);
-	LMX_HIP(ctx, hipMemcpyAsync(out_xyz, sk.d_out.p + (size_t)in.out_offset * 3, (size_t)in.n_verts * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out_xyz, sk.d_out.p + (size_t)in.out_offset * 3, (size_t)in.n_verts * 3, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -436,7 +435,7 @@ int lmx_skin_read_vertices_range(LmxContext* ctx, uint32_t first_instance, uint3
 	const SkinInstance& b = sk.inst[first_instance + n_instances - 1];
 	const size_t n = (size_t)b.out_offset + b.n_verts - a.out_offset; // outputs are laid out in instance order
 	if (cap_verts < n) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu vertices", n);
-	LMX_HIP(ctx, hipMemcpyAsync(out_xyz, sk.d_out.p + (size_t)a.out_offset * 3, n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out_xyz, sk.d_out.p + (size_t)a.out_offset * 3, n * 3, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -460,7 +459,7 @@ int lmx_skin_read_palette(LmxContext* ctx, uint32_t instance, LmxMatrix* out, ui
 	// the palette is kept as the 3 rows evaluateSkin reads (48 B per bone); the constant 4th row is re-attached here
 	LMX_HIP(ctx, sk.d_palette_expanded.reserve(in.n_bones * 4));
 	LMX_HIP(ctx, launch_palette_expand(ctx->stream, sk.d_palette.p + (size_t)in.bone_offset * 3, in.n_bones, sk.d_palette_expanded.p));
-	LMX_HIP(ctx, hipMemcpyAsync(out, sk.d_palette_expanded.p, (size_t)in.n_bones * sizeof(LmxMatrix), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out, (const LmxMatrix*)sk.d_palette_expanded.p, in.n_bones, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -484,7 +483,7 @@ int lmx_skin_read_dual_quats(LmxContext* ctx, uint32_t instance, float* out, uin
 	if (!(sk.want_dual_quats || sk.mode == LMX_SKIN_DQS) || !sk.d_dual_quats.p) return fail(ctx, LMX_ERR_NOT_BUILT, "dual-quaternion palette not enabled before lmx_skin_run");
 	const SkinInstance& in = sk.inst[instance];
 	if (cap_bones < in.n_bones) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bones", in.n_bones);
-	LMX_HIP(ctx, hipMemcpyAsync(out, sk.d_dual_quats.p + (size_t)in.bone_offset * 2, (size_t)in.n_bones * 8 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back((float4*)out, sk.d_dual_quats.p + (size_t)in.bone_offset * 2, (size_t)in.n_bones * 2, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -496,8 +495,8 @@ int lmx_skin_read_pose(LmxContext* ctx, uint32_t instance, float* out_pos, float
 	const SkinInstance& in = sk.inst[instance];
 	if (cap_bones < in.n_bones) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bones", in.n_bones);
 	if (!sk.pose_is_absolute) return fail(ctx, LMX_ERR_NOT_BUILT, "no absolute pose: lmx_skin_run has not run, or pose write-back is disabled");
-	if (out_pos) LMX_HIP(ctx, hipMemcpyAsync(out_pos, sk.d_pose_pos.p + (size_t)in.bone_offset * 3, (size_t)in.n_bones * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-	if (out_rot) LMX_HIP(ctx, hipMemcpyAsync(out_rot, sk.d_pose_rot.p + in.bone_offset, (size_t)in.n_bones * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out_pos, sk.d_pose_pos.p + (size_t)in.bone_offset * 3, (size_t)in.n_bones * 3, ctx->stream));
+	LMX_HIP(ctx, read_back((float4*)out_rot, sk.d_pose_rot.p + in.bone_offset, in.n_bones, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }

@@ -5,10 +5,6 @@
 
 using namespace lmx;
 
-extern "C" {
-
-} // extern "C"
-
 namespace {
 
 // (Re)build the slot order for `parent` and upload: transforms[e] = world transform for roots, Hierarchy::local_transform for
@@ -75,9 +71,9 @@ int world_rebuild(LmxContext* ctx, uint32_t n, const int32_t* parent, const LmxT
 	// transforms; with world values (re-parenting, lmx_world_build_with_world) nothing is recomputed until something is written
 	LMX_HIP(ctx, hipMemset(w.d_dirty.p, world_all ? 0 : XF_MOVED, cap));
 	if (n) {
-		LMX_HIP(ctx, hipMemcpy(w.d_parent_slot.p, w.parent_slot.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(w.d_slot_of_entity.p, w.slot_of_entity.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(w.d_entity_of_slot.p, w.entity_of_slot.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(w.d_parent_slot.p, w.parent_slot));
+		LMX_HIP(ctx, upload_blocking(w.d_slot_of_entity.p, w.slot_of_entity));
+		LMX_HIP(ctx, upload_blocking(w.d_entity_of_slot.p, w.entity_of_slot));
 		// k_xform_subtree's table: the roots cut into runs of ~XF_SUBTREE_NODES nodes (subtrees included); per run and level the first slot.
 		// The subtrees of consecutive roots are contiguous in every level because a level is ordered by parent slot.
 		{
@@ -99,7 +95,6 @@ int world_rebuild(LmxContext* ctx, uint32_t n, const int32_t* parent, const LmxT
 				std::vector<uint32_t> table;
 				auto row = [&](uint32_t r) { for (size_t l = 0; l < n_levels; ++l) table.push_back(bound[l][r]); };
 				uint64_t heaviest = 0;
-				uint32_t run_first = 0;
 				uint64_t in_run = 0;
 				row(0);
 				for (uint32_t r = 0; r < n_roots; ++r) {
@@ -108,18 +103,15 @@ int world_rebuild(LmxContext* ctx, uint32_t n, const int32_t* parent, const LmxT
 					if (in_run && in_run + size > XF_SUBTREE_NODES) { // close the run before this root
 						row(r);
 						heaviest = std::max(heaviest, in_run);
-						run_first = r;
 						in_run = 0;
 					}
 					in_run += size;
 				}
-				(void)run_first;
 				heaviest = std::max(heaviest, in_run);
 				row(n_roots);
 				if (heaviest <= XF_SUBTREE_MAX_RUN) {
 					w.n_sub_runs = (uint32_t)(table.size() / n_levels) - 1;
-					LMX_HIP(ctx, w.d_sub_table.reserve(table.size()));
-					LMX_HIP(ctx, hipMemcpy(w.d_sub_table.p, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+					LMX_HIP(ctx, upload_blocking(w.d_sub_table, table));
 				}
 			}
 		}
@@ -128,13 +120,13 @@ int world_rebuild(LmxContext* ctx, uint32_t n, const int32_t* parent, const LmxT
 		for (uint32_t e = 0; e < n; ++e) all[e] = (int32_t)e;
 		LMX_HIP(ctx, w.d_stage_entity.reserve(n));
 		LMX_HIP(ctx, w.d_stage_tr.reserve(n));
-		LMX_HIP(ctx, hipMemcpy(w.d_stage_entity.p, all.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(w.d_stage_entity.p, all));
 		if (world_all) {
-			LMX_HIP(ctx, hipMemcpy(w.d_stage_tr.p, world_all, n * sizeof(LmxTransform), hipMemcpyHostToDevice));
+			LMX_HIP(ctx, upload_blocking(w.d_stage_tr.p, world_all, n));
 			LMX_HIP(ctx, launch_xform_scatter(ctx->stream, w.dev(), w.d_slot_of_entity.p, w.d_stage_entity.p, w.d_stage_tr.p, n, XF_STAGE_RAW_WORLD));
 			LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		}
-		LMX_HIP(ctx, hipMemcpy(w.d_stage_tr.p, transforms, n * sizeof(LmxTransform), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(w.d_stage_tr.p, transforms, n));
 		LMX_HIP(ctx, launch_xform_scatter(ctx->stream, w.dev(), w.d_slot_of_entity.p, w.d_stage_entity.p, w.d_stage_tr.p, n, XF_STAGE_RAW));
 	}
 	w.bound_generation = ~0ull;
@@ -154,7 +146,7 @@ int world_download(LmxContext* ctx, bool locals, LmxTransform* out) {
 	}
 	LMX_HIP(ctx, w.d_export.reserve(w.n));
 	LMX_HIP(ctx, launch_xform_export(ctx->stream, dev, w.d_entity_of_slot.p, w.n, w.d_export.p));
-	LMX_HIP(ctx, hipMemcpyAsync(out, w.d_export.p, (size_t)w.n * sizeof(LmxTransform), hipMemcpyDeviceToHost, ctx->stream));
+	LMX_HIP(ctx, read_back(out, w.d_export.p, w.n, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
@@ -271,8 +263,7 @@ static int world_stage(LmxContext* ctx, uint32_t n, const int32_t* entity, const
 			w.stage_mark[entity[i]] = w.stage_stamp;
 		}
 		if (dup) {
-			const uint32_t stamp2 = ++w.stage_stamp;
-			(void)stamp2;
+			++w.stage_stamp;
 			ent_dedup.reserve(n);
 			tr_dedup.reserve(n);
 			for (uint32_t i = n; i-- > 0;) { // from the back: the first record seen of an entity is its last write
@@ -289,8 +280,8 @@ static int world_stage(LmxContext* ctx, uint32_t n, const int32_t* entity, const
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // staging buffers may still be read by a previous scatter
 	LMX_HIP(ctx, w.d_stage_entity.reserve(n));
 	LMX_HIP(ctx, w.d_stage_tr.reserve(n));
-	LMX_HIP(ctx, hipMemcpy(w.d_stage_entity.p, entity, n * sizeof(int32_t), hipMemcpyHostToDevice));
-	LMX_HIP(ctx, hipMemcpy(w.d_stage_tr.p, transforms, n * sizeof(LmxTransform), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(w.d_stage_entity.p, entity, n));
+	LMX_HIP(ctx, upload_blocking(w.d_stage_tr.p, transforms, n));
 	LMX_HIP(ctx, launch_xform_scatter(ctx->stream, w.dev(), w.d_slot_of_entity.p, w.d_stage_entity.p, w.d_stage_tr.p, n, mode));
 	return LMX_OK;
 }
@@ -355,11 +346,9 @@ static int world_upload_binding(LmxContext* ctx) {
 	LMX_HIP(ctx, w.d_bound_dyn.reserve(std::max<size_t>(n, 1)));
 	LMX_HIP(ctx, w.d_bound_radius.reserve(std::max<size_t>(n, 1)));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (n) {
-		LMX_HIP(ctx, hipMemcpy(w.d_bound_slot.p, slot.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(w.d_bound_dyn.p, dyn.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(w.d_bound_radius.p, w.bound_radius.data(), n * sizeof(float), hipMemcpyHostToDevice));
-	}
+	LMX_HIP(ctx, upload_blocking(w.d_bound_slot.p, slot));
+	LMX_HIP(ctx, upload_blocking(w.d_bound_dyn.p, dyn));
+	LMX_HIP(ctx, upload_blocking(w.d_bound_radius.p, w.bound_radius));
 	{ // the same binding by slot (k_xform_subtree refreshes the spheres of the slots it walks)
 		std::vector<uint32_t> dyn_of_slot(std::max<size_t>(w.n, 1), 0xffffffffu);
 		std::vector<float> radius_of_slot(std::max<size_t>(w.n, 1), 0.f);
@@ -369,8 +358,8 @@ static int world_upload_binding(LmxContext* ctx) {
 		}
 		LMX_HIP(ctx, w.d_bound_dyn_of_slot.reserve(dyn_of_slot.size()));
 		LMX_HIP(ctx, w.d_bound_radius_of_slot.reserve(radius_of_slot.size()));
-		LMX_HIP(ctx, hipMemcpy(w.d_bound_dyn_of_slot.p, dyn_of_slot.data(), dyn_of_slot.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-		LMX_HIP(ctx, hipMemcpy(w.d_bound_radius_of_slot.p, radius_of_slot.data(), radius_of_slot.size() * sizeof(float), hipMemcpyHostToDevice));
+		LMX_HIP(ctx, upload_blocking(w.d_bound_dyn_of_slot.p, dyn_of_slot));
+		LMX_HIP(ctx, upload_blocking(w.d_bound_radius_of_slot.p, radius_of_slot));
 	}
 	w.bound_generation = cs.dyn_generation;
 	return LMX_OK;
@@ -451,7 +440,7 @@ int lmx_world_set_bone_attachments(LmxContext* ctx, uint32_t n, const int32_t* e
 		if (attached[parent_entity[i]]) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "attachment %u: parent %d is itself a bone attachment (chains are not batched)", i, parent_entity[i]);
 	LMX_HIP(ctx, w.d_attach.reserve(std::max<size_t>(n, 1)));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	if (n) LMX_HIP(ctx, hipMemcpy(w.d_attach.p, att.data(), (size_t)n * sizeof(BoneAttachDevice), hipMemcpyHostToDevice));
+	LMX_HIP(ctx, upload_blocking(w.d_attach.p, att));
 	w.n_attach = n;
 	w.attach_invalidated = false;
 	w.attach_skin_instances = sk.inst.size();
@@ -533,12 +522,7 @@ int lmx_world_read_transforms(LmxContext* ctx, LmxTransform* out, uint32_t n) {
 	WorldState& w = ctx->world;
 	if (!w.built) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_world_build has not been called");
 	if (n < w.n || !out) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u transforms", w.n);
-	if (!w.n) return LMX_OK;
-	LMX_HIP(ctx, w.d_export.reserve(w.n));
-	LMX_HIP(ctx, launch_xform_export(ctx->stream, w.dev(), w.d_entity_of_slot.p, w.n, w.d_export.p));
-	LMX_HIP(ctx, hipMemcpyAsync(out, w.d_export.p, (size_t)w.n * sizeof(LmxTransform), hipMemcpyDeviceToHost, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return world_download(ctx, false, out);
 }
 
 

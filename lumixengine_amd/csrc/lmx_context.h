@@ -61,6 +61,40 @@ template <typename T> struct DevBuf {
 	}
 };
 
+// Copies between host arrays and device buffers, counted in ELEMENTS: source and destination have one element type (cast at the call
+// site where a caller's array is declared otherwise). All return hipError_t for the caller's LMX_HIP; an empty copy issues no HIP call.
+//
+// Ordering: LmxContext::stream may be a caller's non-blocking stream, and a blocking hipMemcpy is NOT ordered behind such a stream.
+// A blocking copy into a buffer that an enqueued kernel may still read therefore needs a hipStreamSynchronize(ctx->stream) in front
+// of it. An on-stream copy is ordered by the stream, but returns before a pageable source has been read: the caller's array must
+// outlive a synchronize behind it. The synchronizes stay at the call sites, where many copies share one.
+//
+// A DevBuf destination is reserved for max(n, 1) elements first (launches want a non-null pointer for an empty table); a pointer
+// destination is copied to as it is. DevBuf::reserve frees the old allocation when it grows: the contents are lost, the pointer
+// changes, and a kernel still reading the old one must have finished - the same synchronize, in front of the reserve.
+
+// precondition: the stream whose kernels use `dst` was synchronized
+template <typename T> hipError_t upload_blocking(T* dst, const T* src, size_t n) { return n ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess; }
+template <typename T> hipError_t upload_blocking(DevBuf<T>& dst, const T* src, size_t n) {
+	const hipError_t e = dst.reserve(std::max<size_t>(n, 1));
+	return e != hipSuccess ? e : upload_blocking(dst.p, src, n);
+}
+template <typename D, typename T> hipError_t upload_blocking(D&& dst, const std::vector<T>& src) { return upload_blocking(dst, src.data(), src.size()); } // D: DevBuf<T>& or T*
+
+template <typename T> hipError_t upload_on_stream(T* dst, const T* src, size_t n, hipStream_t stream) { return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess; }
+template <typename T> hipError_t upload_on_stream(DevBuf<T>& dst, const T* src, size_t n, hipStream_t stream) {
+	const hipError_t e = dst.reserve(std::max<size_t>(n, 1));
+	return e != hipSuccess ? e : upload_on_stream(dst.p, src, n, stream);
+}
+template <typename D, typename T> hipError_t upload_on_stream(D&& dst, const std::vector<T>& src, hipStream_t stream) { return upload_on_stream(dst, src.data(), src.size(), stream); }
+
+// device -> host on the stream, skipped for a null `dst`; the host array is valid after the caller's next synchronize of `stream`
+template <typename T> hipError_t read_back(T* dst, const T* src, size_t n, hipStream_t stream) { return n && dst ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess; }
+
+// device -> device: the blocking kind under upload_blocking's precondition, the on-stream kind ordered by the stream
+template <typename T> hipError_t device_copy_blocking(T* dst, const T* src, size_t n) { return n ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice) : hipSuccess; }
+template <typename T> hipError_t device_copy_on_stream(T* dst, const T* src, size_t n, hipStream_t stream) { return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, stream) : hipSuccess; }
+
 struct CullView {
 	DevBuf<int32_t> out;      // raw result: [n_frusta][out_total], one window per output shard
 	DevBuf<uint32_t> counts;  // [2][cnt_words] shard counters, double-buffered: the cull kernel clears the half the NEXT cull uses
