@@ -78,7 +78,8 @@ enum {
 	LMX_K_SORT_KEYS = 7,
 	LMX_K_ANIM_UPDATE = 8,
 	LMX_K_CULL_PATCH = 9, /* the copy + k_apply_patches launch that ships queued add / remove / set records */
-	LMX_K_COUNT = 10
+	LMX_K_POSE_SLICES = 10, /* lmx_poses_run: slice offsets + the listed instances' dual quaternions */
+	LMX_K_COUNT = 11
 };
 LMX_API int lmx_profile_enable(LmxContext* ctx, int enable);
 LMX_API int lmx_profile_reset(LmxContext* ctx);
@@ -567,6 +568,49 @@ LMX_API int lmx_draw_read_group_data(LmxContext* ctx, void* out, size_t cap_byte
 /* Device pointers of the last run for GPU consumers, valid until the next lmx_draw_run*: run records, instance buffer, group buffer,
  * d_counts = {runs, instance bytes, pairs, group records}. */
 LMX_API int lmx_draw_device_outputs(LmxContext* ctx, const LmxDrawRun** d_runs, const void** d_instance_data, const void** d_group_data, const uint32_t** d_counts);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Pose processor: PipelineImpl's PoseProcessor (renderer/pipeline.cpp:3730-3787) with computeSkeletonDualQuats (:2680-2745), between
+ * lmx_keys_run and lmx_draw_run. The model instances createSortKeys handed over (the Pose::frame stamp, :3889-3898) are packed back to
+ * back, in list order, into the frame's transient dual-quaternion buffer (offset += pose->count * sizeof(DualQuat)); every instance's part
+ * holds DualQuat {r.xyzw, d.xyzw} = toDualQuat(absolute pose[b] * inverse bind[b]) per bone, bit for bit what the reference uploads, and
+ * pose->slice of the entity - the buffer's bindless handle and the byte offset - goes into the tables lmx_draw_run writes into the skinned
+ * records (the ones lmx_draw_set_bones uploads). The list and its length are read on the device: cull -> keys -> pose slices -> draw
+ * records runs without a host wait. The absolute poses are those lmx_skin_run left in the library (pose write-back on). Deviations
+ * (DESIGN.md 4.10): one call is one batch (the reference cuts the stream into jobs of 128 instances with a transient allocation each); the
+ * frame's buffer is sized once for every instance of the skin instance table, since an instance is handed over at most once per frame.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* The skin instance (index into the table of lmx_skin_set_instances) of every entity, -1 for none; indexed like the tables of
+ * lmx_keys_set_instances. Reserves the frame's buffer and - where lmx_draw_set_bones uploaded fewer entities - grows the slice tables
+ * (kept values stay, new entries are zero). Starts a new frame. */
+LMX_API int lmx_poses_set_instances(LmxContext* ctx, uint32_t n_entities, const int32_t* skin_instance);
+/* A new frame: the cursor returns to 0, the counters to zero. handle = gpu::getBindlessHandle(slice.buffer).value of the buffer the
+ * renderer binds the dual quaternions through, base_offset = the byte offset of the frame's slice inside it. Async. */
+LMX_API int lmx_poses_begin_frame(LmxContext* ctx, uint32_t handle, uint32_t base_offset);
+/* Consumes the pose list of the LAST lmx_keys_run in place; once per view, each call appends behind the previous one. A listed entity
+ * without a skin instance (or outside the table) is counted as skipped; a slice that would pass the buffer's end sets the overflow flag
+ * and is not written; entities not listed keep their slice values (a stale pose->slice). Entries of one frame are unique by contract.
+ * LMX_ERR_NOT_BUILT without instance tables, without a key run, or without absolute poses. Async: no host synchronisation. */
+LMX_API int lmx_poses_run(LmxContext* ctx);
+/* The same pass over a caller-given host list (copied before the call returns): tests and tools. */
+LMX_API int lmx_poses_run_list(LmxContext* ctx, const int32_t* entities, uint32_t n);
+typedef struct LmxPosesCounts {
+	uint32_t instances;        /* slices written this frame */
+	uint32_t bytes;            /* the frame's cursor: bytes of the buffer in use */
+	uint32_t skipped;          /* listed entities without a skin instance */
+	uint32_t overflow;         /* != 0: a slice did not fit (never with unique entries) */
+} LmxPosesCounts;
+LMX_API int lmx_poses_counts(LmxContext* ctx, LmxPosesCounts* out); /* synchronizes the stream, as the read_* calls */
+/* pose->slice by entity, as the skinned records will carry it: the arrays hold n_entities entries (LMX_ERR_CAPACITY below the count of
+ * lmx_poses_set_instances), either may be NULL. */
+LMX_API int lmx_poses_read_slices(LmxContext* ctx, uint32_t* handle, uint32_t* offset, uint32_t n_entities);
+/* The frame's buffer from its start: at least LmxPosesCounts::bytes (LMX_ERR_CAPACITY below). A larger array also receives what lies
+ * behind the frame's slices, up to the end of the reservation (32 B per bone of the skin instance table) and of the 256 guard bytes
+ * (0xA5) behind it that no kernel writes. */
+LMX_API int lmx_poses_read_buffer(LmxContext* ctx, void* out, size_t cap_bytes);
+/* Device pointers for GPU consumers, valid until the next lmx_poses_set_instances / lmx_skin_set_instances: the frame's buffer and
+ * d_counts = {instances, bytes, skipped, overflow}. */
+LMX_API int lmx_poses_device_outputs(LmxContext* ctx, const void** d_dual_quats, const uint32_t** d_counts);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Scene ingest: the part of a serialized World (World::serialize / deserialize, engine/world.cpp:837-1043, current

@@ -29,8 +29,10 @@ WORLD_OPT_FUSED_LEVELS = 0
 SKIN_OPT_INSTANCES_PER_BLOCK = 0
 SKIN_INSTANCES_PER_BLOCK_DEFAULT = 2  # what a fresh context uses (lmx_context.h: SkinState::multi)
 (K_CULL_CLASSIFY, K_CULL_SPHERES, K_XFORM_LEVEL, K_SPHERE_REFRESH, K_POSE_PALETTE, K_SKIN_VERTICES, K_CULL_DYNAMIC) = range(7)
-KERNEL_NAMES = ["cull_classify", "cull_spheres", "xform_level", "sphere_refresh", "pose_palette", "skin_vertices", "cull_dynamic", "sort_keys", "anim_update", "cull_patch"]
+KERNEL_NAMES = ["cull_classify", "cull_spheres", "xform_level", "sphere_refresh", "pose_palette", "skin_vertices", "cull_dynamic", "sort_keys", "anim_update", "cull_patch",
+                "pose_slices"]
 K_CULL_PATCH = 9
+K_POSE_SLICES = 10
 
 SHIFTED_FRUSTUM = np.dtype(
     [("xs", "<f4", 8), ("ys", "<f4", 8), ("zs", "<f4", 8), ("ds", "<f4", 8), ("points", "<f4", (8, 3)), ("origin", "<f8", 3), ("_pad", "<f8")],
@@ -83,6 +85,8 @@ DRAW_RUN = np.dtype([(k, "<u4") for k in ("kind", "bucket", "batch", "first_pair
                                           "group", "total_count")])  # LmxDrawRun
 DRAW_VIEW = np.dtype([("camera_pos", "<f8", 3), ("frustum", SHIFTED_FRUSTUM), ("bucket_depth_sorted", "u1", 256)], align=True)  # LmxDrawView
 DRAW_COUNTS = np.dtype([("pairs", "<u4"), ("runs", "<u4"), ("instance_bytes", "<u4"), ("group_records", "<u4"), ("overflow", "<u4")])
+POSES_COUNTS = np.dtype([("instances", "<u4"), ("bytes", "<u4"), ("skipped", "<u4"), ("overflow", "<u4")])  # LmxPosesCounts
+POSES_GUARD_BYTES = 256  # behind the frame's buffer (lmx_poses_read_buffer)
 RUN_MESH, RUN_AUTOINSTANCED, RUN_SKINNED, RUN_DECAL, RUN_CURVE_DECAL, RUN_MOVED_MESH = 0, 1, 2, 3, 4, 32
 VIEWPORT = np.dtype(
     [("is_ortho", "<i4"), ("fov", "<f4"), ("ortho_size", "<f4"), ("w", "<i4"), ("h", "<i4"), ("pos", "<f8", 3), ("rot", "<f4", 4), ("near_plane", "<f4"), ("far_plane", "<f4")],
@@ -224,6 +228,14 @@ SYMBOLS = {
     "lmx_draw_read_instance_data": (_ci, [_vp, _vp, _sz]),
     "lmx_draw_read_group_data": (_ci, [_vp, _vp, _sz]),
     "lmx_draw_device_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "lmx_poses_set_instances": (_ci, [_vp, _u32, _vp]),
+    "lmx_poses_begin_frame": (_ci, [_vp, _u32, _u32]),
+    "lmx_poses_run": (_ci, [_vp]),
+    "lmx_poses_run_list": (_ci, [_vp, _vp, _u32]),
+    "lmx_poses_counts": (_ci, [_vp, _vp]),
+    "lmx_poses_read_slices": (_ci, [_vp, _vp, _vp, _u32]),
+    "lmx_poses_read_buffer": (_ci, [_vp, _vp, _sz]),
+    "lmx_poses_device_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "lmx_viewport_frustum": (_ci, [_vp, _vp]),
     "lmx_frustum_perspective": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "lmx_frustum_ortho": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
@@ -1107,6 +1119,54 @@ class DrawCommands:
         r, i, g, c = _vp(), _vp(), _vp(), _vp()
         self.ctx.check(self.lib.lmx_draw_device_outputs(self.ctx.h, C.byref(r), C.byref(i), C.byref(g), C.byref(c)))
         return r.value, i.value, g.value, c.value
+
+
+class PoseProcessor:
+    """PipelineImpl's PoseProcessor (renderer/pipeline.cpp:3730-3787) over the pose list a SortKeys run left on the device: dual-quaternion
+    slices in the frame's buffer and pose->slice by entity, where DrawCommands reads it (lmx_poses_*)."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.n_entities = 0
+
+    def setInstances(self, skin_instance):
+        a = np.ascontiguousarray(skin_instance, np.int32)
+        self.n_entities = len(a)
+        self.ctx.check(self.lib.lmx_poses_set_instances(self.ctx.h, len(a), _ptr(a)))
+
+    def beginFrame(self, handle: int, base_offset: int = 0):
+        self.ctx.check(self.lib.lmx_poses_begin_frame(self.ctx.h, int(handle), int(base_offset)))
+
+    def run(self):
+        self.ctx.check(self.lib.lmx_poses_run(self.ctx.h))
+
+    def runList(self, entities):
+        a = np.ascontiguousarray(entities, np.int32)
+        self.ctx.check(self.lib.lmx_poses_run_list(self.ctx.h, _ptr(a) if len(a) else None, len(a)))
+
+    def counts(self) -> dict:
+        c = np.zeros(1, POSES_COUNTS)
+        self.ctx.check(self.lib.lmx_poses_counts(self.ctx.h, _ptr(c)))
+        return {k: int(c[k][0]) for k in POSES_COUNTS.names}
+
+    def readSlices(self):
+        """(handle, offset) of every entity's pose->slice."""
+        h, o = np.zeros(max(self.n_entities, 1), np.uint32), np.zeros(max(self.n_entities, 1), np.uint32)
+        self.ctx.check(self.lib.lmx_poses_read_slices(self.ctx.h, _ptr(h), _ptr(o), self.n_entities))
+        return h[: self.n_entities], o[: self.n_entities]
+
+    def readBuffer(self, n_bytes: Optional[int] = None) -> np.ndarray:
+        """The frame's buffer as bytes: what the frame used, or the first n_bytes (up to the reservation + POSES_GUARD_BYTES)."""
+        n = self.counts()["bytes"] if n_bytes is None else int(n_bytes)
+        out = np.zeros(max(n, 1), np.uint8)
+        self.ctx.check(self.lib.lmx_poses_read_buffer(self.ctx.h, _ptr(out), n))
+        return out[:n]
+
+    def deviceOutputs(self):
+        d, c = _vp(), _vp()
+        self.ctx.check(self.lib.lmx_poses_device_outputs(self.ctx.h, C.byref(d), C.byref(c)))
+        return d.value, c.value
 
 
 SKIN_FUSED, SKIN_EXACT, SKIN_DQS = 0, 1, 2

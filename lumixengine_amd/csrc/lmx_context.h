@@ -475,6 +475,21 @@ struct DrawState {
 	uint32_t n = 0, n_group_values = 0; // of the last run
 };
 
+// PoseProcessor (lmx_capi_poses.hip): the skin instance of every entity, the frame's dual-quaternion buffer and its device-side cursor
+constexpr size_t POSES_GUARD_BYTES = 256; // behind the buffer: filled when it is reserved, never written by a kernel (lmx_poses_read_buffer)
+struct PosesState {
+	DevBuf<int32_t> d_skin_of_entity, d_list;
+	DevBuf<uint4> d_entries;
+	DevBuf<uint32_t> d_block_sum, d_state;
+	DevBuf<float4> d_dual_quats;
+	uint32_t n_entities = 0;
+	bool have_instances = false;
+	size_t reserved_bones = ~(size_t)0; // SkinState::bones_total the buffer was reserved for
+	uint32_t cap_bytes = 0;
+	uint32_t handle = 0, base_offset = 0; // lmx_poses_begin_frame
+	uint32_t list_n = 0;                  // lmx_poses_run_list: the source of the copy into POSES_LIST_N
+};
+
 // animation sampling (lmx_capi_anim.hip): Animation resources flattened into concatenated tables, one Animable per skin instance
 struct AnimState {
 	std::vector<AnimDevice> anims;
@@ -526,6 +541,7 @@ struct LmxContext {
 	lmx::SkinState skin;
 	lmx::KeysState keys;
 	lmx::DrawState draw;
+	lmx::PosesState poses;
 	lmx::AnimState anim;
 };
 

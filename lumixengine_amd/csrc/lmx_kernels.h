@@ -390,6 +390,32 @@ hipError_t launch_draw_runs(hipStream_t s, const DrawDevice& d, const DrawViewDe
 hipError_t launch_draw_encode(hipStream_t s, const DrawDevice& d, const DrawViewDevice& v);  // (behind the sums of front / run_bytes) run + instance records
 hipError_t launch_draw_groups(hipStream_t s, const DrawDevice& d, const DrawViewDevice& v);  // the "fill instance data" block
 
+// ---- PoseProcessor (pose_kernels.hip): the listed instances' dual quaternions packed into the frame's buffer, pose->slice by entity ----
+// Frame state words. The first four are LmxPosesCounts; POSES_BYTES is the frame's cursor.
+enum { POSES_INSTANCES = 0, POSES_BYTES = 1, POSES_SKIPPED = 2, POSES_OVERFLOW = 3, POSES_BASE = 4 /* the cursor the running pass started from */,
+	POSES_LIST_N = 5 /* the length of a caller-given list */, POSES_STATE_WORDS = 8 };
+constexpr uint32_t POSE_BONE_BYTES = 32;  // sizeof(DualQuat)
+constexpr uint32_t POSE_BLOCK = 256;
+constexpr uint32_t POSE_GRID = 256;       // blocks of the two slice steps: each owns a contiguous part of the list
+constexpr uint32_t POSE_DQ_GRID = 1024;   // blocks of the dual-quaternion step: 4096 waves stride over the list's entries
+struct PosesDevice {
+	const int32_t* list;           // entities, in hand-over order
+	const uint32_t* list_count;    // on the device: KEYS_N_POSES of the last key run, or POSES_LIST_N
+	uint32_t list_cap;             // entries the list and `entries` hold (<= 2^31)
+	const int32_t* skin_of_entity; uint32_t n_entities; // skin instance by entity, -1: none
+	const SkinInstance* inst; uint32_t n_inst;
+	const float* pose_pos; const float4* pose_rot;      // absolute poses (lmx_skin_run with pose write-back)
+	const float* inv_pos; const float4* inv_rot;
+	uint4* entries;                // [list_cap] {slice offset (in: entity), first pose bone, n_bones, first model bone}; y = 0xffffffff: no slice
+	uint32_t* block_sum;           // [POSE_GRID]
+	uint32_t* state;               // POSES_*
+	float4* dual_quats; uint32_t cap_bytes;
+	uint32_t handle, base_offset;
+	uint32_t *bones_handle, *bones_offset; uint32_t n_table; // DrawDevice::bones_* (by entity)
+};
+hipError_t launch_pose_slices(hipStream_t s, const PosesDevice& d);     // sizes, offsets, slice tables, cursor and counters
+hipError_t launch_pose_dual_quats(hipStream_t s, const PosesDevice& d); // (behind launch_pose_slices) the slices' contents
+
 // Pose::computeAbsolute + computeSkinMatrices (+ optional dual-quaternion palette), one wave per PoseGroup
 hipError_t launch_pose_palette(hipStream_t s, const SkinInstance* inst, const PoseGroup* groups, const uint32_t n_groups[3] /* by capacity 4, 2, 1 */,
 	const float* rel_pos, const float4* rel_rot, float* pose_pos, float4* pose_rot, const uint32_t* level_items, const uint16_t* level_off,

@@ -110,6 +110,9 @@ struct PoseBridge {
 
 	const char* lastError() const { return lmx_last_error(m_ctx); }
 
+	// the skinned instances' entities: entities()[i] carries skin instance i (GpuPoseProcessor::setInstances)
+	const std::vector<EntityRef>& entities() const { return m_entities; }
+
 private:
 	LmxContext* m_ctx;
 	std::vector<EntityRef> m_entities;
