@@ -87,6 +87,9 @@ DRAW_VIEW = np.dtype([("camera_pos", "<f8", 3), ("frustum", SHIFTED_FRUSTUM), ("
 DRAW_COUNTS = np.dtype([("pairs", "<u4"), ("runs", "<u4"), ("instance_bytes", "<u4"), ("group_records", "<u4"), ("overflow", "<u4")])
 POSES_COUNTS = np.dtype([("instances", "<u4"), ("bytes", "<u4"), ("skipped", "<u4"), ("overflow", "<u4")])  # LmxPosesCounts
 POSES_GUARD_BYTES = 256  # behind the frame's buffer (lmx_poses_read_buffer)
+# the launch geometry of pose_kernels.hip (lmx_kernels.h; tests/test_pose_constants.py holds the two together): threads per block, blocks of
+# the two slice steps - each owns a contiguous part of the list - and blocks of the dual-quaternion step (POSE_BLOCK / 64 waves each)
+POSE_BLOCK, POSE_GRID, POSE_DQ_GRID = 256, 256, 1024
 RUN_MESH, RUN_AUTOINSTANCED, RUN_SKINNED, RUN_DECAL, RUN_CURVE_DECAL, RUN_MOVED_MESH = 0, 1, 2, 3, 4, 32
 VIEWPORT = np.dtype(
     [("is_ortho", "<i4"), ("fov", "<f4"), ("ortho_size", "<f4"), ("w", "<i4"), ("h", "<i4"), ("pos", "<f8", 3), ("rot", "<f4", 4), ("near_plane", "<f4"), ("far_plane", "<f4")],

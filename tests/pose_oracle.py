@@ -60,9 +60,62 @@ def dual_quats(oracle):
     return cache[oracle.kind]
 
 
-def upload(api, ctx):
-    """The scene on `ctx` with absolute poses left by lmx_skin_run; returns the Skinning wrapper."""
-    sc = scene()
+N_DENSE = 4500  # more than the waves of the dual-quaternion step (api.POSE_DQ_GRID * api.POSE_BLOCK / 64): they take a second pass
+DENSE_WEIGHTS = (0.22, 0.22, 0.22, 0.22, 0.03, 0.03, 0.03, 0.03)  # of BONES: towards the small skeletons, ~17 bones per instance
+
+
+@functools.lru_cache(maxsize=None)
+def dense_scene():
+    """scene()'s eight models under N_DENSE instances - lists that span waves, tiles and blocks of pose_kernels.hip. An instance never has
+    the model of the one before it (equal sizes side by side hide a prefix that is off by one entry), every model is picked at least 20
+    times, 60-80 k bones in all; a random relative pose per instance. Never modified by a test."""
+    small = scene()
+    w = np.array(DENSE_WEIGHTS)
+    rng = np.random.default_rng(61)
+    pick = rng.choice(len(BONES), size=N_DENSE, p=w).astype(np.int32)
+    for i in range(1, N_DENSE):
+        if pick[i] == pick[i - 1]:
+            p = w.copy()
+            p[pick[i - 1]] = 0.0
+            pick[i] = rng.choice(len(BONES), p=p / p.sum())
+    bones = np.array([BONES[m] for m in pick])
+    assert (pick[1:] != pick[:-1]).all() and np.bincount(pick, minlength=len(BONES)).min() >= 20 and 60_000 <= bones.sum() <= 80_000
+    poses = [None] * N_DENSE
+    for m, nb in enumerate(BONES):  # one draw per model: instance k of the model gets row k
+        of_model = np.flatnonzero(pick == m)
+        pos, rot = scenes.relative_poses(len(of_model), nb, seed=400 + m)
+        for k, i in enumerate(of_model):
+            poses[i] = (pos[k : k + 1], rot[k : k + 1])
+    return {"skel": small["skel"], "meshes": small["meshes"], "pick": pick, "bones": bones,
+            "rel_pos": np.concatenate([p[0].reshape(-1, 3) for p in poses]), "rel_rot": np.concatenate([p[1].reshape(-1, 4) for p in poses]), "poses": poses}
+
+
+def dense_dual_quats(oracle):
+    """dual_quats() of the dense scene (computed once per oracle, a model's instances in one call)."""
+    cache = dense_dual_quats.__dict__.setdefault("cache", {})
+    if oracle.kind not in cache:
+        sc = dense_scene()
+        out = [None] * N_DENSE
+        for m, s in enumerate(sc["skel"]):
+            of_model = np.flatnonzero(sc["pick"] == m)
+            pos = np.concatenate([sc["poses"][i][0] for i in of_model])
+            rot = np.concatenate([sc["poses"][i][1] for i in of_model])
+            apos, arot = oracle.pose_compute_absolute(pos, rot, s["parents"], s["first_nonroot"])
+            dq = oracle.dual_quats(apos, arot, oracle.invert_bind(s["bind"]))
+            for k, i in enumerate(of_model):
+                out[i] = dq[k]
+        cache[oracle.kind] = out
+    return cache[oracle.kind]
+
+
+def assert_slices_hold(buf, slices, want_dq, bones, what=""):
+    """Every slice {entity: (offset, instance)} of the frame's buffer `buf` holds its instance's dual quaternions (`bones`: by instance)."""
+    for e, (off, inst) in slices.items():
+        got = buf[off : off + DUAL_QUAT_BYTES * int(bones[inst])].tobytes()
+        assert got == np.ascontiguousarray(want_dq[inst]).tobytes(), f"{what}: entity {e} (instance {inst}, {bones[inst]} bones): dual quaternions differ"
+
+
+def _upload(api, ctx, sc):
     sk = api.Skinning(ctx)
     sk.setMode(True)
     sk.setPoseWriteback(True)
@@ -72,3 +125,13 @@ def upload(api, ctx):
     sk.uploadPoses(sc["rel_pos"], sc["rel_rot"])
     sk.run()
     return sk
+
+
+def upload(api, ctx):
+    """The scene on `ctx` with absolute poses left by lmx_skin_run; returns the Skinning wrapper."""
+    return _upload(api, ctx, scene())
+
+
+def upload_dense(api, ctx):
+    """upload() of the dense scene."""
+    return _upload(api, ctx, dense_scene())

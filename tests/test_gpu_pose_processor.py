@@ -22,10 +22,7 @@ def entity_table():
 
 
 def assert_slices_hold(buf, slices, want_dq, what=""):
-    bones = PO.scene()["bones"]
-    for e, (off, inst) in slices.items():
-        got = buf[off : off + PO.DUAL_QUAT_BYTES * int(bones[inst])].tobytes()
-        assert got == np.ascontiguousarray(want_dq[inst]).tobytes(), f"{what}: entity {e} (instance {inst}, {bones[inst]} bones): dual quaternions differ"
+    PO.assert_slices_hold(buf, slices, want_dq, PO.scene()["bones"], what)
 
 
 def test_given_list_bit_exact(gpu_ctx, live_oracle):
@@ -95,12 +92,12 @@ def test_append_and_reset(gpu_ctx, oracle_port):
     assert_slices_hold(pp.readBuffer(), s3, want_dq, "second frame")
 
 
-def chain_scene():
+def chain_scene(n_mesh=400, n_skinned=PO.N_INSTANCES, seed=51):
     """~400 mesh entities in a box, 40 of them skinned (the pose scene's instances) over two models whose LOD holds a SKINNED mesh - one
-    of them next to a RIGID mesh - the rest one rigid model."""
-    base = scenes.cull_scene(400, 300.0, seed=51, big_fraction=0.0)
+    of them next to a RIGID mesh - the rest one rigid model. (tests/test_gpu_pose_lists.py asks for a larger one.)"""
+    base = scenes.cull_scene(n_mesh, 300.0, seed=seed, big_fraction=0.0)
     n = len(base["entity"])
-    rng = np.random.default_rng(52)
+    rng = np.random.default_rng(seed + 1)
     models = np.zeros(3, api.KEYS_MODEL)
     models["lod_distances"][:] = np.finfo(np.float32).max
     models["lod_indices"]["from"], models["lod_indices"]["to"] = 0, -1
@@ -108,9 +105,9 @@ def chain_scene():
         models["lod_indices"][m][0] = (0, count - 1)
         models["first_mesh"][m], models["mesh_count"][m] = first, count
     mesh_types = np.array([0, 1, 0, 1], np.uint8)  # model 0: rigid; model 1: skinned + rigid; model 2: skinned
-    skinned = rng.choice(n, size=PO.N_INSTANCES, replace=False)
+    skinned = rng.choice(n, size=n_skinned, replace=False)
     model = np.zeros(n, np.int32)
-    model[skinned] = 1 + (np.arange(PO.N_INSTANCES) % 2)
+    model[skinned] = 1 + (np.arange(n_skinned) % 2)
     counts = models["mesh_count"][model].astype(np.uint32)
     material_offset = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint32)
     mm = np.zeros(int(counts.sum()), api.MESH_MATERIAL)
@@ -122,10 +119,10 @@ def chain_scene():
           "flags": np.full(n, 6, np.uint8), "dirty": np.zeros(n, np.uint8), "pose_frame": np.zeros(n, np.uint32), "layer_to_bucket": layer_to_bucket,
           "bucket_depth_sorted": np.array([0], np.uint8)}
     table = np.full(n, -1, np.int32)
-    table[skinned] = rng.permutation(PO.N_INSTANCES)
+    table[skinned] = rng.permutation(n_skinned)
     tr = scenes.random_transforms(rng, n, 1.0)
     tr["pos"] = base["pos"]
-    return base, sc, scenes.draw_tables(sc, n, seed=53, extent=300.0), tr, table, set(int(e) for e in skinned)
+    return base, sc, scenes.draw_tables(sc, n, seed=seed + 2, extent=300.0), tr, table, set(int(e) for e in skinned)
 
 
 def test_chain_from_the_key_run_to_the_draw_records(oracle_port):
