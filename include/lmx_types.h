@@ -197,6 +197,18 @@ typedef struct LmxDrawCounts {
 	uint32_t overflow;       /* != 0: an output buffer was too small (never with library-sized buffers) */
 } LmxDrawCounts;
 
+/* ---- fillClusters inputs (renderer/pipeline.cpp:3387-3410) ---- */
+
+/* PointLight (renderer/render_module.h:156-171) as fillClusters reads it, by entity index. sizeof == 32. */
+typedef struct LmxPointLight {
+	float color[3];
+	float intensity;
+	float range;
+	float fov;
+	float attenuation_param;
+	uint32_t flags;
+} LmxPointLight;
+
 /* ---- animation sampling inputs (animation/animation.h:86-115, animation.cpp:29-204) ---- */
 
 typedef struct LmxAnimConstTranslation { /* Animation::ConstTranslationTrack */

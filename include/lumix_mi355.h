@@ -756,6 +756,100 @@ LMX_API int lmx_im_read_indirect(LmxInstancedModels* im, uint32_t view_slot, Lmx
  * (LmxImInstance layout, 32 B), indirect records (LmxImIndirect) and per-model LmxImCounts. */
 LMX_API int lmx_im_device_outputs(LmxInstancedModels* im, uint32_t view_slot, const void** d_records, const void** d_indirect, const void** d_counts);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Clustered lights and probes: PipelineImpl::fillClusters (renderer/pipeline.cpp:3327-3684) behind the light query's cull. The visible
+ * LOCAL_LIGHT entities become 64-byte ClusterLight records (:3331-3340, :3387-3410), the enabled environment / reflection probes their
+ * records (:3349-3366, :3500-3538), and all three are binned into the view's cluster grid ((w + 63) / 64, (h + 63) / 64, 16): `clusters`
+ * {offset, lights_count, env_probes_count, refl_probes_count} and `map`, a cluster's segment holding its light indices ascending, then
+ * its environment probe indices, then its reflection probe indices - what the reference's three sequential fill passes leave
+ * (:3628-3667). The list and its length are read on the device: cull -> clusters runs without a host wait. Deviations:
+ * disabled probes are left out (the reference sorts and bins their uninitialised records); the probe sort is stable (ties keep module
+ * order); the shadow atlas (:3384-3442) stays with the engine, the run only carries atlas_idx from a table; the light order is the cull
+ * result's; the z range 0.1 .. 10000 is hard-coded as in the reference.
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum { LMX_CLUSTER_MAX_XY = 64, LMX_CLUSTER_Z = 16, LMX_CLUSTER_MAX_PROBES = 1024 };
+/* The cluster planes of a view (:3464-3495): size = the grid, xplanes[size[0] + 1], yplanes[size[1] + 1], zplanes[17] as {n.xyz, -dot(n, p)},
+ * relative to the frustum's origin; entries behind the used ones are zero. */
+typedef struct LmxClusterPlanes {
+	uint32_t size[3];
+	uint32_t _pad;
+	float xplanes[LMX_CLUSTER_MAX_XY + 1][4];
+	float yplanes[LMX_CLUSTER_MAX_XY + 1][4];
+	float zplanes[LMX_CLUSTER_Z + 1][4];
+} LmxClusterPlanes;
+/* Host-only, needs no context: built per view with libm's powf and the reference's operation order, bit for bit. LMX_ERR_CAPACITY for a
+ * viewport of more than 64 x 64 clusters (the reference's arrays hold 65 planes). */
+LMX_API int lmx_clusters_planes(const LmxShiftedFrustum* frustum, uint32_t viewport_w, uint32_t viewport_h, LmxClusterPlanes* out);
+/* (LmxPointLight - PointLight as fillClusters reads it, by entity index - is declared in lmx_types.h.) */
+/* EnvironmentProbe (render_module.h:193-203), byte-compatible: sizeof == 136. flags & LMX_PROBE_ENABLED: the probe takes part. */
+typedef struct LmxEnvProbe {
+	float inner_range[3];
+	float outer_range[3];
+	uint32_t flags;
+	float sh_coefs[9][3];
+} LmxEnvProbe;
+/* What fillClusters reads of a ReflectionProbe (render_module.h:175-189). sizeof == 20. */
+typedef struct LmxReflProbe {
+	float half_extents[3];
+	uint32_t texture_id;
+	uint32_t flags;
+} LmxReflProbe;
+enum { LMX_PROBE_ENABLED = 1 << 2 };
+/* What a run reads of the view: cp.pos, cp.frustum and m_viewport.w / h. sizeof == 288. */
+typedef struct LmxClusterView {
+	double camera_pos[3];
+	LmxShiftedFrustum frustum;
+	uint32_t viewport_w, viewport_h;
+} LmxClusterView;
+typedef struct LmxClustersCounts {
+	uint32_t lights;       /* listed lights (with overflow bit 0: more than max_lights) */
+	uint32_t env_probes;   /* enabled probes */
+	uint32_t refl_probes;
+	uint32_t map_entries;  /* saturates at 2^32 - 1 */
+	uint32_t overflow;     /* bit 0: more listed lights than max_lights, bit 1: more map entries than map_capacity. With a bit set the counts are
+	                          the sizes a larger lmx_clusters_reserve needs, nothing was written past a buffer, the outputs are not to be used */
+} LmxClustersCounts;
+/* The point lights by entity index; an entity past the table reads as zero (as every table of the draw pass). */
+LMX_API int lmx_clusters_set_lights(LmxContext* ctx, uint32_t n_entities, const LmxPointLight* lights);
+/* m_shadow_atlas.map by entity index: the atlas slot of a light, 0xffffffff for none. NULL (or no call): 0xffffffff for every entity. */
+LMX_API int lmx_clusters_set_atlas(LmxContext* ctx, uint32_t n_entities, const uint32_t* atlas_idx);
+/* RenderModule::getEnvironmentProbes / getReflectionProbes with their entity lists (module order). Each kind holds at most
+ * LMX_CLUSTER_MAX_PROBES (LMX_ERR_CAPACITY above). The enabled probes' order - ascending volume product (:3512-3538), ties by module
+ * index - is a property of the tables and is fixed here; positions and rotations are read at run time. */
+LMX_API int lmx_clusters_set_probes(LmxContext* ctx, uint32_t n_env, const LmxEnvProbe* env, const int32_t* env_entities, uint32_t n_refl,
+	const LmxReflProbe* refl, const int32_t* refl_entities);
+/* Sizes of the `lights` (records) and `map` (entries) buffers. Each is followed by a 256-byte guard no kernel writes. */
+LMX_API int lmx_clusters_reserve(LmxContext* ctx, uint32_t max_lights, uint32_t map_capacity);
+/* fillClusters over the LOCAL_LIGHT list of frustum `frustum` of the cull result in slot `view`. World positions and rotations come from
+ * where lmx_draw_run takes them (lmx_draw_set_transforms, or the bound world: lmx_draw_bind_world). LMX_ERR_NOT_BUILT without light
+ * tables, without a reserve, or when the slot's cull did not cover LOCAL_LIGHT. Async: no host synchronisation. */
+LMX_API int lmx_clusters_run(LmxContext* ctx, uint32_t view, uint32_t frustum, const LmxClusterView* cv);
+/* The same pass over a caller-given host list (copied before the call returns): tests and tools. */
+LMX_API int lmx_clusters_run_list(LmxContext* ctx, const LmxClusterView* cv, const int32_t* entities, uint32_t n);
+LMX_API int lmx_clusters_counts(LmxContext* ctx, LmxClustersCounts* out); /* synchronizes the stream, as the read_* calls */
+/* Read-outs of the last run. `cap` counts elements (64-byte light records, entities, 16-byte clusters, map entries, 208 / 48-byte probe
+ * records): LMX_ERR_CAPACITY below what the run left in the buffer; a larger array also receives what lies behind, up to the end of
+ * the buffer's guard (0xA5). size (optional) = the cluster grid. */
+LMX_API int lmx_clusters_read_lights(LmxContext* ctx, void* out, uint32_t cap);
+LMX_API int lmx_clusters_read_light_entities(LmxContext* ctx, int32_t* out, uint32_t cap);
+LMX_API int lmx_clusters_read_clusters(LmxContext* ctx, void* out, uint32_t cap, uint32_t* size);
+LMX_API int lmx_clusters_read_map(LmxContext* ctx, int32_t* out, uint32_t cap);
+LMX_API int lmx_clusters_read_probes(LmxContext* ctx, void* env, uint32_t env_cap, void* refl, uint32_t refl_cap);
+/* Device pointers for GPU consumers, valid until the next lmx_clusters_reserve / set_probes: the five shader buffers, the lights'
+ * entities, d_counts = LmxClustersCounts, and the grid of the last run. */
+typedef struct LmxClustersDevice {
+	const void* d_lights;
+	const int32_t* d_light_entities;
+	const void* d_clusters;
+	const int32_t* d_map;
+	const void* d_env_probes;
+	const void* d_refl_probes;
+	const uint32_t* d_counts;
+	uint32_t size[3];
+	uint32_t _pad;
+} LmxClustersDevice;
+LMX_API int lmx_clusters_device_outputs(LmxContext* ctx, LmxClustersDevice* out);
+
 LMX_API const char* lmx_version(void);
 
 #ifdef __cplusplus

@@ -90,6 +90,25 @@ POSES_GUARD_BYTES = 256  # behind the frame's buffer (lmx_poses_read_buffer)
 # the launch geometry of pose_kernels.hip (lmx_kernels.h; tests/test_pose_constants.py holds the two together): threads per block, blocks of
 # the two slice steps - each owns a contiguous part of the list - and blocks of the dual-quaternion step (POSE_BLOCK / 64 waves each)
 POSE_BLOCK, POSE_GRID, POSE_DQ_GRID = 256, 256, 1024
+# fillClusters (lmx_clusters_*): table records, the view, the counters and the output records of renderer/pipeline.cpp:3331-3366
+POINT_LIGHT = np.dtype([("color", "<f4", 3), ("intensity", "<f4"), ("range", "<f4"), ("fov", "<f4"), ("attenuation_param", "<f4"), ("flags", "<u4")])  # LmxPointLight
+ENV_PROBE = np.dtype([("inner_range", "<f4", 3), ("outer_range", "<f4", 3), ("flags", "<u4"), ("sh_coefs", "<f4", (9, 3))])  # LmxEnvProbe
+REFL_PROBE = np.dtype([("half_extents", "<f4", 3), ("texture_id", "<u4"), ("flags", "<u4")])  # LmxReflProbe
+PROBE_ENABLED = 1 << 2
+CLUSTER_PLANES = np.dtype([("size", "<u4", 3), ("_pad", "<u4"), ("xplanes", "<f4", (65, 4)), ("yplanes", "<f4", (65, 4)), ("zplanes", "<f4", (17, 4))])  # LmxClusterPlanes
+CLUSTER_VIEW = np.dtype([("camera_pos", "<f8", 3), ("frustum", SHIFTED_FRUSTUM), ("viewport_w", "<u4"), ("viewport_h", "<u4")], align=True)  # LmxClusterView
+CLUSTERS_COUNTS = np.dtype([("lights", "<u4"), ("env_probes", "<u4"), ("refl_probes", "<u4"), ("map_entries", "<u4"), ("overflow", "<u4")])  # LmxClustersCounts
+CLUSTER_LIGHT = np.dtype([("pos", "<f4", 3), ("radius", "<f4"), ("rot", "<f4", 4), ("color", "<f4", 3), ("attenuation_param", "<f4"), ("atlas_idx", "<u4"), ("fov", "<f4"),
+                          ("padding", "<f4", 2)])  # ClusterLight, 64 B
+CLUSTER = np.dtype([("offset", "<u4"), ("lights_count", "<u4"), ("env_probes_count", "<u4"), ("refl_probes_count", "<u4")])
+CLUSTER_ENV_PROBE = np.dtype([("pos", "<f4", 3), ("pad0", "<f4"), ("rot", "<f4", 4), ("inner_range", "<f4", 3), ("pad1", "<f4"), ("outer_range", "<f4", 3), ("pad2", "<f4"),
+                              ("sh_coefs", "<f4", (9, 4))])  # 208 B
+CLUSTER_REFL_PROBE = np.dtype([("pos", "<f4", 3), ("layer", "<u4"), ("rot", "<f4", 4), ("half_extents", "<f4", 3), ("pad1", "<f4")])  # 48 B
+CLUSTERS_GUARD_BYTES = 256  # behind the light records, their entities and the map (lmx_clusters_read_*)
+CLUSTER_MAX_PROBES = 1024
+# the launch geometry of cluster_kernels.hip (lmx_kernels.h; tests/test_cluster_constants.py holds the two together): threads per block = the
+# light tile of the gather, blocks of the record step that stride over the list, blocks of the count / fill steps
+CLUSTER_BLOCK, CLUSTER_REC_GRID, CLUSTER_GRID = 256, 256, 1024
 RUN_MESH, RUN_AUTOINSTANCED, RUN_SKINNED, RUN_DECAL, RUN_CURVE_DECAL, RUN_MOVED_MESH = 0, 1, 2, 3, 4, 32
 VIEWPORT = np.dtype(
     [("is_ortho", "<i4"), ("fov", "<f4"), ("ortho_size", "<f4"), ("w", "<i4"), ("h", "<i4"), ("pos", "<f8", 3), ("rot", "<f4", 4), ("near_plane", "<f4"), ("far_plane", "<f4")],
@@ -239,6 +258,20 @@ SYMBOLS = {
     "lmx_poses_read_slices": (_ci, [_vp, _vp, _vp, _u32]),
     "lmx_poses_read_buffer": (_ci, [_vp, _vp, _sz]),
     "lmx_poses_device_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "lmx_clusters_planes": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_clusters_set_lights": (_ci, [_vp, _u32, _vp]),
+    "lmx_clusters_set_atlas": (_ci, [_vp, _u32, _vp]),
+    "lmx_clusters_set_probes": (_ci, [_vp, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "lmx_clusters_reserve": (_ci, [_vp, _u32, _u32]),
+    "lmx_clusters_run": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_clusters_run_list": (_ci, [_vp, _vp, _vp, _u32]),
+    "lmx_clusters_counts": (_ci, [_vp, _vp]),
+    "lmx_clusters_read_lights": (_ci, [_vp, _vp, _u32]),
+    "lmx_clusters_read_light_entities": (_ci, [_vp, _vp, _u32]),
+    "lmx_clusters_read_clusters": (_ci, [_vp, _vp, _u32, _vp]),
+    "lmx_clusters_read_map": (_ci, [_vp, _vp, _u32]),
+    "lmx_clusters_read_probes": (_ci, [_vp, _vp, _u32, _vp, _u32]),
+    "lmx_clusters_device_outputs": (_ci, [_vp, _vp]),
     "lmx_viewport_frustum": (_ci, [_vp, _vp]),
     "lmx_frustum_perspective": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "lmx_frustum_ortho": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
@@ -1170,6 +1203,105 @@ class PoseProcessor:
         d, c = _vp(), _vp()
         self.ctx.check(self.lib.lmx_poses_device_outputs(self.ctx.h, C.byref(d), C.byref(c)))
         return d.value, c.value
+
+
+def clusters_planes(frustum, w: int, h: int) -> np.ndarray:
+    """The cluster planes of a view (renderer/pipeline.cpp:3464-3495), built on the host; LumixError(CAPACITY) above 64 x 64 clusters."""
+    f = np.ascontiguousarray(frustum, SHIFTED_FRUSTUM).reshape(-1)[:1]
+    out = np.zeros(1, CLUSTER_PLANES)
+    rc = load_library().lmx_clusters_planes(_ptr(f), int(w), int(h), _ptr(out))
+    if rc:
+        raise LumixError(rc, "lmx_clusters_planes")
+    return out
+
+
+def cluster_view(camera_pos, frustum, w: int, h: int) -> np.ndarray:
+    """LmxClusterView: what PipelineImpl::fillClusters reads of a view (cp.pos, cp.frustum, m_viewport.w / h)."""
+    v = np.zeros(1, CLUSTER_VIEW)
+    v["camera_pos"] = camera_pos
+    v["frustum"] = np.ascontiguousarray(frustum, SHIFTED_FRUSTUM).reshape(-1)[0]
+    v["viewport_w"], v["viewport_h"] = w, h
+    return v
+
+
+class ClusterFiller:
+    """PipelineImpl::fillClusters (renderer/pipeline.cpp:3327-3684) over the LOCAL_LIGHT list a cull left on the device: light and probe
+    records, `clusters` and `map` (lmx_clusters_*). Transforms come from DrawCommands.setTransforms / bindWorld."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.max_lights = self.map_capacity = 0
+
+    def setLights(self, lights):
+        a = np.ascontiguousarray(lights, POINT_LIGHT)
+        self.ctx.check(self.lib.lmx_clusters_set_lights(self.ctx.h, len(a), _ptr(a) if len(a) else None))
+
+    def setAtlas(self, atlas_idx=None):
+        a = None if atlas_idx is None else np.ascontiguousarray(atlas_idx, np.uint32)
+        self.ctx.check(self.lib.lmx_clusters_set_atlas(self.ctx.h, 0 if a is None else len(a), _ptr(a)))
+
+    def setProbes(self, env=None, env_entities=None, refl=None, refl_entities=None):
+        e = np.zeros(0, ENV_PROBE) if env is None else np.ascontiguousarray(env, ENV_PROBE)
+        r = np.zeros(0, REFL_PROBE) if refl is None else np.ascontiguousarray(refl, REFL_PROBE)
+        ee = np.ascontiguousarray(np.zeros(0) if env_entities is None else env_entities, np.int32)
+        re_ = np.ascontiguousarray(np.zeros(0) if refl_entities is None else refl_entities, np.int32)
+        assert len(e) == len(ee) and len(r) == len(re_)
+        self.ctx.check(self.lib.lmx_clusters_set_probes(self.ctx.h, len(e), _ptr(e) if len(e) else None, _ptr(ee) if len(e) else None, len(r), _ptr(r) if len(r) else None,
+                                                        _ptr(re_) if len(r) else None))
+
+    def reserve(self, max_lights: int, map_capacity: int):
+        self.ctx.check(self.lib.lmx_clusters_reserve(self.ctx.h, int(max_lights), int(map_capacity)))
+        self.max_lights, self.map_capacity = int(max_lights), int(map_capacity)
+
+    def run(self, view: np.ndarray, cull_view: int = 0, frustum: int = 0):
+        v = np.ascontiguousarray(view, CLUSTER_VIEW)
+        self.ctx.check(self.lib.lmx_clusters_run(self.ctx.h, cull_view, frustum, _ptr(v)))
+
+    def runList(self, view: np.ndarray, entities):
+        v = np.ascontiguousarray(view, CLUSTER_VIEW)
+        a = np.ascontiguousarray(entities, np.int32)
+        self.ctx.check(self.lib.lmx_clusters_run_list(self.ctx.h, _ptr(v), _ptr(a) if len(a) else None, len(a)))
+
+    def counts(self) -> dict:
+        c = np.zeros(1, CLUSTERS_COUNTS)
+        self.ctx.check(self.lib.lmx_clusters_counts(self.ctx.h, _ptr(c)))
+        return {k: int(c[k][0]) for k in CLUSTERS_COUNTS.names}
+
+    def _read(self, fn, dtype, used: int, n):
+        n = used if n is None else int(n)
+        out = np.zeros(max(n, 1), dtype)
+        self.ctx.check(fn(self.ctx.h, _ptr(out), n))
+        return out[:n]
+
+    def readLights(self, n: Optional[int] = None) -> np.ndarray:
+        """The light records the run left, or the first n (up to max_lights + the guard's 4 records)."""
+        return self._read(self.lib.lmx_clusters_read_lights, CLUSTER_LIGHT, min(self.counts()["lights"], self.max_lights), n)
+
+    def readLightEntities(self, n: Optional[int] = None) -> np.ndarray:
+        return self._read(self.lib.lmx_clusters_read_light_entities, np.int32, min(self.counts()["lights"], self.max_lights), n)
+
+    def readMap(self, n: Optional[int] = None) -> np.ndarray:
+        return self._read(self.lib.lmx_clusters_read_map, np.int32, min(self.counts()["map_entries"], self.map_capacity), n)
+
+    def readClusters(self):
+        """(clusters, (size.x, size.y, size.z))"""
+        size = np.zeros(3, np.uint32)
+        out = np.zeros(64 * 64 * 16, CLUSTER)
+        self.ctx.check(self.lib.lmx_clusters_read_clusters(self.ctx.h, _ptr(out), len(out), _ptr(size)))
+        return out[: int(size.prod())].copy(), tuple(int(x) for x in size)
+
+    def readProbes(self):
+        """(environment probe records, reflection probe records), enabled ones in output order"""
+        c = self.counts()
+        e, r = np.zeros(max(c["env_probes"], 1), CLUSTER_ENV_PROBE), np.zeros(max(c["refl_probes"], 1), CLUSTER_REFL_PROBE)
+        self.ctx.check(self.lib.lmx_clusters_read_probes(self.ctx.h, _ptr(e), len(e), _ptr(r), len(r)))
+        return e[: c["env_probes"]], r[: c["refl_probes"]]
+
+    def deviceOutputs(self) -> dict:
+        out = np.zeros(1, np.dtype([(k, "<u8") for k in ("lights", "light_entities", "clusters", "map", "env_probes", "refl_probes", "counts")] + [("size", "<u4", 3), ("_pad", "<u4")]))
+        self.ctx.check(self.lib.lmx_clusters_device_outputs(self.ctx.h, _ptr(out)))
+        return {k: (tuple(int(x) for x in out[k][0]) if k == "size" else int(out[k][0])) for k in out.dtype.names if k != "_pad"}
 
 
 SKIN_FUSED, SKIN_EXACT, SKIN_DQS = 0, 1, 2

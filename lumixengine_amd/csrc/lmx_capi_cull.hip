@@ -611,6 +611,7 @@ int lmx_cull(LmxContext* ctx, uint32_t view, const LmxShiftedFrustum* frusta, ui
 		LMX_HIP(ctx, launch_cull_dynamic(ctx->stream, dyn_view(cs), dyn_begin, dyn_end, cs.dyn_tt, fr, (int)n_frusta, po));
 	}
 	v.valid = true;
+	v.culled_type = type;
 	if (v.ext_out) return cull_view_consolidate(ctx, v); // a bound output receives the contiguous form right away
 	return LMX_OK;
 }

@@ -109,6 +109,7 @@ struct CullView {
 	uint32_t out_start[MAX_TYPES] = {};
 	uint32_t out_cap[MAX_TYPES] = {};
 	bool valid = false;       // holds a cull result
+	uint8_t culled_type = LMX_TYPE_ALL; // the `type` that cull was asked for
 	bool finalized = false;   // totals / pref are current for that result
 	bool consolidated = false;
 	// caller-owned buffers for the CONSOLIDATED result (lmx_cull_bind_output)
@@ -490,6 +491,27 @@ struct PosesState {
 	uint32_t list_n = 0;                  // lmx_poses_run_list: the source of the copy into POSES_LIST_N
 };
 
+// fillClusters (lmx_capi_clusters.hip): the light / atlas tables by entity, the enabled probes in output order, buffers and outputs of the last run
+constexpr size_t CLUSTERS_GUARD_BYTES = 256; // behind the light records, their entities and the map: filled at the reserve, never written by a kernel
+struct ClustersState {
+	DevBuf<LmxPointLight> d_light_tab;
+	DevBuf<uint32_t> d_atlas;
+	uint32_t n_light_tab = 0, n_atlas = 0;
+	bool have_lights = false, have_atlas = false, reserved = false, ran = false;
+	DevBuf<int32_t> d_env_entity, d_refl_entity, d_list, d_light_entities, d_map;
+	DevBuf<float> d_env_radius, d_refl_radius;
+	DevBuf<ClusterEnvRec> d_env_tmpl, d_env_out;
+	DevBuf<ClusterReflRec> d_refl_tmpl, d_refl_out;
+	uint32_t n_env = 0, n_refl = 0;
+	uint32_t max_lights = 0, map_capacity = 0;
+	DevBuf<float4> d_lights;
+	DevBuf<uint4> d_clusters;
+	DevBuf<uint2> d_ranges, d_probe_ranges;
+	DevBuf<uint32_t> d_totals, d_offsets, d_state;
+	uint32_t size[3] = {0, 0, 0}; // the grid of the last run
+	uint32_t list_n = 0;          // lmx_clusters_run_list: the source of the copy into CLUSTERS_LIST_N
+};
+
 // animation sampling (lmx_capi_anim.hip): Animation resources flattened into concatenated tables, one Animable per skin instance
 struct AnimState {
 	std::vector<AnimDevice> anims;
@@ -542,6 +564,7 @@ struct LmxContext {
 	lmx::KeysState keys;
 	lmx::DrawState draw;
 	lmx::PosesState poses;
+	lmx::ClustersState clusters;
 	lmx::AnimState anim;
 };
 

@@ -416,6 +416,50 @@ struct PosesDevice {
 hipError_t launch_pose_slices(hipStream_t s, const PosesDevice& d);     // sizes, offsets, slice tables, cursor and counters
 hipError_t launch_pose_dual_quats(hipStream_t s, const PosesDevice& d); // (behind launch_pose_slices) the slices' contents
 
+// ---- fillClusters (cluster_kernels.hip): light / probe records, per-cluster counts, offsets, the map ----
+// State words = LmxClustersCounts.
+enum { CLUSTERS_LIGHTS = 0, CLUSTERS_ENV = 1, CLUSTERS_REFL = 2, CLUSTERS_MAP = 3, CLUSTERS_OVERFLOW = 4, CLUSTERS_LIST_N = 5 /* the length of a caller-given list */,
+	CLUSTERS_STATE_WORDS = 8 };
+constexpr uint32_t CLUSTER_BLOCK = 256;        // threads per block of the record, count and fill steps; a light tile of the gather = one block's threads
+constexpr uint32_t CLUSTER_REC_GRID = 256;     // blocks of the record step that stride over the list
+constexpr uint32_t CLUSTER_PROBE_BLOCKS = 8;   // ... and the blocks behind them that take the probes (8 x 256 = one thread per probe of both kinds)
+constexpr uint32_t CLUSTER_GRID = 1024;        // blocks of the count and fill steps: each wave owns a cluster, the blocks stride over the grid
+constexpr uint32_t CLUSTER_SCAN_BLOCK = 1024;  // threads of the one block that sums the clusters' sizes
+constexpr uint32_t CLUSTER_MAX_CLUSTERS = 64 * 64 * 16;
+constexpr uint32_t CLUSTER_N_PLANES = 65 + 65 + 17; // x planes at 0, y planes at 65, z planes at 130
+struct ClusterPlanesArg { float4 planes[CLUSTER_N_PLANES]; };
+struct ClusterEnvRec { float4 v[13]; };  // ClusterEnvProbe, 208 B: {pos, pad0} {rot} {inner_range, pad1} {outer_range, pad2} sh_coefs[9]
+struct ClusterReflRec { float4 v[3]; };  // ClusterReflProbe, 48 B: {pos, layer} {rot} {half_extents, pad1}
+struct ClustersDevice {
+	const int32_t* list;           // light entities, in list order
+	const uint32_t* list_count;    // on the device: the cull result's LOCAL_LIGHT total, or CLUSTERS_LIST_N
+	uint32_t list_cap;             // entries the list and `ranges` hold (<= 2^30)
+	// World::getTransforms() as the draw pass reads it (lmx_entity_tr.h)
+	const LmxTransform* tr; uint32_t n_tr;
+	const double *wpx, *wpy, *wpz; const float4* wrot; const float *wsx, *wsy, *wsz; const int32_t* slot_of_entity; uint32_t n_world;
+	const LmxPointLight* light_tab; uint32_t n_light_tab;
+	const uint32_t* atlas; uint32_t n_atlas;          // nullptr: 0xffffffff for every entity
+	// the enabled probes in output order: entity, radius (length of outer_range / half_extents) and the record with pos / rot left open
+	const int32_t* env_entity; const float* env_radius; const ClusterEnvRec* env_tmpl; uint32_t n_env;
+	const int32_t* refl_entity; const float* refl_radius; const ClusterReflRec* refl_tmpl; uint32_t n_refl;
+	double cam[3];
+	uint32_t size_x, size_y, size_z, n_clusters;
+	uint32_t max_lights, map_capacity;
+	// scratch: per listed light / per probe (env first) the cluster range {(x.lo + 1) | (x.hi + 1) << 8 | (y.lo + 1) << 16 | (y.hi + 1) << 24, the
+	// same of z}: zero = in no cluster; the clusters' sizes and their exclusive sum
+	uint2* ranges; uint2* probe_ranges;
+	uint32_t *totals, *offsets;
+	// outputs
+	float4* lights;                // [max_lights] ClusterLight, 4 x float4
+	int32_t* light_entities;       // [max_lights]
+	uint4* clusters;               // [n_clusters] {offset, lights_count, env_probes_count, refl_probes_count}
+	int32_t* map;                  // [map_capacity]
+	ClusterEnvRec* env_out; ClusterReflRec* refl_out;
+	uint32_t* state;               // CLUSTERS_*
+};
+hipError_t launch_cluster_records(hipStream_t s, const ClustersDevice& d, const ClusterPlanesArg& p); // light records + ranges, probe records + ranges
+hipError_t launch_cluster_bins(hipStream_t s, const ClustersDevice& d);                                // (behind it) counts, offsets + counters, the map
+
 // Pose::computeAbsolute + computeSkinMatrices (+ optional dual-quaternion palette), one wave per PoseGroup
 hipError_t launch_pose_palette(hipStream_t s, const SkinInstance* inst, const PoseGroup* groups, const uint32_t n_groups[3] /* by capacity 4, 2, 1 */,
 	const float* rel_pos, const float4* rel_rot, float* pose_pos, float4* pose_rot, const uint32_t* level_items, const uint16_t* level_off,
