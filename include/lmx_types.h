@@ -275,6 +275,24 @@ typedef struct LmxBlendSample {
 #define LMX_TIME_ONE_SECOND (1u << 15)       /* Time::ONE_SECOND, animation/animation.h:41 */
 #define LMX_ANIM_NONE 0xffffffffu
 
+/* One ray of lmx_rays_cast: Ray {origin, dir} (core/geometry.h) with what castRay(ray, ignored) carries besides. sizeof == 48. */
+typedef struct LmxRay {
+	double origin[3];
+	float dir[3];                            /* normalised (getRaySphereIntersection asserts it) */
+	float t_max;                             /* a hit counts when its t < t_max: +inf, or the t of a hit the caller already holds */
+	int32_t ignore;                          /* entity whose hits are left out, -1: none */
+	uint32_t _pad;
+} LmxRay;
+/* The nearest model-instance hit of a ray. A ray without one is all zero. sizeof == 24. */
+typedef struct LmxRayHit {
+	uint32_t is_hit;
+	int32_t entity;
+	uint32_t mesh;                           /* index into the model's mesh list (RayCastModelHit::mesh = &model->getMesh(mesh)) */
+	uint32_t triangle;                       /* index within that mesh */
+	float t;                                 /* world space: length(ray.origin - hit position) */
+	float t_model;                           /* what Model::castRay returned, along the model-space ray */
+} LmxRayHit;
+
 #ifdef __cplusplus
 }
 #endif

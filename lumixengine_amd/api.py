@@ -106,6 +106,22 @@ CLUSTER_ENV_PROBE = np.dtype([("pos", "<f4", 3), ("pad0", "<f4"), ("rot", "<f4",
 CLUSTER_REFL_PROBE = np.dtype([("pos", "<f4", 3), ("layer", "<u4"), ("rot", "<f4", 4), ("half_extents", "<f4", 3), ("pad1", "<f4")])  # 48 B
 CLUSTERS_GUARD_BYTES = 256  # behind the light records, their entities and the map (lmx_clusters_read_*)
 CLUSTER_MAX_PROBES = 1024
+RAY = np.dtype([("origin", "<f8", 3), ("dir", "<f4", 3), ("t_max", "<f4"), ("ignore", "<i4"), ("_pad", "<u4")])  # LmxRay
+RAY_HIT = np.dtype([("is_hit", "<u4"), ("entity", "<i4"), ("mesh", "<u4"), ("triangle", "<u4"), ("t", "<f4"), ("t_model", "<f4")])  # LmxRayHit
+RAY_MODEL = np.dtype([("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3), ("origin_radius", "<f4"), ("ready", "<u4"), ("first_mesh", "<u4"), ("mesh_count", "<u4"),
+                      ("lod0_from", "<u4")])  # LmxRayModel
+RAYS_COUNTS = np.dtype([("rays", "<u4"), ("candidates", "<u4"), ("overflow", "<u4")])  # LmxRaysCounts
+RAY_CANDIDATE = np.dtype([("ray", "<u4"), ("entity", "<u4"), ("o", "<f4", 3), ("d", "<f4", 3), ("model", "<u4"), ("palette_at", "<u4"), ("n_bones", "<u4"), ("pad", "<u4")])  # 48 B
+RAYS_GUARD_BYTES = 288  # behind the candidate list (lmx_rays_read_candidates)
+RAY_INSTANCE_ENABLED, RAY_INSTANCE_VALID = 1 << 1, 1 << 2  # ModelInstance::Flags
+# launch geometry of ray_kernels.hip (lmx_kernels.h; tests/test_ray_constants.py holds the two together)
+RAY_BLOCK = 256
+RAY_BROAD_RAYS = 64
+RAY_BROAD_GRID = 2048
+RAY_RUN = 4
+RAY_NARROW_SPLIT = 4
+RAY_NARROW_GRID = 4096
+RAY_MAX_BONES = 256
 # the launch geometry of cluster_kernels.hip (lmx_kernels.h; tests/test_cluster_constants.py holds the two together): threads per block = the
 # light tile of the gather, blocks of the record step that stride over the list, blocks of the count / fill steps
 CLUSTER_BLOCK, CLUSTER_REC_GRID, CLUSTER_GRID = 256, 256, 1024
@@ -272,6 +288,17 @@ SYMBOLS = {
     "lmx_clusters_read_map": (_ci, [_vp, _vp, _u32]),
     "lmx_clusters_read_probes": (_ci, [_vp, _vp, _u32, _vp, _u32]),
     "lmx_clusters_device_outputs": (_ci, [_vp, _vp]),
+    "lmx_rays_add_mesh": (_ci, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, C.POINTER(_u32)]),
+    "lmx_rays_clear_meshes": (_ci, [_vp]),
+    "lmx_rays_set_models": (_ci, [_vp, _u32, _vp]),
+    "lmx_rays_set_instances": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_rays_reserve": (_ci, [_vp, _u32, _u32]),
+    "lmx_rays_cast": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_cast_device": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_counts": (_ci, [_vp, _vp]),
+    "lmx_rays_read_hits": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_read_candidates": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_device_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "lmx_viewport_frustum": (_ci, [_vp, _vp]),
     "lmx_frustum_perspective": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "lmx_frustum_ortho": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
@@ -1302,6 +1329,87 @@ class ClusterFiller:
         out = np.zeros(1, np.dtype([(k, "<u8") for k in ("lights", "light_entities", "clusters", "map", "env_probes", "refl_probes", "counts")] + [("size", "<u4", 3), ("_pad", "<u4")]))
         self.ctx.check(self.lib.lmx_clusters_device_outputs(self.ctx.h, _ptr(out)))
         return {k: (tuple(int(x) for x in out[k][0]) if k == "size" else int(out[k][0])) for k in out.dtype.names if k != "_pad"}
+
+
+def rays(origin, direction, t_max=np.inf, ignore=-1) -> np.ndarray:
+    """LmxRay records from (n, 3) origins and NORMALISED directions; t_max / ignore broadcast."""
+    o = np.asarray(origin, np.float64).reshape(-1, 3)
+    r = np.zeros(len(o), RAY)
+    r["origin"] = o
+    r["dir"] = np.asarray(direction, np.float32).reshape(-1, 3)
+    r["t_max"] = t_max
+    r["ignore"] = ignore
+    return r
+
+
+class RayCaster:
+    """RenderModuleImpl::castRay's model-instance loop with Model::castRay for batches of rays (lmx_rays_*). Transforms come from
+    DrawCommands.setTransforms / bindWorld, poses from PoseProcessor.setInstances and the last Skinning.run."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.max_rays = self.max_candidates = 0
+
+    def clearMeshes(self):
+        self.ctx.check(self.lib.lmx_rays_clear_meshes(self.ctx.h))
+
+    def addMesh(self, positions, indices, skin=None) -> int:
+        """indices: a uint16 or uint32 array (its dtype is the index width)"""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        i = np.ascontiguousarray(indices)
+        assert i.dtype in (np.uint16, np.uint32), i.dtype
+        i = i.reshape(-1)
+        sk = None if skin is None else np.ascontiguousarray(skin, SKIN)
+        assert sk is None or len(sk) == len(p)
+        out = C.c_uint32(0)
+        self.ctx.check(self.lib.lmx_rays_add_mesh(self.ctx.h, len(p), _ptr(p) if len(p) else None, _ptr(sk), _ptr(i) if len(i) else None, i.dtype.itemsize, len(i), C.byref(out)))
+        return out.value
+
+    def setModels(self, models):
+        m = np.ascontiguousarray(models, RAY_MODEL)
+        self.ctx.check(self.lib.lmx_rays_set_models(self.ctx.h, len(m), _ptr(m) if len(m) else None))
+
+    def setInstances(self, model, flags):
+        m = np.ascontiguousarray(model, np.int32)
+        f = np.ascontiguousarray(flags, np.uint8)
+        assert len(m) == len(f)
+        self.ctx.check(self.lib.lmx_rays_set_instances(self.ctx.h, len(m), _ptr(m) if len(m) else None, _ptr(f) if len(m) else None))
+
+    def reserve(self, max_rays: int, max_candidates: int):
+        self.ctx.check(self.lib.lmx_rays_reserve(self.ctx.h, int(max_rays), int(max_candidates)))
+        self.max_rays, self.max_candidates = int(max_rays), int(max_candidates)
+
+    def cast(self, rays_):
+        r = np.ascontiguousarray(rays_, RAY)
+        self.ctx.check(self.lib.lmx_rays_cast(self.ctx.h, _ptr(r) if len(r) else None, len(r)))
+
+    def castDevice(self, d_rays: int, n: int):
+        self.ctx.check(self.lib.lmx_rays_cast_device(self.ctx.h, C.c_void_p(d_rays), int(n)))
+
+    def counts(self) -> dict:
+        c = np.zeros(1, RAYS_COUNTS)
+        self.ctx.check(self.lib.lmx_rays_counts(self.ctx.h, _ptr(c)))
+        return {k: int(c[k][0]) for k in RAYS_COUNTS.names}
+
+    def readHits(self) -> np.ndarray:
+        n = self.counts()["rays"]
+        out = np.zeros(max(n, 1), RAY_HIT)
+        self.ctx.check(self.lib.lmx_rays_read_hits(self.ctx.h, _ptr(out), len(out)))
+        return out[:n]
+
+    def readCandidates(self, n: Optional[int] = None) -> np.ndarray:
+        """The candidate buffer from its start: the first n records (default: all of it, with the guard's six)"""
+        n = self.max_candidates + RAYS_GUARD_BYTES // RAY_CANDIDATE.itemsize if n is None else int(n)
+        out = np.zeros(max(n, 1), RAY_CANDIDATE)
+        self.ctx.check(self.lib.lmx_rays_read_candidates(self.ctx.h, _ptr(out), n))
+        return out[:n]
+
+    def deviceOutputs(self):
+        """(d_hits, d_counts) device addresses"""
+        h, c = C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.lib.lmx_rays_device_outputs(self.ctx.h, C.byref(h), C.byref(c)))
+        return h.value, c.value
 
 
 SKIN_FUSED, SKIN_EXACT, SKIN_DQS = 0, 1, 2

@@ -239,6 +239,7 @@ int lmx_skin_set_instances(LmxContext* ctx, uint32_t n, const uint32_t* model, c
 	sk.max_verts = max_verts;
 	sk.poses_uploaded = false;
 	sk.pose_is_absolute = false;
+	sk.palette_valid = false;
 	sk.borrowed_pos = nullptr;
 	sk.borrowed_rot = nullptr;
 	LMX_HIP(ctx, sk.d_inst.reserve(std::max<size_t>(n, 1)));
@@ -412,6 +413,7 @@ int lmx_skin_run(LmxContext* ctx) {
 	// a borrowed source provides them every frame
 	sk.poses_uploaded = sk.borrowed_pos != nullptr || !sk.pose_writeback;
 	sk.pose_is_absolute = sk.pose_writeback;
+	sk.palette_valid = true;
 	return LMX_OK;
 }
 

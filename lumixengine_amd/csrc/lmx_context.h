@@ -387,6 +387,7 @@ struct SkinState {
 	bool want_dual_quats = false;
 	bool pose_writeback = true;    // store the absolute pose (Pose::is_absolute) next to the palette
 	bool pose_is_absolute = false; // d_pose_* hold the absolute pose of the last run
+	bool palette_valid = false;    // d_palette holds the palettes of a run over the current instance table (the ray casts read them)
 	DevBuf<float4> d_palette_expanded;
 	DevBuf<float> d_blend_pos;     // staging of lmx_skin_blend_poses (host variant)
 	DevBuf<float4> d_blend_rot;
@@ -512,6 +513,31 @@ struct ClustersState {
 	uint32_t list_n = 0;          // lmx_clusters_run_list: the source of the copy into CLUSTERS_LIST_N
 };
 
+// castRay (lmx_capi_rays.hip): the geometry tables (LOD-0 meshes back to back, the models), the instance table, buffers of the last cast
+constexpr size_t RAYS_GUARD_BYTES = 288; // six candidate records behind the candidate list: filled at the reserve, never written by a kernel
+struct RaysState {
+	std::vector<RayMeshRec> meshes;
+	std::vector<float> positions;
+	std::vector<LmxSkin> skins;
+	std::vector<uint8_t> indices;
+	bool meshes_dirty = false;
+	DevBuf<RayMeshRec> d_meshes;
+	DevBuf<float> d_positions;
+	DevBuf<LmxSkin> d_skins;
+	DevBuf<uint8_t> d_indices, d_inst_flags;
+	DevBuf<RayModelRec> d_models;
+	DevBuf<int32_t> d_inst_model;
+	uint32_t n_models = 0, n_inst = 0;
+	bool have_models = false, have_instances = false, reserved = false, ran = false;
+	uint32_t max_rays = 0, max_cand = 0, n_rays = 0;
+	DevBuf<LmxRay> d_rays;
+	DevBuf<RayCandidate> d_cand;
+	DevBuf<unsigned long long> d_cand_best, d_ray_best;
+	DevBuf<float> d_cand_t;
+	DevBuf<LmxRayHit> d_hits;
+	DevBuf<uint32_t> d_state;
+};
+
 // animation sampling (lmx_capi_anim.hip): Animation resources flattened into concatenated tables, one Animable per skin instance
 struct AnimState {
 	std::vector<AnimDevice> anims;
@@ -565,6 +591,7 @@ struct LmxContext {
 	lmx::DrawState draw;
 	lmx::PosesState poses;
 	lmx::ClustersState clusters;
+	lmx::RaysState rays;
 	lmx::AnimState anim;
 };
 

@@ -460,6 +460,54 @@ struct ClustersDevice {
 hipError_t launch_cluster_records(hipStream_t s, const ClustersDevice& d, const ClusterPlanesArg& p); // light records + ranges, probe records + ranges
 hipError_t launch_cluster_bins(hipStream_t s, const ClustersDevice& d);                                // (behind it) counts, offsets + counters, the map
 
+// ---- castRay (ray_kernels.hip): rays x model instances -> candidates -> nearest triangle per candidate -> nearest entity per ray ----
+// State words. The first three are LmxRaysCounts.
+// The launch constants below are GUESSES: nothing has been measured yet; tools/ray_time.py is the tool to retune them with.
+enum { RAYS_RAYS = 0, RAYS_CANDIDATES = 1, RAYS_OVERFLOW = 2, RAYS_COUNTER = 4 /* two words: the 64-bit append cursor of the broad phase (rays x entities can pass 2^32); RAYS_CANDIDATES is its value saturated at 2^32 - 1 */,
+	RAYS_STATE_WORDS = 8 };
+constexpr uint32_t RAY_BLOCK = 256;          // threads per block of every step
+constexpr uint32_t RAY_BROAD_RAYS = 64;      // rays a block of the broad phase stages in LDS per tile; the tile's other side is one entity per thread
+constexpr uint32_t RAY_BROAD_GRID = 2048;    // blocks of the broad phase: they stride over the (entity tile, ray tile) pairs
+constexpr uint32_t RAY_RUN = 4;              // consecutive triangles per work item of the narrow phase
+constexpr uint32_t RAY_NARROW_SPLIT = 4;     // blocks that share a candidate: block j of them takes the chunks j, j + 4, ... of RAY_BLOCK * RAY_RUN triangles
+constexpr uint32_t RAY_NARROW_GRID = 4096;   // blocks of the narrow phase: RAY_NARROW_GRID / RAY_NARROW_SPLIT candidates at a time
+constexpr uint32_t RAY_RESOLVE_GRID = 1024;  // blocks of the resolve and write-out steps: they stride over the candidates and the rays
+constexpr uint32_t RAY_MAX_BONES = 256;      // Model::castRay's Matrix matrices[256]: a larger pose is cast unskinned
+constexpr uint32_t RAY_NO_PALETTE = 0xffffffffu;
+struct RayModelRec { float aabb_min[3], aabb_max[3]; float radius; uint32_t ready, first_mesh, n_meshes, n_tris /* of LOD 0 */, last_skinned /* the last LOD-0 mesh has a skin */, mesh_base /* index of the first LOD-0 mesh in the model's own mesh list */, pad; };
+struct RayMeshRec { uint32_t first_tri /* ordinal of its first triangle in the model's LOD 0 */, n_tris, index_at /* bytes into `indices`, 4-byte aligned */, index_bytes /* 2 or 4 */, vert_at, n_verts, skin_at /* into `skins`, or 0xffffffff */, pad; };
+// A pair that passed the broad phase: the model-space ray of the entity, its model and the first bone of its palette (RAY_NO_PALETTE: cast unskinned)
+struct RayCandidate { uint32_t ray, entity; float o[3], d[3]; uint32_t model, palette_at, n_bones, pad; };
+static_assert(sizeof(RayCandidate) == 48, "three 16-byte stores");
+struct RaysDevice {
+	const LmxRay* rays; uint32_t n_rays;
+	// the model instances by entity: model (-1: none) and ModelInstance::flags
+	const int32_t* inst_model; const uint8_t* inst_flags; uint32_t n_inst;
+	// World::getTransforms() as the draw pass reads it (lmx_entity_tr.h)
+	const LmxTransform* tr; uint32_t n_tr;
+	const double *wpx, *wpy, *wpz; const float4* wrot; const float *wsx, *wsy, *wsz; const int32_t* slot_of_entity; uint32_t n_world;
+	const RayModelRec* models; uint32_t n_models;
+	const RayMeshRec* meshes;
+	const float* positions;        // xyz per vertex, the meshes back to back
+	const LmxSkin* skins;
+	const uint8_t* indices;
+	// pose: the skin instance of an entity (lmx_poses_set_instances), the instances and the palette lmx_skin_run left (nullptr: nobody is skinned)
+	const int32_t* skin_of_entity; uint32_t n_skin_entities;
+	const SkinInstance* skin_inst; uint32_t n_skin_inst;
+	const float4* palette;         // 3 x float4 per bone (skin_kernels.hip "Palette layout")
+	// scratch
+	RayCandidate* cand; uint32_t max_cand;
+	unsigned long long* cand_best; // [max_cand] (t bits << 32) | triangle ordinal, all ones: no hit
+	float* cand_t;                 // [max_cand] new_t of a candidate with a hit
+	unsigned long long* ray_best;  // [max_rays] (new_t bits << 32) | entity, all ones: no hit
+	// outputs
+	LmxRayHit* hits;
+	uint32_t* state;               // RAYS_*
+};
+hipError_t launch_rays_broad(hipStream_t s, const RaysDevice& d);   // steps 1-6: the candidate list and its counters
+hipError_t launch_rays_narrow(hipStream_t s, const RaysDevice& d);  // (behind it) Model::castRay per candidate
+hipError_t launch_rays_resolve(hipStream_t s, const RaysDevice& d); // (behind it) world-space t per candidate, the minimum per ray, the hit records
+
 // Pose::computeAbsolute + computeSkinMatrices (+ optional dual-quaternion palette), one wave per PoseGroup
 hipError_t launch_pose_palette(hipStream_t s, const SkinInstance* inst, const PoseGroup* groups, const uint32_t n_groups[3] /* by capacity 4, 2, 1 */,
 	const float* rel_pos, const float4* rel_rot, float* pose_pos, float4* pose_rot, const uint32_t* level_items, const uint16_t* level_off,

@@ -1,0 +1,115 @@
+// gpu_ray_caster.h — the castRay stand-in (C++ host side of include/lumix_mi355.h "ray casts").
+//
+// In the reference RenderModuleImpl::castRay (src/renderer/render_module.cpp:2715-2780) walks every model instance on one thread and every
+// LOD-0 triangle of the instances its gates let through. GpuRayCaster answers a batch of rays where the transforms, palettes and meshes
+// already lie: castRays() uploads the rays, enqueues the cast and reads one record per ray back. What the device does not hold - instanced
+// models, procedural geometry, terrain, general filter delegates - stays with the caller: it casts those first, passes the best hit it
+// holds as `held` (its t becomes the ray's t_max, so farther model instances are pruned as the reference's walk prunes them), and gets
+// the nearer of the two back, compared as :2746 and :2761-2775 compare them. Only the filter of castRay(ray, ignored) is supported.
+//
+// The geometry tables go up through the C ABI when models load (lmx_rays_add_mesh / lmx_rays_set_models / lmx_rays_set_instances: an
+// engine has the vertex and index arrays at hand in Model::onBeforeReady); transforms come from where the draw pass takes them.
+//
+// `Module` is RenderModule inside the engine (-DLMX_WITH_LUMIX_HEADERS); a standalone build passes any type with getModelInstances()
+// (tests/cpp/lumix_compat.h + lumix_compat_rays.h).
+#pragma once
+
+#include <cmath>
+#include <vector>
+
+#include "lumix_mi355.h"
+
+#ifdef LMX_WITH_LUMIX_HEADERS
+	#include "core/geometry.h"
+	#include "core/math.h"
+	#include "renderer/model.h"
+	#include "renderer/render_module.h"
+#else
+	#include "lumix_compat.h"
+	#include "lumix_compat_rays.h"
+#endif
+
+namespace Lumix {
+
+struct GpuRayCaster {
+	// model_instance_type: the component type the hits carry (types::model_instance of the renderer)
+	GpuRayCaster(LmxContext* ctx, ComponentType model_instance_type) : m_ctx(ctx), m_type(model_instance_type) {}
+
+	bool reserve(u32 max_rays, u32 max_candidates) { return lmx_rays_reserve(m_ctx, max_rays, max_candidates) == LMX_OK; }
+
+	// RenderModule::castRay(ray, ignored) over the model instances. held: the nearest hit of what the device does not cast, or nullptr.
+	template <typename Module> RayCastModelHit castRay(Module& module, const Ray& ray, EntityPtr ignored, const RayCastModelHit* held = nullptr) {
+		RayCastModelHit hit;
+		castRays(module, Span<const Ray>(&ray, 1), Span<RayCastModelHit>(&hit, 1), ignored, held);
+		return hit;
+	}
+
+	// One hit per ray: origin, dir, entity, mesh, component_type and t as the reference fills them; is_hit = false where nothing is met.
+	// held (optional, one per ray): see above. False when the cast failed or the candidate list overflowed (counts() names the size needed).
+	template <typename Module> bool castRays(Module& module, Span<const Ray> rays, Span<RayCastModelHit> hits, EntityPtr ignored, const RayCastModelHit* held = nullptr) {
+		const u32 n = rays.length();
+		if (hits.length() < n) return false;
+		m_rays.resize(n);
+		m_hits.resize(n);
+		for (u32 i = 0; i < n; ++i) {
+			LmxRay& r = m_rays[i];
+			r.origin[0] = rays[i].origin.x; r.origin[1] = rays[i].origin.y; r.origin[2] = rays[i].origin.z;
+			r.dir[0] = rays[i].dir.x; r.dir[1] = rays[i].dir.y; r.dir[2] = rays[i].dir.z;
+			r.t_max = held && held[i].is_hit ? held[i].t : INFINITY;
+			r.ignore = ignored.isValid() ? ignored.index : -1;
+			r._pad = 0;
+		}
+		if (lmx_rays_cast(m_ctx, m_rays.data(), n) != LMX_OK) return false;
+		LmxRaysCounts c;
+		if (lmx_rays_counts(m_ctx, &c) != LMX_OK || c.overflow) return false;
+		if (lmx_rays_read_hits(m_ctx, m_hits.data(), n) != LMX_OK) return false;
+		auto instances = module.getModelInstances();
+		for (u32 i = 0; i < n; ++i) {
+			RayCastModelHit& out = hits[i];
+			const LmxRayHit& h = m_hits[i];
+			// `!hit.is_hit || new_t < hit.t` (:2746) was applied on the device through t_max: a device hit is the nearer one
+			if (h.is_hit) {
+				out.is_hit = true;
+				out.t = h.t;
+				out.entity = EntityPtr{h.entity};
+				out.component_type = m_type;
+				out.subindex = 0;
+				const auto* model = (u32)h.entity < instances.length() ? instances[h.entity].model : nullptr;
+				out.mesh = model ? const_cast<Mesh*>(&model->getMesh(h.mesh)) : nullptr;
+			} else if (held && held[i].is_hit) {
+				out = held[i];
+			} else {
+				out.is_hit = false;
+				out.t = 0;
+				out.mesh = nullptr;
+				out.entity = EntityPtr{-1};
+				out.subindex = 0;
+			}
+			out.origin = rays[i].origin; // :2777-2778
+			out.dir = rays[i].dir;
+		}
+		return true;
+	}
+
+	// The merge of :2761-2775 for a hit found behind the device cast (procedural geometry, a terrain): it replaces `hit` when it is nearer.
+	static void merge(RayCastModelHit& hit, const RayCastModelHit& other) {
+		if (other.is_hit && (!hit.is_hit || other.t < hit.t)) {
+			const DVec3 origin = hit.origin;
+			const Vec3 dir = hit.dir;
+			hit = other;
+			hit.origin = origin;
+			hit.dir = dir;
+		}
+	}
+
+	bool counts(LmxRaysCounts& out) { return lmx_rays_counts(m_ctx, &out) == LMX_OK; }
+	const char* lastError() const { return lmx_last_error(m_ctx); }
+
+private:
+	LmxContext* m_ctx;
+	ComponentType m_type;
+	std::vector<LmxRay> m_rays;
+	std::vector<LmxRayHit> m_hits;
+};
+
+} // namespace Lumix
