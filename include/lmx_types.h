@@ -292,6 +292,17 @@ typedef struct LmxRayHit {
 	float t;                                 /* world space: length(ray.origin - hit position) */
 	float t_model;                           /* what Model::castRay returned, along the model-space ray */
 } LmxRayHit;
+/* The nearest instanced-model hit of a ray (RenderModuleImpl::castRayInstancedModels). A ray without one is all zero. sizeof == 32. */
+typedef struct LmxRayImHit {
+	uint32_t is_hit;
+	int32_t entity;                          /* the InstancedModel's entity (lmx_rays_set_instanced_models) */
+	uint32_t model;                          /* its lmx_im model id */
+	uint32_t subindex;                       /* RayCastModelHit::subindex: the instance's index in the stored (grid) order */
+	uint32_t mesh;                           /* index into the model's mesh list, as LmxRayHit::mesh */
+	uint32_t triangle;                       /* index within that mesh */
+	float t;                                 /* t_model * the instance's scale: what the reference returns as hit.t */
+	float t_model;                           /* what Model::castRay returned, along the instance-space ray (its direction is not normalised) */
+} LmxRayImHit;
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,9 @@ RAY = np.dtype([("origin", "<f8", 3), ("dir", "<f4", 3), ("t_max", "<f4"), ("ign
 RAY_HIT = np.dtype([("is_hit", "<u4"), ("entity", "<i4"), ("mesh", "<u4"), ("triangle", "<u4"), ("t", "<f4"), ("t_model", "<f4")])  # LmxRayHit
 RAY_MODEL = np.dtype([("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3), ("origin_radius", "<f4"), ("ready", "<u4"), ("first_mesh", "<u4"), ("mesh_count", "<u4"),
                       ("lod0_from", "<u4")])  # LmxRayModel
+RAY_IM_HIT = np.dtype([("is_hit", "<u4"), ("entity", "<i4"), ("model", "<u4"), ("subindex", "<u4"), ("mesh", "<u4"), ("triangle", "<u4"), ("t", "<f4"),
+                       ("t_model", "<f4")])  # LmxRayImHit
+RAYS_IM_COUNTS = np.dtype([("rays", "<u4"), ("candidates", "<u4"), ("overflow", "<u4")])  # LmxRaysImCounts
 RAYS_COUNTS = np.dtype([("rays", "<u4"), ("candidates", "<u4"), ("overflow", "<u4")])  # LmxRaysCounts
 RAY_CANDIDATE = np.dtype([("ray", "<u4"), ("entity", "<u4"), ("o", "<f4", 3), ("d", "<f4", 3), ("model", "<u4"), ("palette_at", "<u4"), ("n_bones", "<u4"), ("pad", "<u4")])  # 48 B
 RAYS_GUARD_BYTES = 288  # behind the candidate list (lmx_rays_read_candidates)
@@ -122,6 +125,9 @@ RAY_RUN = 4
 RAY_NARROW_SPLIT = 4
 RAY_NARROW_GRID = 4096
 RAY_MAX_BONES = 256
+# the instanced-model stage (k_imray_*; tests/test_ray_im_constants.py)
+RAY_IM_BROAD_GRID = 2048
+IM_TILE = 8192  # lmx_im.h: a model's slots start on a multiple of it
 # the launch geometry of cluster_kernels.hip (lmx_kernels.h; tests/test_cluster_constants.py holds the two together): threads per block = the
 # light tile of the gather, blocks of the record step that stride over the list, blocks of the count / fill steps
 CLUSTER_BLOCK, CLUSTER_REC_GRID, CLUSTER_GRID = 256, 256, 1024
@@ -299,6 +305,10 @@ SYMBOLS = {
     "lmx_rays_read_hits": (_ci, [_vp, _vp, _u32]),
     "lmx_rays_read_candidates": (_ci, [_vp, _vp, _u32]),
     "lmx_rays_device_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "lmx_rays_set_instanced_models": (_ci, [_vp, _vp, _u32, _vp, _vp]),
+    "lmx_rays_read_im_hits": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_im_counts": (_ci, [_vp, _vp]),
+    "lmx_rays_device_im_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "lmx_viewport_frustum": (_ci, [_vp, _vp]),
     "lmx_frustum_perspective": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "lmx_frustum_ortho": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
@@ -929,7 +939,8 @@ class InstancedModels:
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.lmx_im_destroy(self.h)
+            if getattr(self.ctx, "h", None):  # (lmx_im_destroy reads its context: behind Context.close() there is nothing left to call it on)
+                self.lib.lmx_im_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -1409,6 +1420,34 @@ class RayCaster:
         """(d_hits, d_counts) device addresses"""
         h, c = C.c_void_p(), C.c_void_p()
         self.ctx.check(self.lib.lmx_rays_device_outputs(self.ctx.h, C.byref(h), C.byref(c)))
+        return h.value, c.value
+
+    def setInstancedModels(self, im, ray_model=(), entity=()):
+        """Attach an InstancedModels (None: detach): castRayInstancedModels runs ahead of every cast. ray_model[m] / entity[m]: the setModels
+        model (-1: none) and the entity of the object's model m."""
+        if im is None:
+            self.ctx.check(self.lib.lmx_rays_set_instanced_models(self.ctx.h, None, 0, None, None))
+            return
+        rm = np.ascontiguousarray(ray_model, np.int32)
+        en = np.ascontiguousarray(entity, np.int32)
+        assert len(rm) == len(en)
+        self.ctx.check(self.lib.lmx_rays_set_instanced_models(self.ctx.h, im.h, len(rm), _ptr(rm) if len(rm) else None, _ptr(en) if len(rm) else None))
+
+    def imCounts(self) -> dict:
+        c = np.zeros(1, RAYS_IM_COUNTS)
+        self.ctx.check(self.lib.lmx_rays_im_counts(self.ctx.h, _ptr(c)))
+        return {k: int(c[k][0]) for k in RAYS_IM_COUNTS.names}
+
+    def readImHits(self) -> np.ndarray:
+        n = self.imCounts()["rays"]
+        out = np.zeros(max(n, 1), RAY_IM_HIT)
+        self.ctx.check(self.lib.lmx_rays_read_im_hits(self.ctx.h, _ptr(out), len(out)))
+        return out[:n]
+
+    def deviceImOutputs(self):
+        """(d_im_hits, d_im_counts) device addresses"""
+        h, c = C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.lib.lmx_rays_device_im_outputs(self.ctx.h, C.byref(h), C.byref(c)))
         return h.value, c.value
 
 

@@ -145,6 +145,25 @@ void invalidate_slots(LmxInstancedModels* im) {
 
 } // namespace
 
+namespace lmx {
+
+LmxContext* im_context(const LmxInstancedModels* im) { return im->ctx; }
+uint32_t im_model_count(const LmxInstancedModels* im) { return (uint32_t)im->models.size(); }
+
+int im_ray_tables(LmxInstancedModels* im, ImRayTables* out) {
+	LmxContext* ctx = im->ctx;
+	if (im->dirty) {
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (int rc = im_upload_tables(im)) return rc;
+	}
+	out->models = im->d_models.p; out->n_models = (uint32_t)im->models.size();
+	out->tile_model = im->d_tile_model.p; out->n_tiles = im->n_tiles;
+	out->pos_scale = im->d_pos_scale.p; out->rot = im->d_rot.p;
+	return LMX_OK;
+}
+
+} // namespace lmx
+
 extern "C" {
 
 int lmx_im_create(LmxContext* ctx, LmxInstancedModels** out) {
@@ -161,6 +180,7 @@ void lmx_im_destroy(LmxInstancedModels* im) {
 	if (!im) return;
 	(void)hipSetDevice(im->ctx->device);
 	(void)hipStreamSynchronize(im->ctx->stream);
+	if (im->ctx->rays.im == im) im->ctx->rays.im = nullptr; // (the ray casts no longer see it)
 	delete im;
 }
 

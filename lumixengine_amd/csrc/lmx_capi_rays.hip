@@ -2,6 +2,7 @@
 // model instances by entity, the launch chain of ray_kernels.hip over a batch of rays and the read-backs. lmx_rays_cast enqueues and
 // returns: the candidate count never reaches the host.
 #include "lmx_context.h"
+#include "lmx_im.h"
 
 using namespace lmx;
 
@@ -12,6 +13,54 @@ static_assert(GUARD_RECORDS * sizeof(RayCandidate) == RAYS_GUARD_BYTES, "whole r
 
 static_assert(sizeof(LmxRay) == 48 && sizeof(LmxRayHit) == 24 && sizeof(LmxRayModel) == 44, "ray records");
 static_assert(sizeof(LmxRaysCounts) == 3 * sizeof(uint32_t), "read out of the state words");
+static_assert(sizeof(LmxRayImHit) == 32 && sizeof(LmxRaysImCounts) == 3 * sizeof(uint32_t), "instanced-model records");
+
+// the instanced-model stage's buffers, once there is both an attached object and a reserve
+int rays_im_reserve(LmxContext* ctx) {
+	RaysState& rs = ctx->rays;
+	if (!rs.im || !rs.reserved) return LMX_OK;
+	const size_t n = std::max<size_t>(rs.max_rays, 1);
+	if (rs.d_im_best.cap >= n && rs.d_im_hits.cap >= n && rs.d_rays_eff.cap >= n && rs.d_im_state.p) return LMX_OK;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, rs.d_im_best.reserve(n));
+	LMX_HIP(ctx, rs.d_im_hits.reserve(n));
+	LMX_HIP(ctx, rs.d_rays_eff.reserve(n));
+	LMX_HIP(ctx, rs.d_im_state.reserve(RAYS_STATE_WORDS));
+	LMX_HIP(ctx, hipMemsetAsync(rs.d_im_state.p, 0, RAYS_STATE_WORDS * sizeof(uint32_t), ctx->stream));
+	return LMX_OK;
+}
+
+// castRayInstancedModels over the attached object: fills q, enqueues the stage. The entity stage behind it casts q.rays_eff.
+int rays_im_pass(LmxContext* ctx, const RaysDevice& d, ImRaysDevice& q) {
+	RaysState& rs = ctx->rays;
+	ImRayTables t;
+	if (int rc = im_ray_tables(rs.im, &t)) return rc;
+	if (rs.im_uploaded != t.n_models || rs.im_ray_models.size() != t.n_models) { // (models registered since the attach have no ray-table model)
+		rs.im_ray_models.resize(t.n_models, RayImModelRec{-1, -1});
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		LMX_HIP(ctx, rs.d_im_ray_models.reserve(std::max<size_t>(t.n_models, 1)));
+		LMX_HIP(ctx, upload_on_stream(rs.d_im_ray_models.p, rs.im_ray_models.data(), t.n_models, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		rs.im_uploaded = t.n_models;
+	}
+	if (int rc = rays_im_reserve(ctx)) return rc;
+	memset(&q, 0, sizeof(q));
+	q.r = d;
+	q.r.state = rs.d_im_state.p;
+	q.r.hits = nullptr;
+	q.im_models = t.models; q.n_im_models = t.n_models;
+	q.tile_model = t.tile_model; q.n_tiles = t.n_tiles;
+	q.pos_scale = t.pos_scale; q.rot = t.rot;
+	q.im_ray_models = rs.d_im_ray_models.p;
+	q.im_best = rs.d_im_best.p; q.im_hits = rs.d_im_hits.p; q.rays_eff = rs.d_rays_eff.p;
+	q.entity_state = rs.d_state.p;
+	LMX_HIP(ctx, hipMemsetAsync(rs.d_im_state.p, 0, RAYS_STATE_WORDS * sizeof(uint32_t), ctx->stream));
+	if (d.n_rays) LMX_HIP(ctx, hipMemsetAsync(rs.d_im_best.p, 0xff, (size_t)d.n_rays * sizeof(unsigned long long), ctx->stream));
+	LMX_HIP(ctx, launch_imrays_broad(ctx->stream, q));
+	LMX_HIP(ctx, launch_rays_narrow(ctx->stream, q.r));
+	LMX_HIP(ctx, launch_imrays_resolve(ctx->stream, q));
+	return LMX_OK;
+}
 
 int rays_upload_meshes(LmxContext* ctx) {
 	RaysState& rs = ctx->rays;
@@ -58,14 +107,20 @@ int rays_pass(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 	d.cand = rs.d_cand.p; d.max_cand = rs.max_cand;
 	d.cand_best = rs.d_cand_best.p; d.cand_t = rs.d_cand_t.p; d.ray_best = rs.d_ray_best.p;
 	d.hits = rs.d_hits.p; d.state = rs.d_state.p;
-	rs.ran = false;
+	rs.ran = rs.im_ran = false;
 	rs.n_rays = n;
 	LMX_HIP(ctx, hipMemsetAsync(rs.d_state.p, 0, RAYS_STATE_WORDS * sizeof(uint32_t), ctx->stream));
+	if (rs.im) { // the instanced models first; the entities see its hits as their rays' t_max. The entity stage's cursor is zero from the line above.
+		ImRaysDevice q;
+		if (int rc = rays_im_pass(ctx, d, q)) return rc;
+		d.rays = q.rays_eff;
+	}
 	if (n) LMX_HIP(ctx, hipMemsetAsync(rs.d_ray_best.p, 0xff, (size_t)n * sizeof(unsigned long long), ctx->stream));
 	LMX_HIP(ctx, launch_rays_broad(ctx->stream, d));
 	LMX_HIP(ctx, launch_rays_narrow(ctx->stream, d));
 	LMX_HIP(ctx, launch_rays_resolve(ctx->stream, d));
 	rs.ran = true;
+	rs.im_ran = rs.im != nullptr;
 	return LMX_OK;
 }
 
@@ -193,8 +248,8 @@ int lmx_rays_reserve(LmxContext* ctx, uint32_t max_rays, uint32_t max_candidates
 	rs.max_rays = max_rays;
 	rs.max_cand = max_candidates;
 	rs.reserved = true;
-	rs.ran = false;
-	return LMX_OK;
+	rs.ran = rs.im_ran = false;
+	return rays_im_reserve(ctx);
 }
 
 int lmx_rays_cast(LmxContext* ctx, const LmxRay* rays, uint32_t n) {
@@ -249,6 +304,59 @@ int lmx_rays_device_outputs(LmxContext* ctx, const LmxRayHit** d_hits, const uin
 	if (!rs.reserved) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_reserve has not been called");
 	if (d_hits) *d_hits = rs.d_hits.p;
 	if (d_counts) *d_counts = rs.d_state.p;
+	return LMX_OK;
+}
+
+int lmx_rays_set_instanced_models(LmxContext* ctx, LmxInstancedModels* im, uint32_t n_models, const int32_t* ray_model, const int32_t* entity) {
+	LMX_CHECK_CTX(ctx);
+	RaysState& rs = ctx->rays;
+	if (!im) {
+		rs.im = nullptr;
+		rs.im_ran = false;
+		return LMX_OK;
+	}
+	if (im_context(im) != ctx) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "the instanced models belong to another context");
+	if (n_models > im_model_count(im)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "%u models: the object has %u", n_models, im_model_count(im));
+	if (n_models && (!ray_model || !entity)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null model table");
+	for (uint32_t m = 0; m < n_models; ++m)
+		if (ray_model[m] >= 0 && (!rs.have_models || (uint32_t)ray_model[m] >= rs.n_models))
+			return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instanced model %u: ray model %d of %u", m, ray_model[m], rs.have_models ? rs.n_models : 0u);
+	rs.im_ray_models.resize(n_models);
+	for (uint32_t m = 0; m < n_models; ++m) rs.im_ray_models[m] = RayImModelRec{ray_model[m] < 0 ? -1 : ray_model[m], entity[m]};
+	rs.im_uploaded = ~(size_t)0;
+	rs.im = im;
+	rs.im_ran = false;
+	return rays_im_reserve(ctx);
+}
+
+int lmx_rays_im_counts(LmxContext* ctx, LmxRaysImCounts* out) {
+	LMX_CHECK_CTX(ctx);
+	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
+	RaysState& rs = ctx->rays;
+	if (!rs.ran || !rs.im_ran) return fail(ctx, LMX_ERR_NOT_BUILT, "no cast with instanced models attached has run");
+	uint32_t c[3];
+	LMX_HIP(ctx, read_back(c, rs.d_im_state.p, 3, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	out->rays = c[RAYS_RAYS]; out->candidates = c[RAYS_CANDIDATES]; out->overflow = c[RAYS_OVERFLOW];
+	return LMX_OK;
+}
+
+int lmx_rays_read_im_hits(LmxContext* ctx, LmxRayImHit* out, uint32_t cap) {
+	LMX_CHECK_CTX(ctx);
+	RaysState& rs = ctx->rays;
+	if (!rs.ran || !rs.im_ran) return fail(ctx, LMX_ERR_NOT_BUILT, "no cast with instanced models attached has run");
+	if (cap < rs.n_rays) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u hits", rs.n_rays);
+	LMX_HIP(ctx, read_back(out, (const LmxRayImHit*)rs.d_im_hits.p, rs.n_rays, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return LMX_OK;
+}
+
+int lmx_rays_device_im_outputs(LmxContext* ctx, const LmxRayImHit** d_hits, const uint32_t** d_counts) {
+	LMX_CHECK_CTX(ctx);
+	RaysState& rs = ctx->rays;
+	if (!rs.reserved || !rs.im) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_reserve / lmx_rays_set_instanced_models has not been called");
+	if (d_hits) *d_hits = rs.d_im_hits.p;
+	if (d_counts) *d_counts = rs.d_im_state.p;
 	return LMX_OK;
 }
 

@@ -536,6 +536,17 @@ struct RaysState {
 	DevBuf<float> d_cand_t;
 	DevBuf<LmxRayHit> d_hits;
 	DevBuf<uint32_t> d_state;
+	// castRayInstancedModels ahead of the entity stage: the attached object (lmx_rays_set_instanced_models; its device pointers are taken at
+	// every cast), its models' ray-table model and entity, the stage's outputs and state words
+	LmxInstancedModels* im = nullptr;
+	std::vector<RayImModelRec> im_ray_models;
+	size_t im_uploaded = ~(size_t)0; // records of im_ray_models on the device
+	bool im_ran = false;
+	DevBuf<RayImModelRec> d_im_ray_models;
+	DevBuf<unsigned long long> d_im_best;
+	DevBuf<LmxRayImHit> d_im_hits;
+	DevBuf<LmxRay> d_rays_eff;
+	DevBuf<uint32_t> d_im_state;
 };
 
 // animation sampling (lmx_capi_anim.hip): Animation resources flattened into concatenated tables, one Animable per skin instance

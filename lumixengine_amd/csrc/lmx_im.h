@@ -65,4 +65,16 @@ hipError_t launch_im_run(hipStream_t s, const ImModelDev* models, const ImGridDe
 	ImArrays a, const uint32_t* indices_count, uint64_t* masks, uint4* tile_counts, uint32_t* model_tot, uint32_t* model_tot_next, LmxImInstance* records,
 	LmxImIndirect* indirect, ImCountsDev* counts);
 
+
+// What the ray casts read of an instanced-models object (lmx_capi_rays.hip): its context, and its tables as they are now - uploaded first
+// if a set_* call changed them (that waits for the stream).
+struct ImRayTables {
+	const ImModelDev* models; uint32_t n_models;
+	const uint32_t* tile_model; uint32_t n_tiles;
+	const float4* pos_scale; const float4* rot;
+};
+LmxContext* im_context(const LmxInstancedModels* im);
+uint32_t im_model_count(const LmxInstancedModels* im);
+int im_ray_tables(LmxInstancedModels* im, ImRayTables* out);
+
 } // namespace lmx

@@ -508,6 +508,28 @@ hipError_t launch_rays_broad(hipStream_t s, const RaysDevice& d);   // steps 1-6
 hipError_t launch_rays_narrow(hipStream_t s, const RaysDevice& d);  // (behind it) Model::castRay per candidate
 hipError_t launch_rays_resolve(hipStream_t s, const RaysDevice& d); // (behind it) world-space t per candidate, the minimum per ray, the hit records
 
+// ---- castRayInstancedModels (ray_kernels.hip, k_imray_*): rays x instances of the attached instanced models, ahead of the stage above ----
+// The stage has state words of its own in the RAYS_* layout (k_ray_narrow reads its cursor there): the first three are LmxRaysImCounts.
+// Word RAYS_IM_OVERFLOW of the ENTITY stage's state carries this stage's overflow (0 or 2) into LmxRaysCounts::overflow.
+// The launch constants below are GUESSES as well: none has been compared on a GPU; tools/ray_im_time.py is the tool.
+enum { RAYS_IM_OVERFLOW = 3 };
+constexpr uint32_t RAY_IM_BROAD_GRID = 2048; // blocks of k_imray_broad: they stride over the (256-slot instance tile, ray tile) pairs
+struct RayImModelRec { int32_t ray_model /* of lmx_rays_set_models, -1: none */, entity; };
+struct ImRaysDevice {
+	RaysDevice r;                  // the shared tables and scratch; rays = the caller's, state = the stage's own words, hits unused
+	// the attached LmxInstancedModels (lmx_im.h): ImModelDev table, model of every IM_TILE tile, the instances in grid order
+	const struct ImModelDev* im_models; uint32_t n_im_models;
+	const uint32_t* tile_model; uint32_t n_tiles;
+	const float4* pos_scale; const float4* rot;
+	const RayImModelRec* im_ray_models; // [n_im_models]
+	unsigned long long* im_best;   // [max_rays] (ordered bits of t_model * scale << 32) | global slot, all ones: no hit
+	LmxRayImHit* im_hits;          // [max_rays]
+	LmxRay* rays_eff;              // [max_rays] the rays with the effective t_max: what the entity stage casts
+	uint32_t* entity_state;        // the entity stage's RAYS_* words (RAYS_IM_OVERFLOW)
+};
+hipError_t launch_imrays_broad(hipStream_t s, const ImRaysDevice& d);   // the candidate list of (ray, instance) pairs and its cursor
+hipError_t launch_imrays_resolve(hipStream_t s, const ImRaysDevice& d); // (behind launch_rays_narrow(d.r)) t_model * scale, the minimum per ray, hit records, effective rays, counters
+
 // Pose::computeAbsolute + computeSkinMatrices (+ optional dual-quaternion palette), one wave per PoseGroup
 hipError_t launch_pose_palette(hipStream_t s, const SkinInstance* inst, const PoseGroup* groups, const uint32_t n_groups[3] /* by capacity 4, 2, 1 */,
 	const float* rel_pos, const float4* rel_rot, float* pose_pos, float4* pose_rot, const uint32_t* level_items, const uint16_t* level_off,

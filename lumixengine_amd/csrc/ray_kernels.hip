@@ -14,8 +14,21 @@
 //   k_ray_resolve  per candidate with a hit: the winning triangle's own t (it is tested once more: the cell holds -0 as +0), the hit
 //                  position back in world space, new_t (:2743-2745), the ray's minimum.
 //   k_ray_write    the hit records: zero for a ray without a hit, the winner's for the others; the counters.
+//
+// RenderModuleImpl::castRayInstancedModels (render_module.cpp:2609-2648) runs AHEAD of them over the attached instanced models, with the same
+// candidate list, narrow phase and scratch, one stage after the other:
+//   k_imray_broad   (256-slot instance tile x ray tile) pairs: one instance per thread in registers (pos_scale, rot, radius), the rays and
+//                   `base` = Vec3(ray.origin - tr.pos) of the tile's model staged in LDS; the `ignore` filter, rel_pos (:2628), the sphere
+//                   (:2631), the instance-space ray (:2632-2634). A survivor becomes a RayCandidate: entity = the global slot, pad = the
+//                   lmx_im model, never a palette (the pose is null).
+//   k_ray_narrow    unchanged, on that list.
+//   k_imray_resolve per candidate with a hit: the triangle's own t, t * scale (:2636), the ray's minimum over ordered float bits (a negative
+//                   scale gives negative products).
+//   k_imray_write   the LmxRayImHit records, the rays with their effective t_max (the instanced-model hit's t, else the ray's own: `cur_dist`
+//                   of :2719 and `new_t < hit.t` of :2746) for the stage above, the counters.
 #include "lmx_kernels.h"
 #include "lmx_entity_tr.h"
+#include "lmx_im.h"
 
 namespace lmx {
 
@@ -334,7 +347,177 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_ray_write(RaysDevice d) {
 		const unsigned long long n = *reinterpret_cast<const unsigned long long*>(d.state + RAYS_COUNTER);
 		d.state[RAYS_RAYS] = d.n_rays;
 		d.state[RAYS_CANDIDATES] = n < 0xffffffffull ? (uint32_t)n : 0xffffffffu;
+		d.state[RAYS_OVERFLOW] = (n > d.max_cand ? 1u : 0u) | d.state[RAYS_IM_OVERFLOW]; // (bit 1: the instanced-model stage ahead of this one overflowed; zero without one)
+	}
+}
+
+// ---- instanced models ----
+
+// (t bits << 32) | slot that orders as `<` does over every non-NaN t, negative ones included; -0 as +0
+__device__ __forceinline__ unsigned long long im_hit_key(float t, uint32_t slot) {
+	const uint32_t bits = t == 0 ? 0u : __float_as_uint(t);
+	const uint32_t ordered = (bits & 0x80000000u) ? ~bits : bits | 0x80000000u;
+	return (unsigned long long)ordered << 32 | slot;
+}
+
+__global__ __launch_bounds__(RAY_BLOCK) void k_imray_broad(ImRaysDevice q) {
+	__shared__ LmxRay s_rays[RAY_BROAD_RAYS];
+	__shared__ V3 s_base[RAY_BROAD_RAYS];
+	constexpr uint32_t SUB = IM_TILE / RAY_BLOCK; // 256-slot tiles of an IM_TILE tile
+	static_assert(SUB * RAY_BLOCK == IM_TILE, "a 256-slot tile belongs to one model");
+	const RaysDevice& d = q.r;
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t n_rt = (d.n_rays + RAY_BROAD_RAYS - 1) / RAY_BROAD_RAYS;
+	const uint32_t n_it = q.n_tiles * SUB;
+	if (n_rt == 0) return;
+	// pair p = it * n_rt + rt, stepped as in k_ray_broad
+	const uint32_t it_step = RAY_IM_BROAD_GRID / n_rt, rt_step = RAY_IM_BROAD_GRID % n_rt;
+	uint32_t cur_it = 0xffffffffu;
+	// the tile's model (block-uniform) and the thread's instance
+	bool live = false, ok = false;
+	uint32_t slot = 0, model = 0, im = 0;
+	int32_t entity = 0;
+	DV3 origin = {};
+	V3 pos = {};
+	Q4 rot = {};
+	float radius = 0, inv_scale = 0;
+	uint32_t rt = blockIdx.x % n_rt;
+	for (uint32_t it = blockIdx.x / n_rt; it < n_it; it += it_step) {
+		if (rt >= n_rt) { // (the carry of the step before)
+			rt -= n_rt;
+			if (++it >= n_it) break;
+		}
+		if (it != cur_it) {
+			cur_it = it;
+			const uint32_t tile = it / SUB;
+			im = q.tile_model[tile];
+			live = ok = false;
+			if (im < q.n_im_models) {
+				const ImModelDev& mo = q.im_models[im];
+				const RayImModelRec rm = q.im_ray_models[im];
+				const uint32_t at = (tile - mo.first_tile) * IM_TILE + (it % SUB) * RAY_BLOCK; // the tile's first instance within the model
+				live = at < mo.n && rm.ray_model >= 0 && (uint32_t)rm.ray_model < d.n_models && d.models[rm.ray_model].ready != 0; // `!im.model || !isReady()`, :2616
+				if (live) {
+					model = (uint32_t)rm.ray_model;
+					entity = rm.entity;
+					origin = DV3{mo.origin[0], mo.origin[1], mo.origin[2]};
+					ok = at + threadIdx.x < mo.n; // (the slots behind are padding up to the next model)
+					if (ok) {
+						slot = mo.first + at + threadIdx.x;
+						const float4 ps = q.pos_scale[slot], r4 = q.rot[slot];
+						pos = V3{ps.x, ps.y, ps.z};
+						radius = mo.radius * ps.w;                                                       // :2629
+						rot = Q4{r4.x, r4.y, r4.z, sqrtf(1 - (r4.x * r4.x + r4.y * r4.y + r4.z * r4.z))}; // getInstanceQuat, :2619-2626
+						inv_scale = 1 / ps.w;                                                            // Vec3::operator/(float), math.cpp:471-474
+					}
+				}
+			}
+		}
+		if (!live) { // (block-uniform: a tile of padding, or a model that is not cast)
+			rt += rt_step;
+			continue;
+		}
+		__syncthreads(); // (the previous tile's rays are no longer read)
+		const uint32_t ray0 = rt * RAY_BROAD_RAYS;
+		const uint32_t n_tile = d.n_rays - ray0 < RAY_BROAD_RAYS ? d.n_rays - ray0 : RAY_BROAD_RAYS;
+		if (threadIdx.x < n_tile) {
+			const LmxRay ray = d.rays[ray0 + threadIdx.x];
+			s_rays[threadIdx.x] = ray;
+			s_base[threadIdx.x] = to_v3(sub(DV3{ray.origin[0], ray.origin[1], ray.origin[2]}, origin)); // Vec3(ray.origin - tr.pos), :2628
+		}
+		__syncthreads();
+		for (uint32_t r = 0; r < n_tile; ++r) { // (block-uniform: every lane takes every ballot)
+			const LmxRay& ray = s_rays[r];
+			bool pass = ok && entity != ray.ignore; // the filter of :2603-2607 refuses every triangle of the model
+			V3 o = {}, dir = {};
+			if (pass) {
+				const V3 rd = V3{ray.dir[0], ray.dir[1], ray.dir[2]};
+				const V3 rel = sub(s_base[r], pos);
+				pass = ray_sphere(rel, rd, radius);
+				if (pass) {
+					dir = rotate(conjugated(rot), rd); // (not normalised)
+					o = rotate(conjugated(rot), V3{rel.x * inv_scale, rel.y * inv_scale, rel.z * inv_scale});
+				}
+			}
+			const unsigned long long mask = __ballot(pass);
+			if (mask == 0) continue; // (wave-uniform)
+			unsigned long long base = 0;
+			if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long*>(d.state + RAYS_COUNTER), (unsigned long long)__popcll(mask));
+			base = __shfl(base, 0);
+			const unsigned long long at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+			if (pass && at < d.max_cand) {
+				RayCandidate c;
+				c.ray = ray0 + r; c.entity = slot;
+				c.o[0] = o.x; c.o[1] = o.y; c.o[2] = o.z;
+				c.d[0] = dir.x; c.d[1] = dir.y; c.d[2] = dir.z;
+				c.model = model; c.palette_at = RAY_NO_PALETTE; c.n_bones = 0; c.pad = im;
+				d.cand[at] = c;
+				d.cand_best[at] = RAY_NONE;
+			}
+		}
+		rt += rt_step; // (< 2 n_rt)
+	}
+}
+
+// the winning triangle of a candidate with a hit: its mesh (relative to LOD 0's first), its index there and its own t (the cell holds -0 as +0)
+__device__ __forceinline__ float im_winner(const RaysDevice& d, const RayCandidate& cd, unsigned long long best, uint32_t* mesh, uint32_t* triangle) {
+	const RayModelRec& mo = d.models[cd.model];
+	const RayMeshRec* meshes = d.meshes + mo.first_mesh;
+	const uint32_t ord = (uint32_t)best;
+	const uint32_t m = mesh_of(meshes, mo.n_meshes, 0, ord);
+	float t = __uint_as_float((uint32_t)(best >> 32));
+	test_mesh_triangle(d, meshes[m], ord - meshes[m].first_tri, nullptr, 0, V3{cd.o[0], cd.o[1], cd.o[2]}, V3{cd.d[0], cd.d[1], cd.d[2]}, &t);
+	*mesh = mo.mesh_base + m;
+	*triangle = ord - meshes[m].first_tri;
+	return t;
+}
+
+__global__ __launch_bounds__(RAY_BLOCK) void k_imray_resolve(ImRaysDevice q) {
+	const RaysDevice& d = q.r;
+	const uint32_t n_cand = candidates(d);
+	for (uint32_t c = blockIdx.x * RAY_BLOCK + threadIdx.x; c < n_cand; c += RAY_RESOLVE_GRID * RAY_BLOCK) {
+		const unsigned long long best = d.cand_best[c];
+		if (best == RAY_NONE) continue;
+		const RayCandidate cd = d.cand[c];
+		uint32_t mesh, triangle;
+		const float t = im_winner(d, cd, best, &mesh, &triangle);
+		const float scaled = t * q.pos_scale[cd.entity].w; // new_hit.t * id.scale, :2636
+		d.cand_t[c] = scaled;
+		if (scaled < d.rays[cd.ray].t_max) atomicMin(&q.im_best[cd.ray], im_hit_key(scaled, cd.entity)); // (a NaN is below nothing)
+	}
+}
+
+__global__ __launch_bounds__(RAY_BLOCK) void k_imray_write(ImRaysDevice q) {
+	const RaysDevice& d = q.r;
+	const uint32_t n_cand = candidates(d);
+	const uint32_t gid = blockIdx.x * RAY_BLOCK + threadIdx.x;
+	for (uint32_t r = gid; r < d.n_rays; r += RAY_RESOLVE_GRID * RAY_BLOCK) {
+		if (q.im_best[r] != RAY_NONE) continue; // (a candidate below writes both)
+		LmxRayImHit h;
+		h.is_hit = 0; h.entity = 0; h.model = 0; h.subindex = 0; h.mesh = 0; h.triangle = 0; h.t = 0.0f; h.t_model = 0.0f;
+		q.im_hits[r] = h;
+		q.rays_eff[r] = d.rays[r];
+	}
+	for (uint32_t c = gid; c < n_cand; c += RAY_RESOLVE_GRID * RAY_BLOCK) {
+		const unsigned long long best = d.cand_best[c];
+		if (best == RAY_NONE) continue;
+		const RayCandidate cd = d.cand[c];
+		const float scaled = d.cand_t[c];
+		LmxRay ray = d.rays[cd.ray];
+		if (!(scaled < ray.t_max) || q.im_best[cd.ray] != im_hit_key(scaled, cd.entity)) continue; // (one candidate per (ray, slot): one winner)
+		LmxRayImHit h;
+		h.t_model = im_winner(d, cd, best, &h.mesh, &h.triangle);
+		h.is_hit = 1; h.entity = q.im_ray_models[cd.pad].entity; h.model = cd.pad; h.subindex = cd.entity - q.im_models[cd.pad].first; h.t = scaled;
+		q.im_hits[cd.ray] = h;
+		ray.t_max = scaled; // cur_dist = hit.t (:2719); `new_t < hit.t` (:2746)
+		q.rays_eff[cd.ray] = ray;
+	}
+	if (gid == 0) {
+		const unsigned long long n = *reinterpret_cast<const unsigned long long*>(d.state + RAYS_COUNTER);
+		d.state[RAYS_RAYS] = d.n_rays;
+		d.state[RAYS_CANDIDATES] = n < 0xffffffffull ? (uint32_t)n : 0xffffffffu;
 		d.state[RAYS_OVERFLOW] = n > d.max_cand ? 1u : 0u;
+		q.entity_state[RAYS_IM_OVERFLOW] = n > d.max_cand ? 2u : 0u;
 	}
 }
 
@@ -355,6 +538,19 @@ hipError_t launch_rays_resolve(hipStream_t s, const RaysDevice& d) {
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(k_ray_write, dim3(RAY_RESOLVE_GRID), dim3(RAY_BLOCK), 0, s, d);
+	return hipGetLastError();
+}
+
+hipError_t launch_imrays_broad(hipStream_t s, const ImRaysDevice& d) {
+	hipLaunchKernelGGL(k_imray_broad, dim3(RAY_IM_BROAD_GRID), dim3(RAY_BLOCK), 0, s, d);
+	return hipGetLastError();
+}
+
+hipError_t launch_imrays_resolve(hipStream_t s, const ImRaysDevice& d) {
+	hipLaunchKernelGGL(k_imray_resolve, dim3(RAY_RESOLVE_GRID), dim3(RAY_BLOCK), 0, s, d);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k_imray_write, dim3(RAY_RESOLVE_GRID), dim3(RAY_BLOCK), 0, s, d);
 	return hipGetLastError();
 }
 

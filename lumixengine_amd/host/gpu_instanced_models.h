@@ -135,6 +135,18 @@ struct GpuInstancedModels {
 	}
 #endif
 
+	// For the ray casts (gpu_ray_caster.h): the C-ABI object, the registered entities in slot order, and the origins brought up to date
+	LmxInstancedModels* handle() const { return m_im; }
+	const std::vector<int32_t>& entities() const { return m_entities; }
+	bool flushOrigins() {
+		if (!m_im || !m_origins_dirty) return m_im != nullptr;
+		lmx_ctx_lock(m_ctx);
+		const int rc = lmx_im_set_origins(m_im, (uint32_t)m_entities.size(), m_origins.data());
+		lmx_ctx_unlock(m_ctx);
+		m_origins_dirty = rc != LMX_OK;
+		return rc == LMX_OK || fail("lmx_im_set_origins");
+	}
+
 	const std::string& lastError() const { return m_error; }
 
 private:

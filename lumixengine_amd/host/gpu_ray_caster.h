@@ -2,10 +2,15 @@
 //
 // In the reference RenderModuleImpl::castRay (src/renderer/render_module.cpp:2715-2780) walks every model instance on one thread and every
 // LOD-0 triangle of the instances its gates let through. GpuRayCaster answers a batch of rays where the transforms, palettes and meshes
-// already lie: castRays() uploads the rays, enqueues the cast and reads one record per ray back. What the device does not hold - instanced
-// models, procedural geometry, terrain, general filter delegates - stays with the caller: it casts those first, passes the best hit it
+// already lie: castRays() uploads the rays, enqueues the cast and reads one record per ray back. What the device does not hold -
+// procedural geometry, terrain, general filter delegates - stays with the caller: it casts those first, passes the best hit it
 // holds as `held` (its t becomes the ray's t_max, so farther model instances are pruned as the reference's walk prunes them), and gets
 // the nearer of the two back, compared as :2746 and :2761-2775 compare them. Only the filter of castRay(ray, ignored) is supported.
+//
+// Instanced models (castRayInstancedModels, :2609-2648, the first thing castRay does) are cast on the device too once the
+// gpu_instanced_models.h adapter is attached with setInstancedModels(): the hit comes back with component_type = types::instanced_model,
+// the model's entity, subindex, mesh and t wherever no model instance is strictly nearer, and `held` shrinks to procedural geometry and
+// terrain. Without an attached adapter they stay with the caller as before.
 //
 // The geometry tables go up through the C ABI when models load (lmx_rays_add_mesh / lmx_rays_set_models / lmx_rays_set_instances: an
 // engine has the vertex and index arrays at hand in Model::onBeforeReady); transforms come from where the draw pass takes them.
@@ -18,6 +23,7 @@
 #include <vector>
 
 #include "lumix_mi355.h"
+#include "gpu_instanced_models.h"
 
 #ifdef LMX_WITH_LUMIX_HEADERS
 	#include "core/geometry.h"
@@ -34,6 +40,22 @@ namespace Lumix {
 struct GpuRayCaster {
 	// model_instance_type: the component type the hits carry (types::model_instance of the renderer)
 	GpuRayCaster(LmxContext* ctx, ComponentType model_instance_type) : m_ctx(ctx), m_type(model_instance_type) {}
+
+	// Attach the instanced models (nullptr: detach). Per slot of `im`, in its registration order: ray_model = the model's id in
+	// lmx_rays_set_models (-1: it has no Model, or is not cast), models = the engine's Model (RayCastModelHit::mesh points into it).
+	// Call again when a model is registered with `im`. instanced_model_type: types::instanced_model of the renderer.
+	bool setInstancedModels(GpuInstancedModels* im, ComponentType instanced_model_type, const i32* ray_model, Model* const* models) {
+		m_im = nullptr;
+		m_im_models.clear();
+		if (!im) return lmx_rays_set_instanced_models(m_ctx, nullptr, 0, nullptr, nullptr) == LMX_OK;
+		const std::vector<int32_t>& entities = im->entities();
+		const u32 n = (u32)entities.size();
+		if (lmx_rays_set_instanced_models(m_ctx, im->handle(), n, ray_model, entities.data()) != LMX_OK) return false;
+		m_im_models.assign(models, models + n);
+		m_im_type = instanced_model_type;
+		m_im = im;
+		return true;
+	}
 
 	bool reserve(u32 max_rays, u32 max_candidates) { return lmx_rays_reserve(m_ctx, max_rays, max_candidates) == LMX_OK; }
 
@@ -59,10 +81,13 @@ struct GpuRayCaster {
 			r.ignore = ignored.isValid() ? ignored.index : -1;
 			r._pad = 0;
 		}
+		if (m_im && !m_im->flushOrigins()) return false;
 		if (lmx_rays_cast(m_ctx, m_rays.data(), n) != LMX_OK) return false;
 		LmxRaysCounts c;
-		if (lmx_rays_counts(m_ctx, &c) != LMX_OK || c.overflow) return false;
+		if (lmx_rays_counts(m_ctx, &c) != LMX_OK || c.overflow) return false; // (bit 1: the instanced-model stage)
 		if (lmx_rays_read_hits(m_ctx, m_hits.data(), n) != LMX_OK) return false;
+		m_im_hits.resize(m_im ? n : 0);
+		if (m_im && lmx_rays_read_im_hits(m_ctx, m_im_hits.data(), n) != LMX_OK) return false;
 		auto instances = module.getModelInstances();
 		for (u32 i = 0; i < n; ++i) {
 			RayCastModelHit& out = hits[i];
@@ -76,6 +101,15 @@ struct GpuRayCaster {
 				out.subindex = 0;
 				const auto* model = (u32)h.entity < instances.length() ? instances[h.entity].model : nullptr;
 				out.mesh = model ? const_cast<Mesh*>(&model->getMesh(h.mesh)) : nullptr;
+			} else if (m_im && m_im_hits[i].is_hit) { // below t_max, so nearer than `held`; no model instance is strictly nearer (:2746)
+				const LmxRayImHit& ih = m_im_hits[i];
+				out.is_hit = true;
+				out.t = ih.t;
+				out.entity = EntityPtr{ih.entity};
+				out.component_type = m_im_type;
+				out.subindex = ih.subindex;
+				Model* model = ih.model < m_im_models.size() ? m_im_models[ih.model] : nullptr;
+				out.mesh = model ? const_cast<Mesh*>(&model->getMesh(ih.mesh)) : nullptr;
 			} else if (held && held[i].is_hit) {
 				out = held[i];
 			} else {
@@ -103,6 +137,7 @@ struct GpuRayCaster {
 	}
 
 	bool counts(LmxRaysCounts& out) { return lmx_rays_counts(m_ctx, &out) == LMX_OK; }
+	bool imCounts(LmxRaysImCounts& out) { return lmx_rays_im_counts(m_ctx, &out) == LMX_OK; }
 	const char* lastError() const { return lmx_last_error(m_ctx); }
 
 private:
@@ -110,6 +145,10 @@ private:
 	ComponentType m_type;
 	std::vector<LmxRay> m_rays;
 	std::vector<LmxRayHit> m_hits;
+	GpuInstancedModels* m_im = nullptr;
+	ComponentType m_im_type = {};
+	std::vector<Model*> m_im_models;
+	std::vector<LmxRayImHit> m_im_hits;
 };
 
 } // namespace Lumix
