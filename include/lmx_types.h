@@ -303,6 +303,61 @@ typedef struct LmxRayImHit {
 	float t;                                 /* t_model * the instance's scale: what the reference returns as hit.t */
 	float t_model;                           /* what Model::castRay returned, along the instance-space ray (its direction is not normalised) */
 } LmxRayImHit;
+/* What castRayProceduralGeometry (render_module.cpp:2650-2712) reads of one ProceduralGeometry. The arrays are read during
+ * lmx_rays_set_procedural_geometries only. sizeof == 64. */
+typedef struct LmxRayProcGeom {
+	int32_t entity;
+	uint32_t triangles;                      /* vertex_decl.primitive_type == gpu::PrimitiveType::TRIANGLES */
+	float aabb_min[3];
+	float aabb_max[3];
+	const void* vertex_data;                 /* a position is the first 12 bytes at index * stride */
+	uint32_t vertex_bytes;                   /* vertex_data.size(); 0: the geometry is kept and never cast */
+	uint32_t stride;                         /* vertex_decl.getStride(), >= 12 */
+	const void* index_data;
+	uint32_t index_bytes;                    /* 0: not indexed; 2 or 4 */
+	uint32_t index_count;                    /* getIndexCount() */
+} LmxRayProcGeom;
+/* What Terrain::castRay (terrain.cpp:474-535) reads of one Terrain. The texels are read during lmx_rays_set_terrains only. sizeof == 40. */
+#define LMX_RAY_TERRAIN_R16 0u               /* gpu::TextureFormat::R16: 2 bytes per texel */
+#define LMX_RAY_TERRAIN_RGBA8 1u             /* gpu::TextureFormat::RGBA8: 4 bytes per texel, the height is the lowest byte */
+typedef struct LmxRayTerrain {
+	int32_t entity;
+	uint32_t width, height;                  /* m_width, m_height */
+	uint32_t format;                         /* LMX_RAY_TERRAIN_* */
+	float scale[3];                          /* m_scale */
+	uint32_t ready;                          /* m_heightmap && m_heightmap->isReady(); 0: never hit */
+	const void* texels;                      /* width * height texels, row z after row z - 1 */
+} LmxRayTerrain;
+/* castRayProceduralGeometry's result for a ray. A ray without a hit is all zero. sizeof == 20. */
+typedef struct LmxRayPgHit {
+	uint32_t is_hit;
+	int32_t entity;
+	uint32_t geom;                           /* index in the table of lmx_rays_set_procedural_geometries */
+	uint32_t triangle;
+	float t;                                 /* along the geometry-space ray, whose direction is not normalised: the world parameter */
+} LmxRayPgHit;
+/* Terrain::castRay's result for a (ray, terrain) pair. A pair without a hit is all zero. sizeof == 28. */
+typedef struct LmxRayTerrainHit {
+	uint32_t is_hit;
+	int32_t entity;
+	uint32_t terrain;                        /* index in the table of lmx_rays_set_terrains */
+	int32_t hx, hz;                          /* the cell of the walk that was hit */
+	uint32_t tri;                            /* 0: (p0, p1, p2), 1: (p0, p2, p3) */
+	float t;
+} LmxRayTerrainHit;
+/* RenderModuleImpl::castRay's result for a ray (render_module.cpp:2718-2775). A ray without a hit is all zero. sizeof == 24. */
+#define LMX_RAY_HIT_MODEL_INSTANCE 1u        /* index = mesh, sub = triangle (LmxRayHit) */
+#define LMX_RAY_HIT_INSTANCED_MODEL 2u       /* index = lmx_im model, sub = subindex (LmxRayImHit) */
+#define LMX_RAY_HIT_PROCEDURAL_GEOM 3u       /* index = geometry, sub = triangle (LmxRayPgHit) */
+#define LMX_RAY_HIT_TERRAIN 4u               /* index = terrain, sub = hz * width + hx (LmxRayTerrainHit) */
+typedef struct LmxRaySceneHit {
+	uint32_t is_hit;
+	uint32_t component;                      /* LMX_RAY_HIT_* */
+	int32_t entity;
+	uint32_t index;
+	uint32_t sub;
+	float t;
+} LmxRaySceneHit;
 
 #ifdef __cplusplus
 }

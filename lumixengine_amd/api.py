@@ -114,6 +114,15 @@ RAY_IM_HIT = np.dtype([("is_hit", "<u4"), ("entity", "<i4"), ("model", "<u4"), (
                        ("t_model", "<f4")])  # LmxRayImHit
 RAYS_IM_COUNTS = np.dtype([("rays", "<u4"), ("candidates", "<u4"), ("overflow", "<u4")])  # LmxRaysImCounts
 RAYS_COUNTS = np.dtype([("rays", "<u4"), ("candidates", "<u4"), ("overflow", "<u4")])  # LmxRaysCounts
+RAY_PROC_GEOM = np.dtype([("entity", "<i4"), ("triangles", "<u4"), ("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3), ("vertex_data", "<u8"), ("vertex_bytes", "<u4"), ("stride", "<u4"),
+                          ("index_data", "<u8"), ("index_bytes", "<u4"), ("index_count", "<u4")])  # LmxRayProcGeom (the pointers as addresses)
+RAY_TERRAIN = np.dtype([("entity", "<i4"), ("width", "<u4"), ("height", "<u4"), ("format", "<u4"), ("scale", "<f4", 3), ("ready", "<u4"), ("texels", "<u8")])  # LmxRayTerrain
+RAY_PG_HIT = np.dtype([("is_hit", "<u4"), ("entity", "<i4"), ("geom", "<u4"), ("triangle", "<u4"), ("t", "<f4")])  # LmxRayPgHit
+RAY_TERRAIN_HIT = np.dtype([("is_hit", "<u4"), ("entity", "<i4"), ("terrain", "<u4"), ("hx", "<i4"), ("hz", "<i4"), ("tri", "<u4"), ("t", "<f4")])  # LmxRayTerrainHit
+RAY_SCENE_HIT = np.dtype([("is_hit", "<u4"), ("component", "<u4"), ("entity", "<i4"), ("index", "<u4"), ("sub", "<u4"), ("t", "<f4")])  # LmxRaySceneHit
+RAYS_SCENE_COUNTS = np.dtype([("rays", "<u4"), ("candidates", "<u4"), ("overflow", "<u4")])  # LmxRaysSceneCounts
+RAY_TERRAIN_R16, RAY_TERRAIN_RGBA8 = 0, 1  # LMX_RAY_TERRAIN_*
+RAY_HIT_MODEL_INSTANCE, RAY_HIT_INSTANCED_MODEL, RAY_HIT_PROCEDURAL_GEOM, RAY_HIT_TERRAIN = 1, 2, 3, 4  # LMX_RAY_HIT_*
 RAY_CANDIDATE = np.dtype([("ray", "<u4"), ("entity", "<u4"), ("o", "<f4", 3), ("d", "<f4", 3), ("model", "<u4"), ("palette_at", "<u4"), ("n_bones", "<u4"), ("pad", "<u4")])  # 48 B
 RAYS_GUARD_BYTES = 288  # behind the candidate list (lmx_rays_read_candidates)
 RAY_INSTANCE_ENABLED, RAY_INSTANCE_VALID = 1 << 1, 1 << 2  # ModelInstance::Flags
@@ -127,6 +136,12 @@ RAY_NARROW_GRID = 4096
 RAY_MAX_BONES = 256
 # the instanced-model stage (k_imray_*; tests/test_ray_im_constants.py)
 RAY_IM_BROAD_GRID = 2048
+# ray_scene_kernels.hip (tests/test_ray_scene_constants.py)
+RAY_PG_BROAD_GRID = 1024
+RAY_TERRAIN_CHUNK = 64
+RAY_TERRAIN_GRID = 2048
+RAY_MAX_TERRAINS = 1024
+RAYS_PG_OVERFLOW = 4  # bit of LmxRaysCounts::overflow
 IM_TILE = 8192  # lmx_im.h: a model's slots start on a multiple of it
 # the launch geometry of cluster_kernels.hip (lmx_kernels.h; tests/test_cluster_constants.py holds the two together): threads per block = the
 # light tile of the gather, blocks of the record step that stride over the list, blocks of the count / fill steps
@@ -309,6 +324,13 @@ SYMBOLS = {
     "lmx_rays_read_im_hits": (_ci, [_vp, _vp, _u32]),
     "lmx_rays_im_counts": (_ci, [_vp, _vp]),
     "lmx_rays_device_im_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "lmx_rays_set_procedural_geometries": (_ci, [_vp, _u32, _vp]),
+    "lmx_rays_set_terrains": (_ci, [_vp, _u32, _vp]),
+    "lmx_rays_read_pg_hits": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_read_terrain_hits": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_read_scene_hits": (_ci, [_vp, _vp, _u32]),
+    "lmx_rays_scene_counts": (_ci, [_vp, _vp]),
+    "lmx_rays_device_scene_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "lmx_viewport_frustum": (_ci, [_vp, _vp]),
     "lmx_frustum_perspective": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "lmx_frustum_ortho": (_ci, [_vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
@@ -1448,6 +1470,69 @@ class RayCaster:
         """(d_im_hits, d_im_counts) device addresses"""
         h, c = C.c_void_p(), C.c_void_p()
         self.ctx.check(self.lib.lmx_rays_device_im_outputs(self.ctx.h, C.byref(h), C.byref(c)))
+        return h.value, c.value
+
+    def setProceduralGeometries(self, geometries):
+        """castRayProceduralGeometry runs behind every cast ([] clears the table). geometries: dicts in m_procedural_geometries order with
+        entity, aabb_min, aabb_max, vertex_data (any array: its bytes; empty: never cast), stride, indices (None, or a uint16 / uint32
+        array), index_count (default: len(indices)) and triangles (default True: the primitive type is TRIANGLES)."""
+        recs = np.zeros(len(geometries), RAY_PROC_GEOM)
+        keep = []
+        for r, g in zip(recs, geometries):
+            v = np.frombuffer(np.ascontiguousarray(g["vertex_data"]).tobytes(), np.uint8)
+            idx = g.get("indices")
+            i = np.zeros(0, np.uint32) if idx is None else np.ascontiguousarray(idx).reshape(-1)
+            keep += [v, i]
+            r["entity"], r["triangles"] = g["entity"], 1 if g.get("triangles", True) else 0
+            r["aabb_min"], r["aabb_max"] = g["aabb_min"], g["aabb_max"]
+            r["vertex_data"], r["vertex_bytes"], r["stride"] = (v.ctypes.data if len(v) else 0), len(v), g["stride"]
+            r["index_data"] = i.ctypes.data if len(i) else 0
+            r["index_bytes"] = g.get("index_bytes", 0 if idx is None else i.dtype.itemsize)
+            r["index_count"] = g.get("index_count", len(i))
+        self.ctx.check(self.lib.lmx_rays_set_procedural_geometries(self.ctx.h, len(recs), _ptr(recs) if len(recs) else None))
+
+    def setTerrains(self, terrains):
+        """Terrain::castRay runs behind every cast for each terrain, in this (m_terrains) order ([] clears the table). terrains: dicts with
+        entity, scale (x, y, z), heightmap ((height, width) uint16: R16, or uint32: RGBA8) and ready (default True)."""
+        recs = np.zeros(len(terrains), RAY_TERRAIN)
+        keep = []
+        for r, t in zip(recs, terrains):
+            h = np.ascontiguousarray(t["heightmap"])
+            assert h.ndim == 2 and h.dtype in (np.uint16, np.uint32), (h.shape, h.dtype)
+            keep.append(h)
+            r["entity"], r["height"], r["width"] = t["entity"], h.shape[0], h.shape[1]
+            r["format"] = t.get("format", RAY_TERRAIN_R16 if h.dtype == np.uint16 else RAY_TERRAIN_RGBA8)
+            r["scale"], r["ready"], r["texels"] = t["scale"], 1 if t.get("ready", True) else 0, (h.ctypes.data if h.size else 0)
+        self.ctx.check(self.lib.lmx_rays_set_terrains(self.ctx.h, len(recs), _ptr(recs) if len(recs) else None))
+        self.n_terrains = len(recs)
+
+    def sceneCounts(self) -> dict:
+        c = np.zeros(1, RAYS_SCENE_COUNTS)
+        self.ctx.check(self.lib.lmx_rays_scene_counts(self.ctx.h, _ptr(c)))
+        return {k: int(c[k][0]) for k in RAYS_SCENE_COUNTS.names}
+
+    def _read_scene(self, fn, dtype, per_ray=1):
+        n = self.sceneCounts()["rays"] * per_ray
+        out = np.zeros(max(n, 1), dtype)
+        self.ctx.check(fn(self.ctx.h, _ptr(out), len(out)))
+        return out[:n]
+
+    def readPgHits(self) -> np.ndarray:
+        return self._read_scene(self.lib.lmx_rays_read_pg_hits, RAY_PG_HIT)
+
+    def readTerrainHits(self) -> np.ndarray:
+        """(rays, terrains) records"""
+        k = getattr(self, "n_terrains", 0)
+        return self._read_scene(self.lib.lmx_rays_read_terrain_hits, RAY_TERRAIN_HIT, k).reshape(-1, k) if k else np.zeros((self.sceneCounts()["rays"], 0), RAY_TERRAIN_HIT)
+
+    def readSceneHits(self) -> np.ndarray:
+        """RenderModule::castRay's result per ray"""
+        return self._read_scene(self.lib.lmx_rays_read_scene_hits, RAY_SCENE_HIT)
+
+    def deviceSceneOutputs(self):
+        """(d_scene_hits, d_scene_counts) device addresses"""
+        h, c = C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.lib.lmx_rays_device_scene_outputs(self.ctx.h, C.byref(h), C.byref(c)))
         return h.value, c.value
 
 

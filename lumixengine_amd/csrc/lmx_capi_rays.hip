@@ -107,7 +107,7 @@ int rays_pass(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 	d.cand = rs.d_cand.p; d.max_cand = rs.max_cand;
 	d.cand_best = rs.d_cand_best.p; d.cand_t = rs.d_cand_t.p; d.ray_best = rs.d_ray_best.p;
 	d.hits = rs.d_hits.p; d.state = rs.d_state.p;
-	rs.ran = rs.im_ran = false;
+	rs.ran = rs.im_ran = rs.scene_ran = false;
 	rs.n_rays = n;
 	LMX_HIP(ctx, hipMemsetAsync(rs.d_state.p, 0, RAYS_STATE_WORDS * sizeof(uint32_t), ctx->stream));
 	if (rs.im) { // the instanced models first; the entities see its hits as their rays' t_max. The entity stage's cursor is zero from the line above.
@@ -119,8 +119,11 @@ int rays_pass(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 	LMX_HIP(ctx, launch_rays_broad(ctx->stream, d));
 	LMX_HIP(ctx, launch_rays_narrow(ctx->stream, d));
 	LMX_HIP(ctx, launch_rays_resolve(ctx->stream, d));
+	if (rs.scene()) // procedural geometry, terrains and castRay's merge (:2761-2775) behind it
+		if (int rc = rays_scene_pass(ctx, d, d_rays, rs.im ? rs.d_im_hits.p : nullptr)) return rc;
 	rs.ran = true;
 	rs.im_ran = rs.im != nullptr;
+	rs.scene_ran = rs.scene();
 	return LMX_OK;
 }
 
@@ -248,8 +251,9 @@ int lmx_rays_reserve(LmxContext* ctx, uint32_t max_rays, uint32_t max_candidates
 	rs.max_rays = max_rays;
 	rs.max_cand = max_candidates;
 	rs.reserved = true;
-	rs.ran = rs.im_ran = false;
-	return rays_im_reserve(ctx);
+	rs.ran = rs.im_ran = rs.scene_ran = false;
+	if (int rc = rays_im_reserve(ctx)) return rc;
+	return rays_scene_reserve(ctx);
 }
 
 int lmx_rays_cast(LmxContext* ctx, const LmxRay* rays, uint32_t n) {

@@ -547,6 +547,22 @@ struct RaysState {
 	DevBuf<LmxRayImHit> d_im_hits;
 	DevBuf<LmxRay> d_rays_eff;
 	DevBuf<uint32_t> d_im_state;
+	// castRayProceduralGeometry and Terrain::castRay behind the entity stage (lmx_capi_rays_scene.hip): the two tables on the device - a
+	// one-mesh model per geometry in the layout k_ray_narrow reads, the heightmaps as they were given - the stages' outputs and state words
+	uint32_t n_pg = 0, n_terrains = 0;
+	bool scene_ran = false;
+	DevBuf<RayPgRec> d_pg;
+	DevBuf<RayModelRec> d_pg_models;
+	DevBuf<RayMeshRec> d_pg_meshes;
+	DevBuf<float> d_pg_positions;
+	DevBuf<uint8_t> d_pg_indices, d_texels;
+	DevBuf<RayTerrainRec> d_terrains;
+	DevBuf<unsigned long long> d_pg_best;
+	DevBuf<LmxRayPgHit> d_pg_hits;
+	DevBuf<LmxRayTerrainHit> d_terrain_hits;
+	DevBuf<LmxRaySceneHit> d_scene_hits;
+	DevBuf<uint32_t> d_scene_state;
+	bool scene() const { return n_pg != 0 || n_terrains != 0; }
 };
 
 // animation sampling (lmx_capi_anim.hip): Animation resources flattened into concatenated tables, one Animable per skin instance
@@ -615,6 +631,8 @@ int keys_before_layout_change(LmxContext* ctx); // lmx_capi_keys.hip: the slot-o
 int keys_before_tombstones(LmxContext* ctx, const PatchId* d_patches, uint32_t n); // ... for the slots of these id patches (device-visible records; enqueued BEFORE the patch kernel)
 int keys_upload_instances(LmxContext* ctx); // ... the host mirror of the per-entity records goes up if it changed (lmx_keys_run, the draw pass)
 void prof_drain(LmxContext* ctx);
+int rays_scene_reserve(LmxContext* ctx);  // lmx_capi_rays_scene.hip: the scene stages' buffers for the current reserve and tables (may wait for the stream when they grow)
+int rays_scene_pass(LmxContext* ctx, const RaysDevice& d, const LmxRay* rays, const LmxRayImHit* im_hits); // ... enqueues them behind the entity stage `d`; rays: the caller's
 int cull_flush(LmxContext* ctx);          // lmx_capi_cull.hip: make the device copy of the culling sets current
 int cull_dyn_sync_mirror(LmxContext* ctx); // lmx_capi_cull.hip: dyn[] <- device when lmx_world_propagate refreshed it
 bool cull_make_dynamic(LmxContext* ctx, int32_t entity); // lmx_capi_cull_set.hip: move an entity to the dynamic set and mark it as bound to the hierarchy

@@ -530,6 +530,36 @@ struct ImRaysDevice {
 hipError_t launch_imrays_broad(hipStream_t s, const ImRaysDevice& d);   // the candidate list of (ray, instance) pairs and its cursor
 hipError_t launch_imrays_resolve(hipStream_t s, const ImRaysDevice& d); // (behind launch_rays_narrow(d.r)) t_model * scale, the minimum per ray, hit records, effective rays, counters
 
+// ---- castRayProceduralGeometry, Terrain::castRay and castRay's merge (ray_scene_kernels.hip), behind the two stages above ----
+// The procedural stage has state words of its own in the RAYS_* layout (k_ray_narrow reads its cursor there): the first three are
+// LmxRaysSceneCounts. Its overflow goes into the ENTITY stage's RAYS_OVERFLOW word as RAYS_PG_OVERFLOW (k_pgray_write runs behind k_ray_write).
+// The launch constants below are GUESSES as well: none has been compared on a GPU; tools/ray_scene_time.py is the tool.
+enum { RAYS_PG_OVERFLOW = 4 };
+constexpr uint32_t RAY_PG_BROAD_GRID = 1024;  // blocks of k_pgray_broad: they stride over the (256-geometry tile, ray tile) pairs
+constexpr uint32_t RAY_TERRAIN_CHUNK = 64;    // steps of a terrain walk a wave takes at a time: one cell per lane
+constexpr uint32_t RAY_TERRAIN_GRID = 2048;   // blocks of k_terrain_ray: RAY_BLOCK / 64 (ray, terrain) pairs each, strided
+constexpr uint32_t RAY_MAX_TERRAINS = 1024;   // entries of the terrain table (a batch holds rays x terrains hit records)
+struct RayPgRec { int32_t entity; uint32_t castable /* has vertex data and is a triangle list */; };
+struct RayTerrainRec { int32_t entity; uint32_t width, height, format /* LMX_RAY_TERRAIN_* */; float scale[3]; uint32_t ready; uint64_t texel_at /* bytes into `texels`, 4-byte aligned */; };
+struct SceneRaysDevice {
+	RaysDevice r;                  // rays = the caller's, the transforms, the shared scratch; models / meshes / positions / indices = the procedural
+	                               // geometries' own tables (model g = geometry g, one mesh each); state = the stage's own words; hits unused
+	const RayPgRec* pg; uint32_t n_pg;
+	unsigned long long* pg_best;   // [max_rays] (ordered bits of t << 32) | geometry, all ones: no hit
+	LmxRayPgHit* pg_hits;          // [max_rays]
+	const RayTerrainRec* terrains; uint32_t n_terrains;
+	const uint8_t* texels;         // the heightmaps as they were given, back to back
+	LmxRayTerrainHit* terrain_hits; // [max_rays * n_terrains], ray-major
+	const LmxRayHit* hits;         // the entity stage's
+	const LmxRayImHit* im_hits;    // the instanced-model stage's, nullptr without one
+	LmxRaySceneHit* scene_hits;    // [max_rays]
+	uint32_t* entity_state;        // the entity stage's RAYS_* words (RAYS_OVERFLOW)
+};
+hipError_t launch_pgrays_broad(hipStream_t s, const SceneRaysDevice& d);   // the candidate list of (ray, geometry) pairs and its cursor
+hipError_t launch_pgrays_resolve(hipStream_t s, const SceneRaysDevice& d); // (behind launch_rays_narrow(d.r)) the minimum per ray, LmxRayPgHit, counters
+hipError_t launch_terrain_rays(hipStream_t s, const SceneRaysDevice& d);   // LmxRayTerrainHit per (ray, terrain)
+hipError_t launch_scene_write(hipStream_t s, const SceneRaysDevice& d);    // (behind every stage) LmxRaySceneHit per ray
+
 // Pose::computeAbsolute + computeSkinMatrices (+ optional dual-quaternion palette), one wave per PoseGroup
 hipError_t launch_pose_palette(hipStream_t s, const SkinInstance* inst, const PoseGroup* groups, const uint32_t n_groups[3] /* by capacity 4, 2, 1 */,
 	const float* rel_pos, const float4* rel_rot, float* pose_pos, float4* pose_rot, const uint32_t* level_items, const uint16_t* level_off,

@@ -29,6 +29,7 @@
 #include "lmx_kernels.h"
 #include "lmx_entity_tr.h"
 #include "lmx_im.h"
+#include "lmx_ray_math.h"
 
 namespace lmx {
 
@@ -38,9 +39,6 @@ constexpr unsigned long long RAY_NONE = ~0ull;
 constexpr uint32_t RAY_CHUNK = RAY_BLOCK * RAY_RUN; // triangles a block takes per step
 enum : uint32_t { INSTANCE_ENABLED = 1u << 1, INSTANCE_VALID = 1u << 2 }; // ModelInstance::Flags, render_module.h:209-212
 
-__device__ __forceinline__ float safe_inverse_scale(float v) { return v == 0.0f ? 0.0f : 1.0f / v; } // core/math.cpp:9-12
-__device__ __forceinline__ float minimum(float a, float b) { return a < b ? a : b; }               // core/math.h:420-422
-__device__ __forceinline__ float maximum(float a, float b) { return a > b ? a : b; }               // core/math.h:472-475
 __device__ __forceinline__ double length_d(DV3 v) { return sqrt(v.x * v.x + v.y * v.y + v.z * v.z); } // core/math.cpp:393
 
 struct RayTr { DV3 pos; Q4 rot; V3 scale; };
@@ -63,38 +61,6 @@ __device__ __forceinline__ bool ray_sphere(V3 o, V3 dir, float radius) {
 	const float t = tca - thc;
 	const float out = t >= 0 ? t : tca + thc;
 	return out >= 0;
-}
-
-// getRayAABBIntersection(origin, dir, min, size), core/geometry.cpp:861-889; `max` = min + size as the function forms it
-__device__ __forceinline__ bool ray_aabb(V3 o, V3 dir, V3 mn, V3 mx) {
-	const float fx = 1.0f / (dir.x == 0 ? 0.00000001f : dir.x);
-	const float fy = 1.0f / (dir.y == 0 ? 0.00000001f : dir.y);
-	const float fz = 1.0f / (dir.z == 0 ? 0.00000001f : dir.z);
-	const float t1 = (mn.x - o.x) * fx, t2 = (mx.x - o.x) * fx;
-	const float t3 = (mn.y - o.y) * fy, t4 = (mx.y - o.y) * fy;
-	const float t5 = (mn.z - o.z) * fz, t6 = (mx.z - o.z) * fz;
-	const float tmin = maximum(maximum(minimum(t1, t2), minimum(t3, t4)), minimum(t5, t6));
-	const float tmax = minimum(minimum(maximum(t1, t2), maximum(t3, t4)), maximum(t5, t6));
-	if (tmax < 0) return false;
-	if (tmin > tmax) return false;
-	return true;
-}
-
-// The triangle test of Model::castRay, model.cpp:186-206. A NaN t is no hit (the reference accepts it as a first hit).
-__device__ __forceinline__ bool ray_triangle(V3 p0, V3 p1, V3 p2, V3 origin, V3 dir, float* out_t) {
-	const V3 normal = cross(sub(p1, p0), sub(p2, p0));
-	const float q = dot(normal, dir);
-	if (q == 0) return false;
-	const float dd = -dot(normal, p0);
-	const float t = -(dot(normal, origin) + dd) / q;
-	if (t < 0) return false;
-	if (t != t) return false;
-	const V3 hit_point = add(origin, mul(dir, t));
-	if (dot(normal, cross(sub(p1, p0), sub(hit_point, p0))) < 0) return false;
-	if (dot(normal, cross(sub(p2, p1), sub(hit_point, p1))) < 0) return false;
-	if (dot(normal, cross(sub(p0, p2), sub(hit_point, p2))) < 0) return false;
-	*out_t = t;
-	return true;
 }
 
 // evaluateSkin (model.cpp:103-109): ((M0 * w.x + M1 * w.y) + M2 * w.z) + M3 * w.w element by element (math.cpp:1022-1071), then
@@ -147,11 +113,6 @@ __device__ __forceinline__ uint32_t mesh_of(const RayMeshRec* meshes, uint32_t n
 __device__ __forceinline__ unsigned long long hit_key(float t, uint32_t index) {
 	const uint32_t bits = t == 0 ? 0u : __float_as_uint(t); // -0 orders as +0
 	return (unsigned long long)bits << 32 | index;
-}
-
-__device__ __forceinline__ uint32_t candidates(const RaysDevice& d) {
-	const unsigned long long n = *reinterpret_cast<const unsigned long long*>(d.state + RAYS_COUNTER);
-	return n < d.max_cand ? (uint32_t)n : d.max_cand;
 }
 
 __global__ __launch_bounds__(RAY_BLOCK) void k_ray_broad(RaysDevice d) {
@@ -353,13 +314,6 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_ray_write(RaysDevice d) {
 
 // ---- instanced models ----
 
-// (t bits << 32) | slot that orders as `<` does over every non-NaN t, negative ones included; -0 as +0
-__device__ __forceinline__ unsigned long long im_hit_key(float t, uint32_t slot) {
-	const uint32_t bits = t == 0 ? 0u : __float_as_uint(t);
-	const uint32_t ordered = (bits & 0x80000000u) ? ~bits : bits | 0x80000000u;
-	return (unsigned long long)ordered << 32 | slot;
-}
-
 __global__ __launch_bounds__(RAY_BLOCK) void k_imray_broad(ImRaysDevice q) {
 	__shared__ LmxRay s_rays[RAY_BROAD_RAYS];
 	__shared__ V3 s_base[RAY_BROAD_RAYS];
@@ -483,7 +437,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_imray_resolve(ImRaysDevice q) {
 		const float t = im_winner(d, cd, best, &mesh, &triangle);
 		const float scaled = t * q.pos_scale[cd.entity].w; // new_hit.t * id.scale, :2636
 		d.cand_t[c] = scaled;
-		if (scaled < d.rays[cd.ray].t_max) atomicMin(&q.im_best[cd.ray], im_hit_key(scaled, cd.entity)); // (a NaN is below nothing)
+		if (scaled < d.rays[cd.ray].t_max) atomicMin(&q.im_best[cd.ray], ordered_key(scaled, cd.entity)); // (a NaN is below nothing)
 	}
 }
 
@@ -504,7 +458,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_imray_write(ImRaysDevice q) {
 		const RayCandidate cd = d.cand[c];
 		const float scaled = d.cand_t[c];
 		LmxRay ray = d.rays[cd.ray];
-		if (!(scaled < ray.t_max) || q.im_best[cd.ray] != im_hit_key(scaled, cd.entity)) continue; // (one candidate per (ray, slot): one winner)
+		if (!(scaled < ray.t_max) || q.im_best[cd.ray] != ordered_key(scaled, cd.entity)) continue; // (one candidate per (ray, slot): one winner)
 		LmxRayImHit h;
 		h.t_model = im_winner(d, cd, best, &h.mesh, &h.triangle);
 		h.is_hit = 1; h.entity = q.im_ray_models[cd.pad].entity; h.model = cd.pad; h.subindex = cd.entity - q.im_models[cd.pad].first; h.t = scaled;

@@ -3,7 +3,7 @@
 // In the reference RenderModuleImpl::castRay (src/renderer/render_module.cpp:2715-2780) walks every model instance on one thread and every
 // LOD-0 triangle of the instances its gates let through. GpuRayCaster answers a batch of rays where the transforms, palettes and meshes
 // already lie: castRays() uploads the rays, enqueues the cast and reads one record per ray back. What the device does not hold -
-// procedural geometry, terrain, general filter delegates - stays with the caller: it casts those first, passes the best hit it
+// general filter delegates, and procedural geometry and terrain until their tables are set - stays with the caller: it casts those first, passes the best hit it
 // holds as `held` (its t becomes the ray's t_max, so farther model instances are pruned as the reference's walk prunes them), and gets
 // the nearer of the two back, compared as :2746 and :2761-2775 compare them. Only the filter of castRay(ray, ignored) is supported.
 //
@@ -11,6 +11,12 @@
 // gpu_instanced_models.h adapter is attached with setInstancedModels(): the hit comes back with component_type = types::instanced_model,
 // the model's entity, subindex, mesh and t wherever no model instance is strictly nearer, and `held` shrinks to procedural geometry and
 // terrain. Without an attached adapter they stay with the caller as before.
+//
+// Procedural geometry (castRayProceduralGeometry, :2650-2712) and terrains (Terrain::castRay, terrain.cpp:474-535) are cast on the device as
+// well once setProceduralGeometries(module) / setTerrains(module) have filled their tables: castRays() then takes the whole result of
+// castRay(ray, ignored) - the merge of :2761-2775 included - from one LmxRaySceneHit per ray, with component_type = the procedural_geom or
+// terrain type of setSceneTypes(), mesh = nullptr and the entity of :2703 / :2771, and `held` shrinks to what general filter delegates
+// leave with the caller. Call them again when a geometry or a heightmap changes.
 //
 // The geometry tables go up through the C ABI when models load (lmx_rays_add_mesh / lmx_rays_set_models / lmx_rays_set_instances: an
 // engine has the vertex and index arrays at hand in Model::onBeforeReady); transforms come from where the draw pass takes them.
@@ -28,11 +34,15 @@
 #ifdef LMX_WITH_LUMIX_HEADERS
 	#include "core/geometry.h"
 	#include "core/math.h"
+	#include "renderer/gpu/gpu.h"
 	#include "renderer/model.h"
 	#include "renderer/render_module.h"
+	#include "renderer/terrain.h"
+	#include "renderer/texture.h"
 #else
 	#include "lumix_compat.h"
 	#include "lumix_compat_rays.h"
+	#include "lumix_compat_scene_rays.h"
 #endif
 
 namespace Lumix {
@@ -54,6 +64,60 @@ struct GpuRayCaster {
 		m_im_models.assign(models, models + n);
 		m_im_type = instanced_model_type;
 		m_im = im;
+		return true;
+	}
+
+	// The component types the procedural-geometry and terrain hits carry (types::procedural_geom, types::terrain of the renderer)
+	void setSceneTypes(ComponentType procedural_geom_type, ComponentType terrain_type) {
+		m_pg_type = procedural_geom_type;
+		m_terrain_type = terrain_type;
+	}
+
+	// RenderModule::getProceduralGeometries() in its iterated() order -> the device's table (an empty map clears it). The vertex and index
+	// streams are copied before the call returns.
+	template <typename Module> bool setProceduralGeometries(Module& module) {
+		std::vector<LmxRayProcGeom> recs;
+		const auto& geometries = module.getProceduralGeometries(); // (const: walked through begin() / end(), the order of iterated())
+		for (auto iter = geometries.begin(), end = geometries.end(); iter != end; ++iter) {
+			const ProceduralGeometry& pg = iter.value();
+			LmxRayProcGeom g = {};
+			g.entity = iter.key().index;
+			g.triangles = pg.vertex_decl.primitive_type == gpu::PrimitiveType::TRIANGLES ? 1u : 0u;
+			g.aabb_min[0] = pg.aabb.min.x; g.aabb_min[1] = pg.aabb.min.y; g.aabb_min[2] = pg.aabb.min.z;
+			g.aabb_max[0] = pg.aabb.max.x; g.aabb_max[1] = pg.aabb.max.y; g.aabb_max[2] = pg.aabb.max.z;
+			g.vertex_data = pg.vertex_data.data();
+			g.vertex_bytes = (u32)pg.vertex_data.size();
+			g.stride = pg.vertex_decl.getStride();
+			g.index_data = pg.index_data.data();
+			g.index_bytes = pg.index_data.size() == 0 ? 0u : (pg.index_type == gpu::DataType::U16 ? 2u : 4u);
+			g.index_count = pg.getIndexCount();
+			recs.push_back(g);
+		}
+		if (lmx_rays_set_procedural_geometries(m_ctx, (u32)recs.size(), recs.data()) != LMX_OK) return false; // (the device keeps the table it had)
+		m_n_pg = (u32)recs.size();
+		return true;
+	}
+
+	// RenderModule::getTerrains() in its own order (the merge is sequential) -> the device's table. A terrain whose heightmap is missing,
+	// not ready, without data or in a format Terrain::getHeight does not read is kept in the table and never hit.
+	template <typename Module> bool setTerrains(Module& module) {
+		std::vector<LmxRayTerrain> recs;
+		for (Terrain* terrain : module.getTerrains()) {
+			const Texture* hm = terrain->getHeightmap();
+			LmxRayTerrain t = {};
+			t.entity = terrain->getEntity().index;
+			t.width = (u32)terrain->getWidth();
+			t.height = (u32)terrain->getHeight();
+			const Vec3 scale = terrain->getScale();
+			t.scale[0] = scale.x; t.scale[1] = scale.y; t.scale[2] = scale.z;
+			const bool known = hm && (hm->format == gpu::TextureFormat::R16 || hm->format == gpu::TextureFormat::RGBA8);
+			t.format = known && hm->format == gpu::TextureFormat::RGBA8 ? LMX_RAY_TERRAIN_RGBA8 : LMX_RAY_TERRAIN_R16;
+			t.texels = hm ? hm->getData() : nullptr;
+			t.ready = known && hm->isReady() && t.texels && t.width && t.height ? 1u : 0u;
+			recs.push_back(t);
+		}
+		if (lmx_rays_set_terrains(m_ctx, (u32)recs.size(), recs.data()) != LMX_OK) return false; // (the device keeps the table it had)
+		m_n_terrains = (u32)recs.size();
 		return true;
 	}
 
@@ -84,16 +148,28 @@ struct GpuRayCaster {
 		if (m_im && !m_im->flushOrigins()) return false;
 		if (lmx_rays_cast(m_ctx, m_rays.data(), n) != LMX_OK) return false;
 		LmxRaysCounts c;
-		if (lmx_rays_counts(m_ctx, &c) != LMX_OK || c.overflow) return false; // (bit 1: the instanced-model stage)
+		if (lmx_rays_counts(m_ctx, &c) != LMX_OK || c.overflow) return false; // (bit 1: the instanced-model stage, bit 2: the procedural geometries)
 		if (lmx_rays_read_hits(m_ctx, m_hits.data(), n) != LMX_OK) return false;
 		m_im_hits.resize(m_im ? n : 0);
 		if (m_im && lmx_rays_read_im_hits(m_ctx, m_im_hits.data(), n) != LMX_OK) return false;
+		const bool scene = m_n_pg != 0 || m_n_terrains != 0; // the device merged all four stages (:2761-2775)
+		m_scene_hits.resize(scene ? n : 0);
+		if (scene && lmx_rays_read_scene_hits(m_ctx, m_scene_hits.data(), n) != LMX_OK) return false;
 		auto instances = module.getModelInstances();
 		for (u32 i = 0; i < n; ++i) {
 			RayCastModelHit& out = hits[i];
 			const LmxRayHit& h = m_hits[i];
+			if (scene && m_scene_hits[i].is_hit && (m_scene_hits[i].component == LMX_RAY_HIT_PROCEDURAL_GEOM || m_scene_hits[i].component == LMX_RAY_HIT_TERRAIN)) {
+				const LmxRaySceneHit& s = m_scene_hits[i]; // nearer than the model-instance and instanced-model hits as :2762 / :2769 compare them
+				out.is_hit = true;
+				out.t = s.t;
+				out.entity = EntityPtr{s.entity}; // iter.key() (:2703) / terrain->getEntity() (:2771)
+				out.component_type = s.component == LMX_RAY_HIT_TERRAIN ? m_terrain_type : m_pg_type;
+				out.subindex = 0;
+				out.mesh = nullptr;
+			}
 			// `!hit.is_hit || new_t < hit.t` (:2746) was applied on the device through t_max: a device hit is the nearer one
-			if (h.is_hit) {
+			else if (h.is_hit) {
 				out.is_hit = true;
 				out.t = h.t;
 				out.entity = EntityPtr{h.entity};
@@ -138,6 +214,7 @@ struct GpuRayCaster {
 
 	bool counts(LmxRaysCounts& out) { return lmx_rays_counts(m_ctx, &out) == LMX_OK; }
 	bool imCounts(LmxRaysImCounts& out) { return lmx_rays_im_counts(m_ctx, &out) == LMX_OK; }
+	bool sceneCounts(LmxRaysSceneCounts& out) { return lmx_rays_scene_counts(m_ctx, &out) == LMX_OK; }
 	const char* lastError() const { return lmx_last_error(m_ctx); }
 
 private:
@@ -149,6 +226,10 @@ private:
 	ComponentType m_im_type = {};
 	std::vector<Model*> m_im_models;
 	std::vector<LmxRayImHit> m_im_hits;
+	ComponentType m_pg_type = {};
+	ComponentType m_terrain_type = {};
+	u32 m_n_pg = 0, m_n_terrains = 0;
+	std::vector<LmxRaySceneHit> m_scene_hits;
 };
 
 } // namespace Lumix
