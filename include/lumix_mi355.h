@@ -36,7 +36,9 @@ enum {
 	LMX_ERR_OUT_OF_MEMORY = 4,
 	LMX_ERR_CAPACITY = 5,      /* caller buffer too small / too many views, frusta or types */
 	LMX_ERR_NOT_BUILT = 6,     /* operation needs data that has not been uploaded yet */
-	LMX_ERR_BUSY = 7           /* every result slot is held by a caller that has not released it (lmx_cull_view_acquire timed out) */
+	LMX_ERR_BUSY = 7,          /* every result slot is held by a caller that has not released it (lmx_cull_view_acquire timed out) */
+	LMX_ERR_INVALID = 8,       /* a particle program that is malformed or could leave a buffer (lmx_particles_set_program) */
+	LMX_ERR_UNSUPPORTED = 9    /* a well-formed request for something this library does not run on the device */
 };
 
 enum {
@@ -977,6 +979,82 @@ LMX_API int lmx_rays_read_scene_hits(LmxContext* ctx, LmxRaySceneHit* out, uint3
 LMX_API int lmx_rays_scene_counts(LmxContext* ctx, LmxRaysSceneCounts* out);
 /* Device pointers for GPU consumers, valid until the next lmx_rays_reserve or table change: the scene hits and d_counts = LmxRaysSceneCounts. */
 LMX_API int lmx_rays_device_scene_outputs(LmxContext* ctx, const LmxRaySceneHit** d_hits, const uint32_t** d_counts);
+
+/* ---- particle systems: emit, update, kill and fill ---------------------------------------------------------------------------------
+ * ParticleSystem::update (renderer/particle_system.cpp:1620-1656, per emitter :1456-1572) and Emitter::fillInstanceData (:1664-1686) for
+ * every non-ribbon emitter of every registered system, in a fixed number of launches per step and with no host wait inside a step. The
+ * programs are the engine's bytecode, decoded and validated once on the host; particle counts live on the device.
+ *
+ * An LmxParticles object uses its context's device and stream; destroy it before the context. Systems are numbered in the order they are
+ * added, emitters by their index in ParticleSystemResource::getEmitters(); counts, slices and device records are indexed by the GLOBAL
+ * emitter index (systems in order, each system's emitters in order).
+ *
+ * lmx_particles_set_program takes the byte stream of ParticleSystemResource::Emitter::instructions as the engine holds it.
+ *   LMX_ERR_INVALID: anything that could leave a buffer or that the reference only asserts on - a stream type or index out of range for
+ *     its operand position, channel / register indices >= 16 or past the emitter's counts, output indices >= outputs_count, a block size
+ *     past the program, nesting deeper than 4, a GRADIENT with < 2 or > 8 keys, an EMIT target out of range, a missing END, KILL / EMIT
+ *     outside a conditional block, NOT outside one, BLEND / GRADIENT inside one, a conditional inside the true arm of a CMP_ELSE, a
+ *     destination of type LITERAL, GLOBAL or SYSTEM_VALUE.
+ *     Also: more than 8 EMIT instructions in one update program.
+ *   LMX_ERR_UNSUPPORTED: MESH and SPLINE (they need the entity's mesh, pose and spline); ribbons stay with the engine.
+ * Sub-emission (EMIT inside a conditional block) runs on the device: the records are drained in the reference's order at the end of the
+ *   emitter's update, before the system's next emitter updates, and the target's emit program runs init_emit_count times per record.
+ * lmx_particles_reserve sets an emitter's capacity (rounded up to a multiple of four). An emission past it is counted and not written:
+ *   LmxParticlesCounts::overflow. Any reserve or set_program lays the buffers out anew and resets every system (lmx_particles_reset).
+ * lmx_particles_step advances every system by dt: first-frame and rate emission, update, kills, compaction and sub-emission. LMX_ERR_NOT_BUILT while an
+ *   emitter has no program. lmx_particles_fill runs the output programs into one frame buffer: the slice of emitter e is
+ *   ((count + 3) & ~3) * outputs_count * 4 bytes at a 16-byte-aligned offset; rows between count and the next multiple of four are
+ *   written and unspecified. Both enqueue and return
+ *   (a step waits at most for the host-to-device copies of the step before the last).
+ * RAND draws are counter based: keyed by (lmx_particles_set_seed, global emitter, step number, particle slot, instruction). */
+typedef struct LmxParticles LmxParticles;
+typedef struct LmxParticleProgram {
+	const uint8_t* instructions;
+	uint32_t size, emit_offset, output_offset;
+	uint32_t channels_count, registers_count, outputs_count, emit_inputs_count;
+	uint32_t init_emit_count;
+	float emit_per_second;
+} LmxParticleProgram;
+typedef struct LmxParticlesCounts {
+	uint32_t particles;   /* Emitter::particles_count */
+	uint32_t emit_index;  /* Emitter::emit_index */
+	uint32_t overflow;    /* bit 0: an emission went past the reserved capacity since the last reset */
+	uint32_t killed;      /* by the last step */
+} LmxParticlesCounts;
+typedef struct LmxParticleSlice {
+	uint32_t offset;      /* bytes from the start of the frame buffer, a multiple of 16 */
+	uint32_t bytes;       /* Emitter::getParticlesDataSizeBytes */
+	uint32_t particles;
+	uint32_t outputs_count;
+} LmxParticleSlice;
+typedef struct LmxParticlesDevice {
+	const float* d_frame;              /* the slices of the last lmx_particles_fill */
+	const LmxParticleSlice* d_slices;  /* one per emitter */
+	const LmxParticlesCounts* d_counts;/* one per emitter, current after every step */
+	uint32_t n_emitters, frame_bytes;  /* frame_bytes: what the buffer holds (every emitter at capacity) */
+} LmxParticlesDevice;
+enum { LMX_PARTICLES_GUARD_FLOATS = 64 }; /* behind every channel and behind the frame buffer: filled with 0xA5 bytes, never written by a kernel */
+LMX_API int lmx_particles_create(LmxContext* ctx, LmxParticles** out);
+LMX_API void lmx_particles_destroy(LmxParticles* ps);
+LMX_API int lmx_particles_add_system(LmxParticles* ps, uint32_t n_emitters, uint32_t n_globals, uint32_t* out_system);
+LMX_API int lmx_particles_set_program(LmxParticles* ps, uint32_t system, uint32_t emitter, const LmxParticleProgram* program);
+LMX_API int lmx_particles_set_globals(LmxParticles* ps, uint32_t system, const float* globals, uint32_t n);
+/* World::getPosition of every system's entity: n_systems x 3 doubles */
+LMX_API int lmx_particles_set_entity_positions(LmxParticles* ps, uint32_t n_systems, const double* pos_xyz);
+LMX_API int lmx_particles_reserve(LmxParticles* ps, uint32_t system, uint32_t emitter, uint32_t capacity);
+/* ParticleSystem::reset of one system, or of all with system == 0xffffffff */
+LMX_API int lmx_particles_reset(LmxParticles* ps, uint32_t system);
+LMX_API int lmx_particles_set_seed(LmxParticles* ps, uint32_t seed);
+LMX_API int lmx_particles_step(LmxParticles* ps, float dt);
+LMX_API int lmx_particles_fill(LmxParticles* ps);
+/* Read-backs (they wait for the stream). counts: one record per emitter, cap >= the number of emitters. */
+LMX_API int lmx_particles_counts(LmxParticles* ps, LmxParticlesCounts* out, uint32_t cap);
+/* channels_count rows of capacity + LMX_PARTICLES_GUARD_FLOATS floats each; *out_stride: floats per row. cap_floats >= rows x stride. */
+LMX_API int lmx_particles_read_channels(LmxParticles* ps, uint32_t system, uint32_t emitter, float* out, uint32_t cap_floats, uint32_t* out_stride);
+/* slices: one per emitter (cap_slices >= emitters); data (may be NULL): the frame buffer and its guard, cap_bytes >= frame_bytes + guard */
+LMX_API int lmx_particles_read_slices(LmxParticles* ps, LmxParticleSlice* slices, uint32_t cap_slices, void* data, uint32_t cap_bytes);
+/* Device pointers for GPU consumers, valid until the next reserve or set_program; stream-ordered behind lmx_particles_fill */
+LMX_API int lmx_particles_device_outputs(LmxParticles* ps, LmxParticlesDevice* out);
 
 LMX_API const char* lmx_version(void);
 

@@ -353,10 +353,25 @@ SYMBOLS = {
     "lmx_im_read_records": (_ci, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "lmx_im_read_indirect": (_ci, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "lmx_im_device_outputs": (_ci, [_vp, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "lmx_particles_create": (_ci, [_vp, C.POINTER(_vp)]),
+    "lmx_particles_destroy": (None, [_vp]),
+    "lmx_particles_add_system": (_ci, [_vp, _u32, _u32, C.POINTER(_u32)]),
+    "lmx_particles_set_program": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_particles_set_globals": (_ci, [_vp, _u32, _vp, _u32]),
+    "lmx_particles_set_entity_positions": (_ci, [_vp, _u32, _vp]),
+    "lmx_particles_reserve": (_ci, [_vp, _u32, _u32, _u32]),
+    "lmx_particles_reset": (_ci, [_vp, _u32]),
+    "lmx_particles_set_seed": (_ci, [_vp, _u32]),
+    "lmx_particles_step": (_ci, [_vp, _f32]),
+    "lmx_particles_fill": (_ci, [_vp]),
+    "lmx_particles_counts": (_ci, [_vp, _vp, _u32]),
+    "lmx_particles_read_channels": (_ci, [_vp, _u32, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_particles_read_slices": (_ci, [_vp, _vp, _u32, _vp, _u32]),
+    "lmx_particles_device_outputs": (_ci, [_vp, _vp]),
     "lmx_version": (C.c_char_p, []),
 }
 
-ERROR_NAMES = {1: "INVALID_ARGUMENT", 2: "NO_DEVICE", 3: "HIP", 4: "OUT_OF_MEMORY", 5: "CAPACITY", 6: "NOT_BUILT", 7: "BUSY"}
+ERROR_NAMES = {1: "INVALID_ARGUMENT", 2: "NO_DEVICE", 3: "HIP", 4: "OUT_OF_MEMORY", 5: "CAPACITY", 6: "NOT_BUILT", 7: "BUSY", 8: "INVALID", 9: "UNSUPPORTED"}
 ERR_BUSY = 7
 
 
@@ -1695,3 +1710,110 @@ class Skinning:
         rot = np.zeros((n, 4), np.float32)
         self.ctx.check(self.lib.lmx_skin_read_pose(self.ctx.h, instance, _ptr(pos), _ptr(rot), n))
         return pos, rot
+
+
+PARTICLES_COUNTS = np.dtype([("particles", "<u4"), ("emit_index", "<u4"), ("overflow", "<u4"), ("killed", "<u4")])  # LmxParticlesCounts
+PARTICLE_SLICE = np.dtype([("offset", "<u4"), ("bytes", "<u4"), ("particles", "<u4"), ("outputs_count", "<u4")])  # LmxParticleSlice
+PARTICLES_GUARD_FLOATS = 64
+
+
+class LmxParticleProgram(C.Structure):
+    _fields_ = [("instructions", C.c_void_p), ("size", _u32), ("emit_offset", _u32), ("output_offset", _u32), ("channels_count", _u32), ("registers_count", _u32),
+                ("outputs_count", _u32), ("emit_inputs_count", _u32), ("init_emit_count", _u32), ("emit_per_second", _f32)]
+
+
+class LmxParticlesDevice(C.Structure):
+    _fields_ = [("d_frame", C.c_void_p), ("d_slices", C.c_void_p), ("d_counts", C.c_void_p), ("n_emitters", _u32), ("frame_bytes", _u32)]
+
+
+class ParticleSystems:
+    """ParticleSystem::update and Emitter::fillInstanceData of every registered system on the device (lmx_particles_*)."""
+
+    ALL = 0xFFFFFFFF
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(self.lib.lmx_particles_create(ctx.h, C.byref(h)))
+        self.h = h
+        self.emitters = []  # (system, emitter) by global emitter index
+        self.capacity = {}
+        self.outputs = {}
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.lib.lmx_particles_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def addSystem(self, n_emitters: int, n_globals: int = 0) -> int:
+        s = _u32()
+        self.ctx.check(self.lib.lmx_particles_add_system(self.h, n_emitters, n_globals, C.byref(s)))
+        self.emitters += [(s.value, e) for e in range(n_emitters)]
+        return s.value
+
+    def setProgram(self, system: int, emitter: int, instructions: bytes, emit_offset: int, output_offset: int, channels_count: int, registers_count: int,
+                   outputs_count: int, emit_inputs_count: int = 0, init_emit_count: int = 0, emit_per_second: float = 0.0):
+        buf = np.frombuffer(bytes(instructions), np.uint8).copy() if len(instructions) else np.zeros(1, np.uint8)
+        p = LmxParticleProgram(_ptr(buf), len(instructions), emit_offset, output_offset, channels_count, registers_count, outputs_count, emit_inputs_count,
+                               init_emit_count, emit_per_second)
+        self.ctx.check(self.lib.lmx_particles_set_program(self.h, system, emitter, C.byref(p)))
+        self.outputs[(system, emitter)] = outputs_count
+
+    def setGlobals(self, system: int, values):
+        v = np.ascontiguousarray(values, np.float32)
+        self.ctx.check(self.lib.lmx_particles_set_globals(self.h, system, _ptr(v) if len(v) else None, len(v)))
+
+    def setEntityPositions(self, pos):
+        p = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        self.ctx.check(self.lib.lmx_particles_set_entity_positions(self.h, len(p), _ptr(p) if len(p) else None))
+
+    def reserve(self, system: int, emitter: int, capacity: int):
+        self.ctx.check(self.lib.lmx_particles_reserve(self.h, system, emitter, capacity))
+        self.capacity[(system, emitter)] = (capacity + 3) & ~3
+
+    def reset(self, system: int = ALL):
+        self.ctx.check(self.lib.lmx_particles_reset(self.h, system))
+
+    def setSeed(self, seed: int):
+        self.ctx.check(self.lib.lmx_particles_set_seed(self.h, seed))
+
+    def update(self, dt: float):
+        self.ctx.check(self.lib.lmx_particles_step(self.h, float(dt)))
+
+    def fill(self):
+        self.ctx.check(self.lib.lmx_particles_fill(self.h))
+
+    def counts(self) -> np.ndarray:
+        out = np.zeros(len(self.emitters), PARTICLES_COUNTS)
+        self.ctx.check(self.lib.lmx_particles_counts(self.h, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def readChannels(self, system: int, emitter: int, channels_count: int) -> np.ndarray:
+        """[channels_count, capacity + guard] floats: the guard columns must still hold 0xA5 bytes."""
+        stride = self.capacity.get((system, emitter), 0) + PARTICLES_GUARD_FLOATS
+        out = np.zeros((channels_count, stride), np.float32)
+        got = _u32()
+        self.ctx.check(self.lib.lmx_particles_read_channels(self.h, system, emitter, _ptr(out) if out.size else None, out.size, C.byref(got)))
+        assert got.value == stride
+        return out
+
+    def deviceOutputs(self) -> LmxParticlesDevice:
+        d = LmxParticlesDevice()
+        self.ctx.check(self.lib.lmx_particles_device_outputs(self.h, C.byref(d)))
+        return d
+
+    def readSlices(self):
+        """(slice records by global emitter index, the frame buffer with its guard as float32)."""
+        d = self.deviceOutputs()
+        slices = np.zeros(len(self.emitters), PARTICLE_SLICE)
+        data = np.zeros(d.frame_bytes // 4 + PARTICLES_GUARD_FLOATS, np.float32)
+        self.ctx.check(self.lib.lmx_particles_read_slices(self.h, _ptr(slices) if len(slices) else None, len(slices), _ptr(data), data.nbytes))
+        return slices, data

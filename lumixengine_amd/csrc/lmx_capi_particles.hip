@@ -1,0 +1,432 @@
+// lmx_capi_particles.hip — particle-system entry points (include/lumix_mi355.h, "particle systems" section): the registered systems and
+// their decoded programs, the buffer layout, the host's scalar emission state (emit_timer, total time) and the launch chain of
+// particle_kernels.hip. lmx_particles_step and lmx_particles_fill enqueue and return: no particle count reaches the host inside a step.
+#include "lmx_context.h"
+#include "lmx_particles.h"
+
+using namespace lmx;
+
+namespace {
+constexpr uint32_t PARTICLES_MAGIC = 0x50415254u; // "PART": an object of another kind passed as LmxParticles is refused, not used
+constexpr uint32_t MAX_CAPACITY = 1u << 26;
+}
+
+struct LmxParticles {
+	uint32_t magic = PARTICLES_MAGIC;
+	LmxContext* ctx = nullptr;
+	struct Emitter {
+		ParticleProgram prog;
+		bool has_program = false;
+		uint32_t channels = 0, registers = 0, outputs = 0, emit_inputs = 0, init_emit_count = 0, capacity = 0;
+		float emit_per_second = 0.0f;
+		float emit_timer = 0.0f; // Emitter::emit_timer: host state, it depends on dt alone
+	};
+	struct System {
+		uint32_t first = 0, n = 0;
+		std::vector<float> globals;
+		double pos[3] = {0, 0, 0};
+		float total_time = 0.0f; // ParticleSystem::m_total_time
+	};
+	std::vector<System> systems;
+	std::vector<Emitter> emitters;
+	bool dirty = true; // the device tables and buffers are older than the registered programs / capacities
+	uint32_t seed = 0, step = 0;
+	uint32_t max_chunks = 0, max_registers = 0, max_shadow = 0, frame_floats = 0;
+	uint32_t levels = 0;   // the largest number of emitters in one system
+	bool any_emit = false; // a program holds EMIT: emitter k of every system is updated and drained before emitter k + 1 (one pass per k)
+	std::vector<ParticleEmitterDev> table;
+	// what a step uploads, twice: a step fills the set the step before the last one used, once that one's copies have left the host
+	// (uploaded[set], recorded behind them) - lmx_particles_step never waits for the kernels of an earlier step
+	std::vector<ParticleSystemDev> sys_host, sys_up[2];
+	std::vector<ParticleEmitJob> jobs_first_up[2], jobs_rate_up[2];
+	hipEvent_t uploaded[2] = {nullptr, nullptr};
+	bool upload_pending[2] = {false, false};
+	~LmxParticles() {
+		for (hipEvent_t e : uploaded)
+			if (e) (void)hipEventDestroy(e);
+	}
+	DevBuf<ParticleEmitterDev> d_emitters;
+	DevBuf<ParticleSystemDev> d_systems;
+	DevBuf<ParticleRec> d_prog;
+	DevBuf<ParticleGradient> d_gradients;
+	DevBuf<float> d_globals, d_channels, d_frame;
+	DevBuf<ParticleStateDev> d_state;
+	DevBuf<uint32_t> d_kill, d_n_ops, d_stage, d_n_sub;
+	DevBuf<ParticleSubJob> d_sub_jobs;
+	DevBuf<ParticleCopyOp> d_ops;
+	DevBuf<LmxParticleSlice> d_slices;
+	DevBuf<ParticleEmitJob> d_jobs_first, d_jobs_rate;
+
+	ParticlesDevice dev() const {
+		ParticlesDevice d;
+		d.emitters = d_emitters.p; d.systems = d_systems.p; d.prog = d_prog.p; d.gradients = d_gradients.p; d.globals = d_globals.p;
+		d.channels = d_channels.p; d.state = d_state.p; d.kill = d_kill.p; d.ops = d_ops.p; d.n_ops = d_n_ops.p; d.slices = d_slices.p; d.frame = d_frame.p;
+		d.stage = d_stage.p; d.sub_jobs = d_sub_jobs.p; d.n_sub = d_n_sub.p; d.level = 0xffffffffu;
+		d.n_emitters = (uint32_t)emitters.size(); d.seed = seed; d.step = step; d.frame_floats = frame_floats;
+		return d;
+	}
+};
+
+static_assert(sizeof(LmxParticlesCounts) == sizeof(ParticleStateDev), "lmx_particles_counts reads the state records as they are");
+
+namespace {
+
+#define LMX_CHECK_PARTICLES(ps)                                                         \
+	if (!(ps) || (ps)->magic != PARTICLES_MAGIC) return LMX_ERR_INVALID_ARGUMENT;      \
+	LmxContext* ctx = (ps)->ctx;                                                        \
+	LMX_CHECK_CTX(ctx)
+
+int find_emitter(LmxParticles* ps, uint32_t system, uint32_t emitter, uint32_t* out) {
+	if (system >= ps->systems.size()) return fail(ps->ctx, LMX_ERR_INVALID_ARGUMENT, "particle system %u: %zu registered", system, ps->systems.size());
+	if (emitter >= ps->systems[system].n) return fail(ps->ctx, LMX_ERR_INVALID_ARGUMENT, "emitter %u: system %u has %u", emitter, system, ps->systems[system].n);
+	*out = ps->systems[system].first + emitter;
+	return LMX_OK;
+}
+
+void reset_host(LmxParticles* ps, uint32_t system) {
+	LmxParticles::System& s = ps->systems[system];
+	s.total_time = 0.0f;
+	for (uint32_t e = s.first; e < s.first + s.n; ++e) ps->emitters[e].emit_timer = 0.0f;
+}
+
+// Device tables, program records and buffers for the registered programs and capacities. Everything starts empty: a new layout is a reset.
+int build(LmxParticles* ps) {
+	LmxContext* ctx = ps->ctx;
+	for (size_t e = 0; e < ps->emitters.size(); ++e)
+		if (!ps->emitters[e].has_program) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_particles_set_program has not been called for every emitter (global emitter %zu)", e);
+	if (!ps->dirty) return LMX_OK;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	const size_t n = ps->emitters.size();
+	std::vector<ParticleRec> recs;
+	std::vector<ParticleGradient> grads;
+	std::vector<float> globals;
+	ps->table.assign(n, ParticleEmitterDev());
+	ps->sys_host.assign(ps->systems.size(), ParticleSystemDev());
+	uint64_t floats = 0, frame = 0, stage_words = 0, sub_jobs = 0;
+	uint32_t chunks_total = 0;
+	ps->levels = 0;
+	ps->any_emit = false;
+	ps->max_chunks = ps->max_registers = ps->max_shadow = 0;
+	for (size_t s = 0; s < ps->systems.size(); ++s) {
+		LmxParticles::System& sy = ps->systems[s];
+		memset(&ps->sys_host[s], 0, sizeof(ParticleSystemDev));
+		ps->sys_host[s].globals_at = (uint32_t)globals.size();
+		ps->sys_host[s].n_globals = (uint32_t)sy.globals.size();
+		globals.insert(globals.end(), sy.globals.begin(), sy.globals.end());
+		for (uint32_t k = 0; k < sy.n; ++k) {
+			const LmxParticles::Emitter& em = ps->emitters[sy.first + k];
+			ParticleEmitterDev& t = ps->table[sy.first + k];
+			memset(&t, 0, sizeof(t));
+			const uint32_t base = (uint32_t)recs.size(), gbase = (uint32_t)grads.size();
+			for (ParticleRec r : em.prog.recs) { // record indices become absolute
+				if (r.op == P_CMP || r.op == P_CMP_ELSE) { r.a += base; r.c += base; }
+				if (r.op == P_END && r.kind == PE_JUMP) r.a += base;
+				if (r.op == P_GRADIENT) r.a += gbase;
+				recs.push_back(r);
+			}
+			grads.insert(grads.end(), em.prog.gradients.begin(), em.prog.gradients.end());
+			t.system = (uint32_t)s;
+			t.prog_update = base + em.prog.update_at; t.prog_emit = base + em.prog.emit_at; t.prog_output = base + em.prog.output_at;
+			t.channels = em.channels; t.registers = em.registers; t.outputs = em.outputs; t.emit_inputs = em.emit_inputs;
+			t.capacity = em.capacity;
+			t.stride = em.capacity + PARTICLE_GUARD_FLOATS;
+			t.max_chunks = (em.capacity + PARTICLE_CHUNK - 1) / PARTICLE_CHUNK;
+			t.shadow_mask = em.prog.shadow_mask;
+			t.channel_base = floats;
+			t.kill_base = chunks_total;
+			t.local = k; t.first_of_system = sy.first; t.init_emit_count = em.init_emit_count;
+			t.n_emit = em.prog.emit_count;
+			memcpy(t.emit_group, em.prog.emit_group, sizeof(t.emit_group));
+			t.stage_base = stage_words;
+			t.job_base = (uint32_t)sub_jobs;
+			stage_words += (uint64_t)em.capacity * t.n_emit * PARTICLE_STAGE_WORDS;
+			sub_jobs += (uint64_t)em.capacity * t.n_emit;
+			ps->any_emit = ps->any_emit || t.n_emit != 0;
+			ps->levels = std::max(ps->levels, k + 1);
+			floats += (uint64_t)t.stride * em.channels;
+			frame += (uint64_t)em.capacity * em.outputs;
+			chunks_total += t.max_chunks;
+			ps->max_chunks = std::max(ps->max_chunks, t.max_chunks);
+			ps->max_registers = std::max(ps->max_registers, em.registers);
+			ps->max_shadow = std::max(ps->max_shadow, (uint32_t)__builtin_popcount(em.prog.shadow_mask));
+		}
+	}
+	if (sub_jobs > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "the sub-emission staging of every emitter at capacity exceeds 2^32 records");
+	if (frame * 4 + PARTICLE_GUARD_FLOATS * 4 > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "the frame buffer of every emitter at capacity exceeds 4 GiB");
+	ps->frame_floats = (uint32_t)frame;
+	LMX_HIP(ctx, upload_on_stream(ps->d_emitters, ps->table, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ps->d_prog, recs, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ps->d_gradients, grads, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ps->d_globals, globals, ctx->stream));
+	LMX_HIP(ctx, ps->d_systems.reserve(std::max<size_t>(ps->systems.size(), 1)));
+	LMX_HIP(ctx, ps->d_channels.reserve(std::max<size_t>(floats, 1)));
+	LMX_HIP(ctx, ps->d_frame.reserve(frame + PARTICLE_GUARD_FLOATS));
+	LMX_HIP(ctx, ps->d_state.reserve(std::max<size_t>(n, 1)));
+	LMX_HIP(ctx, ps->d_kill.reserve(std::max<uint32_t>(chunks_total, 1)));
+	LMX_HIP(ctx, ps->d_ops.reserve(std::max<uint32_t>(chunks_total, 1)));
+	LMX_HIP(ctx, ps->d_n_ops.reserve(std::max<size_t>(n, 1)));
+	LMX_HIP(ctx, ps->d_n_sub.reserve(std::max<size_t>(n, 1)));
+	LMX_HIP(ctx, ps->d_stage.reserve(std::max<uint64_t>(stage_words, 1)));
+	LMX_HIP(ctx, ps->d_sub_jobs.reserve(std::max<uint64_t>(sub_jobs, 1)));
+	LMX_HIP(ctx, ps->d_slices.reserve(std::max<size_t>(n, 1)));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_channels.p, 0, floats * sizeof(float), ctx->stream));
+	for (size_t e = 0; e < n; ++e) { // the guards behind every channel
+		const ParticleEmitterDev& t = ps->table[e];
+		for (uint32_t c = 0; c < t.channels; ++c)
+			LMX_HIP(ctx, hipMemsetAsync(ps->d_channels.p + t.channel_base + (size_t)c * t.stride + t.capacity, 0xA5, PARTICLE_GUARD_FLOATS * 4, ctx->stream));
+	}
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_frame.p, 0, frame * sizeof(float), ctx->stream));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_frame.p + frame, 0xA5, PARTICLE_GUARD_FLOATS * 4, ctx->stream));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_state.p, 0, std::max<size_t>(n, 1) * sizeof(ParticleStateDev), ctx->stream));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_kill.p, 0, std::max<uint32_t>(chunks_total, 1) * sizeof(uint32_t), ctx->stream));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_n_ops.p, 0, std::max<size_t>(n, 1) * sizeof(uint32_t), ctx->stream));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_n_sub.p, 0, std::max<size_t>(n, 1) * sizeof(uint32_t), ctx->stream));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_stage.p, 0, std::max<uint64_t>(stage_words, 1) * sizeof(uint32_t), ctx->stream));
+	LMX_HIP(ctx, hipMemsetAsync(ps->d_slices.p, 0, std::max<size_t>(n, 1) * sizeof(LmxParticleSlice), ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	for (uint32_t s = 0; s < ps->systems.size(); ++s) reset_host(ps, s);
+	ps->step = 0;
+	ps->dirty = false;
+	return LMX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int lmx_particles_create(LmxContext* ctx, LmxParticles** out) {
+	LMX_CHECK_CTX(ctx);
+	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
+	LmxParticles* ps = new (std::nothrow) LmxParticles();
+	if (!ps) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "particles: host allocation failed");
+	ps->ctx = ctx;
+	*out = ps;
+	return LMX_OK;
+}
+
+void lmx_particles_destroy(LmxParticles* ps) {
+	if (!ps || ps->magic != PARTICLES_MAGIC) return;
+	(void)hipSetDevice(ps->ctx->device);
+	(void)hipStreamSynchronize(ps->ctx->stream);
+	ps->magic = 0;
+	delete ps;
+}
+
+int lmx_particles_add_system(LmxParticles* ps, uint32_t n_emitters, uint32_t n_globals, uint32_t* out_system) {
+	LMX_CHECK_PARTICLES(ps);
+	if (n_globals > 256) return fail(ctx, LMX_ERR_CAPACITY, "%u globals: a program's operand indexes at most 256", n_globals);
+	if (n_emitters > 65536 || ps->emitters.size() + n_emitters > 65535) return fail(ctx, LMX_ERR_CAPACITY, "more than 65535 emitters (a launch's grid)");
+	LmxParticles::System s;
+	s.first = (uint32_t)ps->emitters.size();
+	s.n = n_emitters;
+	s.globals.assign(n_globals, 0.0f);
+	ps->emitters.resize(ps->emitters.size() + n_emitters);
+	if (out_system) *out_system = (uint32_t)ps->systems.size();
+	ps->systems.push_back(std::move(s));
+	ps->dirty = true;
+	return LMX_OK;
+}
+
+int lmx_particles_set_program(LmxParticles* ps, uint32_t system, uint32_t emitter, const LmxParticleProgram* p) {
+	LMX_CHECK_PARTICLES(ps);
+	uint32_t e;
+	if (int rc = find_emitter(ps, system, emitter, &e)) return rc;
+	if (!p || !p->instructions) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null program");
+	ParticleProgramDesc desc;
+	desc.bytes = p->instructions; desc.size = p->size; desc.emit_offset = p->emit_offset; desc.output_offset = p->output_offset;
+	desc.channels_count = p->channels_count; desc.registers_count = p->registers_count; desc.outputs_count = p->outputs_count;
+	desc.emit_inputs_count = p->emit_inputs_count;
+	desc.n_emitters = ps->systems[system].n;
+	desc.n_globals = (uint32_t)ps->systems[system].globals.size();
+	ParticleProgram prog;
+	std::string err;
+	if (particle_program_decode(desc, prog, err) != PD_OK) return fail(ctx, LMX_ERR_INVALID, "%s", err.c_str());
+	if (prog.has_mesh_or_spline) return fail(ctx, LMX_ERR_UNSUPPORTED, "MESH / SPLINE instructions need the entity's mesh, pose and spline: not run on the device");
+	if (!(p->emit_per_second == p->emit_per_second)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "emit_per_second is not a number");
+	LmxParticles::Emitter& em = ps->emitters[e];
+	em.prog = std::move(prog);
+	em.has_program = true;
+	em.channels = p->channels_count; em.registers = p->registers_count; em.outputs = p->outputs_count; em.emit_inputs = p->emit_inputs_count;
+	em.init_emit_count = p->init_emit_count;
+	em.emit_per_second = p->emit_per_second;
+	ps->dirty = true;
+	return LMX_OK;
+}
+
+int lmx_particles_set_globals(LmxParticles* ps, uint32_t system, const float* globals, uint32_t n) {
+	LMX_CHECK_PARTICLES(ps);
+	if (system >= ps->systems.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "particle system %u: %zu registered", system, ps->systems.size());
+	LmxParticles::System& s = ps->systems[system];
+	if (n != s.globals.size() || (n && !globals)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "system %u has %zu globals", system, s.globals.size());
+	if (n) memcpy(s.globals.data(), globals, n * sizeof(float));
+	if (!ps->dirty && n) {
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ps->d_globals.p + ps->sys_host[system].globals_at, s.globals.data(), n, ctx->stream)); // (the system's own array: it stays)
+	}
+	return LMX_OK;
+}
+
+int lmx_particles_set_entity_positions(LmxParticles* ps, uint32_t n_systems, const double* pos_xyz) {
+	LMX_CHECK_PARTICLES(ps);
+	if (n_systems != ps->systems.size() || (n_systems && !pos_xyz)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "%zu particle systems registered", ps->systems.size());
+	for (uint32_t s = 0; s < n_systems; ++s) memcpy(ps->systems[s].pos, pos_xyz + 3 * (size_t)s, sizeof(double) * 3);
+	return LMX_OK;
+}
+
+int lmx_particles_reserve(LmxParticles* ps, uint32_t system, uint32_t emitter, uint32_t capacity) {
+	LMX_CHECK_PARTICLES(ps);
+	uint32_t e;
+	if (int rc = find_emitter(ps, system, emitter, &e)) return rc;
+	if (capacity > MAX_CAPACITY) return fail(ctx, LMX_ERR_CAPACITY, "%u particles: at most 2^26 per emitter", capacity);
+	ps->emitters[e].capacity = (capacity + 3u) & ~3u;
+	ps->dirty = true;
+	return LMX_OK;
+}
+
+int lmx_particles_reset(LmxParticles* ps, uint32_t system) {
+	LMX_CHECK_PARTICLES(ps);
+	if (system != 0xffffffffu && system >= ps->systems.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "particle system %u: %zu registered", system, ps->systems.size());
+	const uint32_t s0 = system == 0xffffffffu ? 0 : system, s1 = system == 0xffffffffu ? (uint32_t)ps->systems.size() : system + 1;
+	for (uint32_t s = s0; s < s1; ++s) {
+		reset_host(ps, s);
+		if (!ps->dirty && ps->systems[s].n)
+			LMX_HIP(ctx, hipMemsetAsync(ps->d_state.p + ps->systems[s].first, 0, ps->systems[s].n * sizeof(ParticleStateDev), ctx->stream));
+	}
+	return LMX_OK;
+}
+
+int lmx_particles_set_seed(LmxParticles* ps, uint32_t seed) {
+	LMX_CHECK_PARTICLES(ps);
+	ps->seed = seed;
+	return LMX_OK;
+}
+
+int lmx_particles_step(LmxParticles* ps, float dt) {
+	LMX_CHECK_PARTICLES(ps);
+	if (int rc = build(ps)) return rc;
+	if (ps->emitters.empty()) return LMX_OK;
+	const uint32_t set = ps->step & 1u;
+	if (!ps->uploaded[set]) LMX_HIP(ctx, hipEventCreateWithFlags(&ps->uploaded[set], hipEventDisableTiming));
+	if (ps->upload_pending[set]) LMX_HIP(ctx, hipEventSynchronize(ps->uploaded[set])); // the copies of two steps ago have left this set's arrays
+	ps->upload_pending[set] = false;
+	std::vector<ParticleEmitJob>&jobs_first = ps->jobs_first_up[set], &jobs_rate = ps->jobs_rate_up[set];
+	jobs_first.clear();
+	jobs_rate.clear();
+	uint32_t max_first = 0, max_rate = 0;
+	for (size_t s = 0; s < ps->systems.size(); ++s) { // ParticleSystem::update(dt, page_allocator), the scalar part
+		LmxParticles::System& sy = ps->systems[s];
+		ParticleSystemDev& sv = ps->sys_host[s];
+		sv.values[PSV_TIME_DELTA] = dt;
+		sv.values[PSV_EMIT_INDEX] = 0.0f;
+		sv.values[PSV_RIBBON_INDEX] = 0.0f;
+		sv.values[PSV_ENTITY_X] = (float)sy.pos[0]; sv.values[PSV_ENTITY_Y] = (float)sy.pos[1]; sv.values[PSV_ENTITY_Z] = (float)sy.pos[2];
+		if (sy.total_time == 0.0f) {
+			for (uint32_t e = sy.first; e < sy.first + sy.n; ++e) {
+				const LmxParticles::Emitter& em = ps->emitters[e];
+				if (em.emit_inputs == 0 && em.init_emit_count) {
+					jobs_first.push_back(ParticleEmitJob{e, em.init_emit_count, sy.total_time, 0.0f});
+					max_first = std::max(max_first, em.init_emit_count);
+				}
+			}
+		}
+		sy.total_time += dt;
+		sv.values[PSV_TOTAL_TIME] = sy.total_time;
+		for (uint32_t e = sy.first; e < sy.first + sy.n; ++e) { // the head of update(dt, emitter_idx, ...), :1467-1478
+			LmxParticles::Emitter& em = ps->emitters[e];
+			if (!(em.emit_per_second > 0)) continue;
+			em.emit_timer += dt;
+			if (!(em.emit_timer > 0)) continue;
+			const float d = 1.f / em.emit_per_second;
+			const float q = floorf(em.emit_timer / d);
+			const uint32_t count = q < 9223372036854775808.0f ? (uint32_t)(uint64_t)(int64_t)q : 0u; // u32(float) as x86-64 converts it
+			em.emit_timer -= d * count;
+			if (!count) continue;
+			jobs_rate.push_back(ParticleEmitJob{e, count, sy.total_time, d});
+			max_rate = std::max(max_rate, count);
+		}
+	}
+	ps->sys_up[set] = ps->sys_host;
+	LMX_HIP(ctx, upload_on_stream(ps->d_systems, ps->sys_up[set], ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(ps->d_jobs_first, jobs_first, ctx->stream));
+	// (the rate jobs were pushed system by system: sorted by the emitter's index in its system, one pass takes a contiguous range)
+	std::stable_sort(jobs_rate.begin(), jobs_rate.end(), [&](const ParticleEmitJob& a, const ParticleEmitJob& b) { return ps->table[a.emitter].local < ps->table[b.emitter].local; });
+	LMX_HIP(ctx, upload_on_stream(ps->d_jobs_rate, jobs_rate, ctx->stream));
+	LMX_HIP(ctx, hipEventRecord(ps->uploaded[set], ctx->stream));
+	ps->upload_pending[set] = true;
+	++ps->step;
+	ParticlesDevice d = ps->dev();
+	const uint32_t cap_lanes = ps->max_chunks * PARTICLE_CHUNK; // a launch covers what fits the emitters' capacities: the rest of an oversized emission is only counted
+	LMX_HIP(ctx, launch_particles_emit(ctx->stream, d, ps->d_jobs_first.p, (uint32_t)jobs_first.size(), std::min(max_first, cap_lanes)));
+	if (!ps->any_emit) { // no emitter depends on another: one pass over all of them
+		LMX_HIP(ctx, launch_particles_emit(ctx->stream, d, ps->d_jobs_rate.p, (uint32_t)jobs_rate.size(), std::min(max_rate, cap_lanes)));
+		LMX_HIP(ctx, launch_particles_update(ctx->stream, d, ps->max_chunks, ps->max_registers, ps->max_shadow, false));
+		return LMX_OK;
+	}
+	size_t at = 0;
+	for (uint32_t k = 0; k < ps->levels; ++k) { // emitter k of every system: its rate emission, update, compaction, then the drain of its EMIT records
+		size_t end = at;
+		while (end < jobs_rate.size() && ps->table[jobs_rate[end].emitter].local == k) ++end;
+		d.level = k;
+		LMX_HIP(ctx, launch_particles_emit(ctx->stream, d, ps->d_jobs_rate.p + at, (uint32_t)(end - at), std::min(max_rate, cap_lanes)));
+		LMX_HIP(ctx, launch_particles_update(ctx->stream, d, ps->max_chunks, ps->max_registers, ps->max_shadow, true));
+		at = end;
+	}
+	return LMX_OK;
+}
+
+int lmx_particles_fill(LmxParticles* ps) {
+	LMX_CHECK_PARTICLES(ps);
+	if (int rc = build(ps)) return rc;
+	if (ps->emitters.empty()) return LMX_OK;
+	LMX_HIP(ctx, launch_particles_fill(ctx->stream, ps->dev(), ps->max_chunks, ps->max_registers));
+	return LMX_OK;
+}
+
+int lmx_particles_counts(LmxParticles* ps, LmxParticlesCounts* out, uint32_t cap) {
+	LMX_CHECK_PARTICLES(ps);
+	if (int rc = build(ps)) return rc;
+	if (cap < ps->emitters.size() || (!out && !ps->emitters.empty())) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu emitters", ps->emitters.size());
+	LMX_HIP(ctx, read_back((ParticleStateDev*)out, (const ParticleStateDev*)ps->d_state.p, ps->emitters.size(), ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return LMX_OK;
+}
+
+int lmx_particles_read_channels(LmxParticles* ps, uint32_t system, uint32_t emitter, float* out, uint32_t cap_floats, uint32_t* out_stride) {
+	LMX_CHECK_PARTICLES(ps);
+	uint32_t e;
+	if (int rc = find_emitter(ps, system, emitter, &e)) return rc;
+	if (int rc = build(ps)) return rc;
+	const ParticleEmitterDev& t = ps->table[e];
+	const size_t need = (size_t)t.stride * t.channels;
+	if (out_stride) *out_stride = t.stride;
+	if (cap_floats < need || (!out && need)) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu floats", need);
+	LMX_HIP(ctx, read_back(out, (const float*)ps->d_channels.p + t.channel_base, need, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return LMX_OK;
+}
+
+int lmx_particles_read_slices(LmxParticles* ps, LmxParticleSlice* slices, uint32_t cap_slices, void* data, uint32_t cap_bytes) {
+	LMX_CHECK_PARTICLES(ps);
+	if (int rc = build(ps)) return rc;
+	if (cap_slices < ps->emitters.size() || (!slices && !ps->emitters.empty())) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu slices", ps->emitters.size());
+	const size_t bytes = ((size_t)ps->frame_floats + PARTICLE_GUARD_FLOATS) * 4;
+	if (data && cap_bytes < bytes) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu bytes", bytes);
+	LMX_HIP(ctx, read_back(slices, (const LmxParticleSlice*)ps->d_slices.p, ps->emitters.size(), ctx->stream));
+	LMX_HIP(ctx, read_back((float*)data, (const float*)ps->d_frame.p, bytes / 4, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return LMX_OK;
+}
+
+int lmx_particles_device_outputs(LmxParticles* ps, LmxParticlesDevice* out) {
+	LMX_CHECK_PARTICLES(ps);
+	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
+	if (int rc = build(ps)) return rc;
+	out->d_frame = ps->d_frame.p;
+	out->d_slices = ps->d_slices.p;
+	out->d_counts = (const LmxParticlesCounts*)ps->d_state.p;
+	out->n_emitters = (uint32_t)ps->emitters.size();
+	out->frame_bytes = ps->frame_floats * 4;
+	return LMX_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,86 @@
+// lmx_particles.h — device layout and launchers of the particle kernels (particle_kernels.hip), shared with lmx_capi_particles.hip.
+//
+// Every emitter of every registered system has one ParticleEmitterDev. Its channels lie back to back in one float buffer, `stride`
+// floats apart: `capacity` slots (a multiple of four) and a guard the kernels never write. Particle counts live on the device
+// (ParticleStateDev) and never travel to the host inside a step: grids are sized by reserved capacity, and a block whose chunk starts
+// at or past the count exits after one load.
+#pragma once
+
+#include "lmx_kernels.h"
+#include "lmx_particle_program.h"
+#include "lumix_mi355.h"
+
+namespace lmx {
+
+constexpr uint32_t PARTICLE_BLOCK = PARTICLE_CHUNK;     // one lane per particle of a chunk
+constexpr uint32_t PARTICLE_EMIT_BLOCK = 256;           // one lane per new particle
+constexpr uint32_t PARTICLE_GUARD_FLOATS = 64;          // behind every channel and behind the frame buffer
+constexpr uint32_t PARTICLE_SCAN_BLOCK = 1024;
+
+struct ParticleEmitterDev {
+	uint32_t system, prog_update, prog_emit, prog_output; // absolute record indices
+	uint32_t channels, registers, outputs, emit_inputs;
+	uint32_t capacity, stride, max_chunks, shadow_mask;
+	uint64_t channel_base;  // float index of channel 0, slot 0
+	uint32_t kill_base;     // first of max_chunks kill counters; the compaction's copy list starts at the same index
+	uint32_t local;         // index within its system: emitter k's sub-emission is drained before emitter k + 1 updates
+	uint32_t first_of_system; // global index of the system's emitter 0 (EMIT targets are system-local)
+	uint32_t init_emit_count;
+	uint32_t n_emit;        // EMIT instructions of the update program; 0: no staging
+	uint32_t job_base;      // first of capacity x n_emit sub-emission jobs
+	uint64_t stage_base;    // word index of the staging records [slot][n_emit] of PARTICLE_STAGE_WORDS words
+	uint8_t emit_group[PARTICLE_MAX_EMITS];
+};
+
+struct ParticleSystemDev {
+	float values[8];        // ParticleSystemValues of the step (EMIT_INDEX is per particle and lives elsewhere)
+	uint32_t globals_at, n_globals, pad[2];
+};
+
+struct ParticleStateDev {   // per emitter
+	uint32_t count, emit_index, overflow, killed;
+};
+
+struct ParticleEmitJob {    // one call of ParticleSystem::emit
+	uint32_t emitter, count;
+	float total_time, time_step; // TOTAL_TIME of the first new particle, and what each further one adds
+};
+
+struct ParticleCopyOp { uint32_t dst, src, len, pad; };
+
+// One EMIT a particle executed: {1, target, 16 emit outputs}, at [slot * n_emit + ordinal] of the emitter's staging area
+constexpr uint32_t PARTICLE_STAGE_WORDS = 18;
+constexpr uint32_t PARTICLE_SUB_BLOCKS = 32; // blocks per emitter of the sub-emission launch: each strides over the emitter's jobs
+// One drained record: ParticleSystem::emit(target, outputs, init_emit_count, 0), with the slots it got
+struct ParticleSubJob { uint32_t stage_index, target, slot, emit_index, n; };
+
+struct ParticlesDevice {
+	const ParticleEmitterDev* emitters;
+	const ParticleSystemDev* systems;
+	const ParticleRec* prog;
+	const ParticleGradient* gradients;
+	const float* globals;
+	float* channels;
+	ParticleStateDev* state;
+	uint32_t* kill;          // per chunk
+	ParticleCopyOp* ops;     // per chunk
+	uint32_t* n_ops;         // per emitter
+	uint32_t* stage;         // staging records of the emitters whose update programs hold EMIT
+	ParticleSubJob* sub_jobs;
+	uint32_t* n_sub;         // per emitter: jobs of the last plan
+	LmxParticleSlice* slices;
+	float* frame;
+	uint32_t n_emitters, seed, step, frame_floats;
+	uint32_t level;          // only emitters with this index in their system take part; 0xffffffff: all
+};
+
+size_t particle_chunk_lds_bytes(uint32_t registers, uint32_t shadow_channels);
+
+hipError_t launch_particles_emit(hipStream_t s, const ParticlesDevice& d, const ParticleEmitJob* jobs, uint32_t n_jobs, uint32_t max_count);
+// processChunk over every chunk of every emitter with the update program, then the compaction plan and its copies
+// ... and, with `sub_emit`, the drain of the EMIT records into their targets behind them
+hipError_t launch_particles_update(hipStream_t s, const ParticlesDevice& d, uint32_t max_chunks, uint32_t max_registers, uint32_t max_shadow, bool sub_emit);
+// slice offsets, then processChunk with the output program
+hipError_t launch_particles_fill(hipStream_t s, const ParticlesDevice& d, uint32_t max_chunks, uint32_t max_registers);
+
+} // namespace lmx

@@ -1,0 +1,593 @@
+// particle_kernels.hip — ParticleSystem::update and Emitter::fillInstanceData on the device (renderer/particle_system.cpp), for every
+// emitter of every registered system in a fixed number of launches per step.
+//
+//   k_particles_emit     ParticleSystem::emit (:411-452): one lane per new particle runs the emit program through the scalar interpreter.
+//   k_particles_commit   adds what was emitted to the device-resident counts (clamped to the reserved capacity: overflow bit).
+//   k_particles_chunk    processChunk (:1052-1375): one block per 1024-particle chunk, one lane per particle. The whole-chunk instructions
+//                        run per lane; CMP / CMP_ELSE blocks run per particle with the scalar interpreter's semantics (run, :684-1013) and
+//                        their kills land as the reference's sequential swap-with-last does. <false>: update program, <true>: output program.
+//   k_particles_plan     the head / tail compaction plan over the chunks' kill counts (:1518-1556): integer logic, one lane per emitter.
+//   k_particles_compact  the plan's copies: parallel over every channel.
+//   k_particles_subemit  sub-emission: the EMIT records a step staged, drained by k_particles_plan in the reference's order, run the target's emit program.
+//   k_particles_slices   the frame's slice offsets: a scan over ((count + 3) & ~3) * outputs_count * 4 bytes.
+//
+// The decoded program (lmx_particle_program.h) is wave-uniform outside conditional blocks: `ip` is a loop counter there and the records
+// come through scalar loads (the program is a kernel argument of its own, const and __restrict__: no store of the kernel can clobber it). The VM's registers are LDS pages of 1024 floats, indexed by lane (chunk-local: DESIGN §4.15 deviation 3).
+// Arithmetic is fp32 under -ffp-contract=off; MULTIPLY_ADD is a multiply and an add, MIX is a + (b - a) * c.
+#include "lmx_particles.h"
+
+namespace lmx {
+
+namespace {
+
+constexpr uint32_t MAP_PRE = 0x8000u; // s_map: the slot's content is the origin's value from BEFORE the block ran (the snapshot)
+
+__device__ __forceinline__ float bits_f(uint32_t u) { return __uint_as_float(u); }
+__device__ __forceinline__ uint32_t f_bits(float f) { return __float_as_uint(f); }
+
+// The reference's arithmetic is x86 SSE: an operation without a NaN operand that has no value (0 / 0, inf - inf, sqrt(-1), fmod(x, 0))
+// gives the negative default NaN 0xffc00000, and a NaN operand comes back quieted, the first one first. The VM's results are compared
+// bit for bit and feed sign-bit masks, so NaN results are put into that form (a compare and, on the rare path, two selects).
+__device__ __forceinline__ float nan_x86(float r, float a, float b) {
+	if (r != r) r = a != a ? bits_f(f_bits(a) | 0x00400000u) : b != b ? bits_f(f_bits(b) | 0x00400000u) : bits_f(0xffc00000u);
+	return r;
+}
+__device__ __forceinline__ float f_add(float a, float b) { return nan_x86(a + b, a, b); }
+__device__ __forceinline__ float f_sub(float a, float b) { return nan_x86(a - b, a, b); }
+__device__ __forceinline__ float f_mul(float a, float b) { return nan_x86(a * b, a, b); }
+__device__ __forceinline__ float f_div(float a, float b) { return nan_x86(a / b, a, b); }
+__device__ __forceinline__ float f_sqrt(float a) { return nan_x86(sqrtf(a), a, a); }
+#ifndef LMX_PARTICLE_NO_LIBM
+__device__ __forceinline__ float f_mod(float a, float b) { return nan_x86(fmodf(a, b), a, b); }
+__device__ __forceinline__ float f_sin(float a) { return nan_x86(sinf(a), a, a); }
+__device__ __forceinline__ float f_cos(float a) { return nan_x86(cosf(a), a, a); }
+#else // tests/test_isa_particle_kernels.py alone defines it (no build of the library does): without the library's fmod, sine and cosine expansions no fused multiply-add may be left
+__device__ __forceinline__ float f_mod(float a, float b) { return a - b; }
+__device__ __forceinline__ float f_sin(float a) { return a; }
+__device__ __forceinline__ float f_cos(float a) { return -a; }
+#endif
+
+// hash / gnoise of particle_system.cpp:320-338. u32(floor(p)) is x86-64's: through a signed 64-bit conversion, low word kept, 0 out of range.
+__device__ __forceinline__ float p_hash(uint32_t n) {
+	n = (n << 13U) ^ n;
+	n = n * (n * n * 15731U + 789221U) + 1376312589U;
+	return float(n & 0x0fffffffU) / 268435456.0f; // float(0x0ffFFffF) rounds to 2^28
+}
+__device__ __forceinline__ float p_gnoise(float p) {
+	const float fl = floorf(p);
+	uint32_t i = 0;
+	if (fabsf(fl) < 9223372036854775808.0f) i = (uint32_t)(uint64_t)(int64_t)fl;
+	const float f = f_sub(p, float(i));
+	const float u = f_mul(f_mul(f_mul(f, f), f), f_add(f_mul(f, f_sub(f_mul(f, 6.f), 15.f)), 10.f));
+	const float v0 = p_hash(i + 0u);
+	const float v1 = p_hash(i + 1u);
+	return f_mul(f_sub(f_add(f_mul(v0, f_sub(1.f, u)), f_mul(v1, u)), 0.5f), 4.8f);
+}
+
+__device__ __forceinline__ uint32_t p_mix(uint32_t x) {
+	x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+	return x;
+}
+// RAND: a counter-based draw keyed by (seed, emitter, step, particle, instruction ordinal) through RandomGenerator::randFloat's formula
+__device__ __forceinline__ float p_rand(uint32_t seed, uint32_t emitter, uint32_t step, uint32_t particle, uint32_t ordinal, float from, float to) {
+	uint32_t r = p_mix(seed ^ 0x9e3779b9u);
+	r = p_mix(r ^ emitter);
+	r = p_mix(r ^ step);
+	r = p_mix(r ^ particle);
+	r = p_mix(r ^ ordinal);
+	return from + float((to - from) * (r * 2.328306435996595e-10));
+}
+
+// What one lane of the VM sees
+struct Lane {
+	float* ch;            // channel 0, slot 0 of the emitter
+	uint32_t stride, slot;
+	float* regs;          // LDS register pages
+	uint32_t rstride, lane;
+	const float* sysv;
+	const float* globals;
+	float* outp;          // the particle's output row (output program only)
+	float total_time, emit_index; // the emit program's own TOTAL_TIME / EMIT_INDEX
+	bool emitting;
+	uint32_t seed, emitter, step;
+	uint32_t* stage;      // the emitter's staging records (update program with EMIT only)
+	uint32_t n_emit;
+};
+
+__device__ __forceinline__ float lane_read(const Lane& L, const ParticleOperand& o) {
+	switch (o.type) {
+		case PS_CHANNEL: return L.ch[(size_t)o.index * L.stride + L.slot];
+		case PS_REGISTER: return L.regs[o.index * L.rstride + L.lane];
+		case PS_SYSTEM_VALUE:
+			if (L.emitting && o.index == PSV_TOTAL_TIME) return L.total_time;
+			if (o.index == PSV_EMIT_INDEX) return L.emit_index;
+			return L.sysv[o.index];
+		case PS_GLOBAL: return L.globals[o.index];
+		case PS_OUT: return L.outp[o.index];
+		default: return o.value;
+	}
+}
+__device__ __forceinline__ void lane_write(const Lane& L, const ParticleOperand& o, float v) {
+	switch (o.type) {
+		case PS_CHANNEL: L.ch[(size_t)o.index * L.stride + L.slot] = v; break;
+		case PS_REGISTER: L.regs[o.index * L.rstride + L.lane] = v; break;
+		case PS_OUT: L.outp[o.index] = v; break;
+		default: break;
+	}
+}
+
+// ParticleSystem::run from record `ip` to the END that returns. True: the particle was killed.
+__device__ __forceinline__ bool run_scalar(Lane L, const ParticleRec* prog, uint32_t ip) {
+	bool killed = false;
+	float* const outp = L.outp;
+	for (;;) {
+		const ParticleRec& r = prog[ip];
+		uint32_t next = ip + 1;
+		switch (r.op) {
+			case P_END:
+				if (r.kind == PE_RETURN) return killed;
+				if (r.kind == PE_JUMP) next = r.a;
+				if (r.kind == PE_EMIT_END) L.outp = outp;
+				break;
+			case P_EMIT: { // the block behind it writes its outputs into the particle's staging record of this EMIT (run :958-983)
+				uint32_t* rec = L.stage + ((size_t)L.slot * L.n_emit + r.b) * PARTICLE_STAGE_WORDS;
+				rec[0] = 1u;
+				rec[1] = r.a;
+				for (uint32_t k = 0; k < 16; ++k) rec[2 + k] = 0u;
+				L.outp = reinterpret_cast<float*>(rec + 2);
+				break;
+			}
+			case P_KILL: killed = true; break;
+			case P_CMP: case P_CMP_ELSE:
+				if (!(lane_read(L, r.o[0]) != 0.0f)) next = r.a;
+				break;
+			case P_RAND: lane_write(L, r.o[0], p_rand(L.seed, L.emitter, L.step, L.slot, r.a, r.o[1].value, r.o[2].value)); break;
+			case P_MULTIPLY_ADD: lane_write(L, r.o[0], f_add(f_mul(lane_read(L, r.o[1]), lane_read(L, r.o[2])), lane_read(L, r.o[3]))); break;
+			case P_MIX: { // lerp of core/math.cpp:190
+				const float a = lane_read(L, r.o[1]), b = lane_read(L, r.o[2]), t = lane_read(L, r.o[3]);
+				lane_write(L, r.o[0], f_add(f_mul(a, f_sub(1.f, t)), f_mul(b, t)));
+				break;
+			}
+			case P_MOV: lane_write(L, r.o[0], lane_read(L, r.o[1])); break;
+			case P_SIN: lane_write(L, r.o[0], f_sin(lane_read(L, r.o[1]))); break;
+			case P_COS: lane_write(L, r.o[0], f_cos(lane_read(L, r.o[1]))); break;
+			case P_SQRT: lane_write(L, r.o[0], f_sqrt(lane_read(L, r.o[1]))); break;
+			case P_NOISE: lane_write(L, r.o[0], p_gnoise(lane_read(L, r.o[1]))); break;
+			case P_NOT: lane_write(L, r.o[0], bits_f(lane_read(L, r.o[1]) == 0.0f ? 0xffffffffu : 0u)); break;
+			default: {
+				const float a = lane_read(L, r.o[1]), b = lane_read(L, r.o[2]);
+				float v = 0.0f;
+				switch (r.op) {
+					case P_ADD: v = f_add(a, b); break;
+					case P_SUB: v = f_sub(a, b); break;
+					case P_MUL: v = f_mul(a, b); break;
+					case P_DIV: v = f_div(a, b); break;
+					case P_MOD: v = f_mod(a, b); break;
+					case P_AND: v = (a != 0.0f && b != 0.0f) ? 1.f : 0.f; break;
+					case P_OR: v = (a != 0.0f || b != 0.0f) ? 1.f : 0.f; break;
+					case P_MAX: v = a > b ? a : b; break;
+					case P_MIN: v = a < b ? a : b; break;
+					case P_LT: v = a < b ? 1.f : 0.f; break;
+					case P_GT: v = a > b ? 1.f : 0.f; break;
+					default: break;
+				}
+				lane_write(L, r.o[0], v);
+				break;
+			}
+		}
+		ip = next;
+	}
+}
+
+// One whole-chunk instruction for one lane (ProcessHelper::run1 / run2 / run3 and the cases of processChunk): the intrinsic form of core/simd.h
+__device__ __forceinline__ void run_whole(const Lane& L, const ParticleRec& r, const ParticleGradient* gradients) {
+	float v;
+	switch (r.op) {
+		case P_MOV: v = lane_read(L, r.o[1]); break;
+		case P_SIN: v = f_sin(lane_read(L, r.o[1])); break;
+		case P_COS: v = f_cos(lane_read(L, r.o[1])); break;
+		case P_SQRT: v = f_sqrt(lane_read(L, r.o[1])); break;
+		case P_NOISE: v = p_gnoise(lane_read(L, r.o[1])); break;
+		case P_RAND: v = p_rand(L.seed, L.emitter, L.step, L.slot, r.a, r.o[1].value, r.o[2].value); break;
+		case P_GRADIENT: {
+			const ParticleGradient& g = gradients[r.a];
+			const float arg = lane_read(L, r.o[1]);
+			const float lo = g.keys[0], hi = g.keys[g.count - 1];
+			const float m = arg > lo ? arg : lo;
+			const float c = m < hi ? m : hi;
+			uint32_t k = 1;
+			while (k + 1 < g.count && c > g.keys[k]) ++k;
+			v = f_sub(g.values[k], f_mul(f_sub(g.keys[k], c), g.ms[k]));
+			break;
+		}
+		case P_MULTIPLY_ADD: v = f_add(f_mul(lane_read(L, r.o[1]), lane_read(L, r.o[2])), lane_read(L, r.o[3])); break;
+		case P_MIX: {
+			const float a = lane_read(L, r.o[1]), b = lane_read(L, r.o[2]), c = lane_read(L, r.o[3]);
+			v = f_add(a, f_mul(f_sub(b, a), c));
+			break;
+		}
+		case P_BLEND: { // _mm_blendv_ps(false_val, true_val, mask): the mask's sign bit selects
+			const float fv = lane_read(L, r.o[1]), tv = lane_read(L, r.o[2]);
+			v = (f_bits(lane_read(L, r.o[3])) & 0x80000000u) ? tv : fv;
+			break;
+		}
+		default: {
+			const float a = lane_read(L, r.o[1]), b = lane_read(L, r.o[2]);
+			v = 0.0f;
+			switch (r.op) {
+				case P_ADD: v = f_add(a, b); break;
+				case P_SUB: v = f_sub(a, b); break;
+				case P_MUL: v = f_mul(a, b); break;
+				case P_DIV: v = f_div(a, b); break;
+				case P_MOD: v = f_mod(a, b); break;
+				case P_AND: v = bits_f(f_bits(a) & f_bits(b)); break;
+				case P_OR: v = bits_f(f_bits(a) | f_bits(b)); break;
+				case P_MAX: v = a > b ? a : b; break; // _mm_max_ps: the second operand when either is NaN
+				case P_MIN: v = a < b ? a : b; break;
+				case P_LT: v = bits_f(a < b ? 0xffffffffu : 0u); break;
+				case P_GT: v = bits_f(a > b ? 0xffffffffu : 0u); break;
+				default: break;
+			}
+			break;
+		}
+	}
+	lane_write(L, r.o[0], v);
+}
+
+__global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_emit(ParticlesDevice d, const ParticleEmitJob* __restrict__ jobs, const ParticleRec* __restrict__ prog) {
+	__shared__ float s_regs[PARTICLE_MAX_REGISTERS * PARTICLE_EMIT_BLOCK];
+	const ParticleEmitJob job = jobs[blockIdx.y];
+	const uint32_t i = blockIdx.x * PARTICLE_EMIT_BLOCK + threadIdx.x;
+	if (i >= job.count) return;
+	const ParticleEmitterDev em = d.emitters[job.emitter];
+	const ParticleStateDev st = d.state[job.emitter];
+	const uint32_t slot = st.count + i;
+	if (slot < st.count || slot >= em.capacity) return; // past the reserved capacity: counted by k_particles_commit, not written
+	for (uint32_t r = 0; r < PARTICLE_MAX_REGISTERS; ++r) s_regs[r * PARTICLE_EMIT_BLOCK + threadIdx.x] = 0.0f;
+	Lane L;
+	L.ch = d.channels + em.channel_base;
+	L.stride = em.stride;
+	L.slot = slot;
+	L.regs = s_regs;
+	L.rstride = PARTICLE_EMIT_BLOCK;
+	L.lane = threadIdx.x;
+	L.sysv = d.systems[em.system].values;
+	L.globals = d.globals + d.systems[em.system].globals_at;
+	L.outp = nullptr;
+	float t = job.total_time; // the reference's repeated sum c1 + d + d + ..., not c1 + i * d
+	if (job.time_step != 0.0f)
+		for (uint32_t k = 0; k < i; ++k) t += job.time_step;
+	L.total_time = t;
+	L.emit_index = float(st.emit_index + i);
+	L.emitting = true;
+	L.seed = d.seed; L.emitter = job.emitter; L.step = d.step;
+	L.stage = nullptr; L.n_emit = 0;
+	(void)run_scalar(L, prog, em.prog_emit);
+}
+
+__global__ void k_particles_commit(ParticlesDevice d, const ParticleEmitJob* __restrict__ jobs, uint32_t n_jobs) {
+	const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= n_jobs) return;
+	const ParticleEmitJob job = jobs[j];
+	ParticleStateDev st = d.state[job.emitter];
+	const uint32_t cap = d.emitters[job.emitter].capacity;
+	const uint32_t room = cap - st.count;
+	if (job.count > room) {
+		st.count = cap;
+		st.overflow = 1;
+	} else {
+		st.count += job.count;
+	}
+	st.emit_index += job.count;
+	d.state[job.emitter] = st;
+}
+
+template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particles_chunk(ParticlesDevice d, const ParticleRec* __restrict__ prog, const ParticleGradient* __restrict__ gradients) {
+	LMX_DYNAMIC_LDS(float, s_lds); // [registers][1024] register pages | [shadow channels][1024] | map[1024] | ballots[16 x 2] | kill count
+	const uint32_t e = blockIdx.y;
+	const ParticleStateDev st = d.state[e];
+	const uint32_t from = blockIdx.x * PARTICLE_CHUNK;
+	if (from >= st.count) return;
+	const ParticleEmitterDev em = d.emitters[e];
+	if (!FILL && d.level != 0xffffffffu && em.local != d.level) return;
+	const uint32_t n = min(PARTICLE_CHUNK, st.count - from), n4 = (n + 3u) & ~3u;
+	const uint32_t lane = threadIdx.x;
+	const bool active = lane < n4;
+	const uint32_t n_shadow = FILL ? 0u : (uint32_t)__popc(em.shadow_mask);
+	float* s_shadow = s_lds + em.registers * PARTICLE_CHUNK;
+	uint32_t* s_map = reinterpret_cast<uint32_t*>(s_shadow + n_shadow * PARTICLE_CHUNK);
+	uint32_t* s_ball = s_map + PARTICLE_CHUNK;
+	uint32_t* s_kc = s_ball + 32;
+	for (uint32_t r = 0; r < em.registers; ++r) s_lds[r * PARTICLE_CHUNK + lane] = 0.0f;
+	if (!FILL && lane == 0) d.kill[em.kill_base + blockIdx.x] = 0;
+
+	Lane L;
+	L.ch = d.channels + em.channel_base;
+	L.stride = em.stride;
+	L.slot = from + lane;
+	L.regs = s_lds;
+	L.rstride = PARTICLE_CHUNK;
+	L.lane = lane;
+	L.sysv = d.systems[em.system].values;
+	L.globals = d.globals + d.systems[em.system].globals_at;
+	L.outp = FILL ? d.frame + d.slices[e].offset / 4 + (size_t)(from + lane) * em.outputs : nullptr;
+	L.total_time = 0.0f;
+	L.emit_index = L.sysv[PSV_EMIT_INDEX];
+	L.emitting = false;
+	L.seed = d.seed; L.emitter = e; L.step = d.step;
+	L.stage = d.stage + em.stage_base;
+	L.n_emit = FILL ? 0u : em.n_emit;
+	if (active)
+		for (uint32_t j = 0; j < L.n_emit; ++j) L.stage[((size_t)L.slot * L.n_emit + j) * PARTICLE_STAGE_WORDS] = 0u;
+
+	uint32_t ip = FILL ? em.prog_output : em.prog_update;
+	for (;;) {
+		const ParticleRec& r = prog[ip];
+		const uint32_t op = r.op;
+		if (op == P_END) break;
+		if (op != P_CMP && op != P_CMP_ELSE) {
+			if (active) run_whole(L, r, gradients);
+			++ip;
+			continue;
+		}
+		// ---- a conditional block: per particle, then the kills in the reference's sequential order -----------------------------------
+		const bool has_else = op == P_CMP_ELSE, kills = !FILL && (r.b & 1u) != 0;
+		const uint32_t wmask = r.wmask;
+		if (kills && active) { // the values a killed slot takes from a slot the loop has not visited yet are those from before the block
+			uint32_t k = 0;
+			for (uint32_t m = wmask; m; m &= m - 1, ++k) s_shadow[k * PARTICLE_CHUNK + lane] = L.ch[(size_t)(__ffs((int)m) - 1) * L.stride + L.slot];
+		}
+		bool killed = false;
+		if (active) {
+			const bool is_true = (f_bits(lane_read(L, r.o[0])) & 0x80000000u) && lane < n; // f4MoveMask: the sign bit
+			if (is_true || has_else) killed = run_scalar(L, prog, is_true ? ip + 1 : r.a);
+		}
+		if (kills) {
+			const unsigned long long ball = __ballot(killed);
+			if ((lane & 63u) == 0) {
+				s_ball[2 * (lane >> 6)] = (uint32_t)ball;
+				s_ball[2 * (lane >> 6) + 1] = (uint32_t)(ball >> 32);
+			}
+			s_map[lane] = lane;
+			__syncthreads();
+			if (lane == 0) { // integer index logic only: `data[i] = data[last]; --last` for every kill, ascending
+				int32_t last = (int32_t)n - 1;
+				uint32_t kc = 0;
+				for (uint32_t w = 0; w < 32; ++w) {
+					for (uint32_t bits = s_ball[w]; bits; bits &= bits - 1) {
+						const int32_t i = (int32_t)(w * 32u) + __ffs((int)bits) - 1;
+						++kc;
+						if (last >= 0) { // (below the chunk the reference reads its neighbour: unspecified, nothing moves here)
+							if (last > i) s_map[i] = (uint32_t)last | MAP_PRE;
+							else if (last < i) s_map[i] = s_map[last];
+						}
+						--last;
+					}
+				}
+				*s_kc = kc;
+				if (kc) d.kill[em.kill_base + blockIdx.x] = kc;
+			}
+			__syncthreads();
+			if (*s_kc) {
+				const uint32_t mp = s_map[lane], src = mp & 0x3ffu;
+				const bool moved = active && mp != lane;
+				for (uint32_t c = 0; c < em.channels; ++c) {
+					float v = 0.0f;
+					if (moved) {
+						if ((mp & MAP_PRE) && ((wmask >> c) & 1u)) v = s_shadow[(uint32_t)__popc(wmask & ((1u << c) - 1u)) * PARTICLE_CHUNK + src];
+						else v = L.ch[(size_t)c * L.stride + from + src];
+					}
+					__syncthreads();
+					if (moved) L.ch[(size_t)c * L.stride + L.slot] = v;
+				}
+			}
+			__syncthreads(); // s_map / s_kc are rewritten by the next block
+		}
+		ip = r.c;
+	}
+}
+
+__global__ void k_particles_plan(ParticlesDevice d) {
+	const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+	if (e >= d.n_emitters) return;
+	ParticleStateDev st = d.state[e];
+	const ParticleEmitterDev& em = d.emitters[e]; // (read in place: emit_group is indexed by a loop counter)
+	if (d.level != 0xffffffffu && em.local != d.level) return;
+	uint32_t n_ops = 0, n_sub = 0;
+	const uint32_t updated = st.count; // what the chunk kernel ran over
+	st.killed = 0;
+	if (st.count) {
+		uint32_t* kc = d.kill + em.kill_base;
+		ParticleCopyOp* ops = d.ops + em.kill_base;
+		const uint32_t chunks = (st.count + PARTICLE_CHUNK - 1) / PARTICLE_CHUNK;
+		uint32_t head = 0, tail = chunks - 1, total = 0;
+		for (uint32_t i = 0; i < chunks; ++i) total += kc[i];
+		while (head != tail) {
+			const uint32_t kh = kc[head];
+			if (kh == 0) {
+				++head;
+				continue;
+			}
+			const uint32_t tail_start = PARTICLE_CHUNK * tail;
+			const uint32_t tail_count = min(PARTICLE_CHUNK, st.count - tail_start) - kc[tail];
+			ParticleCopyOp op;
+			op.dst = head * PARTICLE_CHUNK + PARTICLE_CHUNK - kh;
+			op.pad = 0;
+			if (tail_count <= kh) {
+				op.src = tail_start;
+				op.len = tail_count;
+				--tail;
+				kc[head] = kh - tail_count;
+			} else {
+				op.src = tail_start + tail_count - kh;
+				op.len = kh;
+				kc[tail] += kh;
+				++head;
+			}
+			// (kill counts beyond a chunk's particles are outside what the reference defines: such a copy is dropped, never out of bounds)
+			if (op.len && op.len <= PARTICLE_CHUNK && op.dst <= em.capacity - op.len && op.src <= em.capacity - op.len && n_ops < em.max_chunks) ops[n_ops++] = op;
+			if (tail_count > PARTICLE_CHUNK) break;
+		}
+		st.killed = total;
+		st.count = total < st.count ? st.count - total : 0;
+	}
+	// The drain of :1558-1571, integer part: the staged EMIT records in the reference's order - chunk by chunk, within a chunk conditional
+	// block by block, particle by particle - each takes init_emit_count slots of its target (past the capacity: counted, not written).
+	if (em.n_emit && updated) {
+		const uint32_t* stage = d.stage + em.stage_base;
+		ParticleSubJob* jobs = d.sub_jobs + em.job_base;
+		for (uint32_t from = 0; from < updated; from += PARTICLE_CHUNK) {
+			const uint32_t to4 = from + ((min(PARTICLE_CHUNK, updated - from) + 3u) & ~3u);
+			for (uint32_t j0 = 0; j0 < em.n_emit;) {
+				uint32_t j1 = j0 + 1;
+				while (j1 < em.n_emit && em.emit_group[j1] == em.emit_group[j0]) ++j1;
+				for (uint32_t p = from; p < to4; ++p)
+					for (uint32_t j = j0; j < j1; ++j) {
+						const uint32_t at = p * em.n_emit + j;
+						const uint32_t* rec = stage + (size_t)at * PARTICLE_STAGE_WORDS;
+						if (!rec[0]) continue;
+						const uint32_t t = em.first_of_system + rec[1];
+						ParticleStateDev ts = t == e ? st : d.state[t];
+						const uint32_t want = d.emitters[t].init_emit_count, room = d.emitters[t].capacity - ts.count;
+						ParticleSubJob job;
+						job.stage_index = at; job.target = t; job.slot = ts.count; job.emit_index = ts.emit_index; job.n = min(want, room);
+						if (want > room) ts.overflow = 1;
+						ts.count += job.n;
+						ts.emit_index += want;
+						if (t == e) st = ts;
+						else d.state[t] = ts;
+						jobs[n_sub++] = job;
+					}
+				j0 = j1;
+			}
+		}
+	}
+	d.n_ops[e] = n_ops;
+	d.n_sub[e] = n_sub;
+	d.state[e] = st;
+}
+
+// ParticleSystem::emit of every drained record: the target's emit program once per new particle, the record's outputs in its first registers,
+// time_step = 0
+__global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_subemit(ParticlesDevice d, const ParticleRec* __restrict__ prog) {
+	__shared__ float s_regs[PARTICLE_MAX_REGISTERS * PARTICLE_EMIT_BLOCK];
+	const uint32_t e = blockIdx.y;
+	const ParticleEmitterDev src = d.emitters[e];
+	if (!src.n_emit || (d.level != 0xffffffffu && src.local != d.level)) return;
+	const uint32_t n_sub = d.n_sub[e];
+	for (uint32_t r = blockIdx.x; r < n_sub; r += gridDim.x) {
+		const ParticleSubJob job = d.sub_jobs[src.job_base + r];
+		const ParticleEmitterDev em = d.emitters[job.target];
+		const float* in = reinterpret_cast<const float*>(d.stage + src.stage_base + (size_t)job.stage_index * PARTICLE_STAGE_WORDS + 2);
+		for (uint32_t i = threadIdx.x; i < job.n; i += PARTICLE_EMIT_BLOCK) {
+			for (uint32_t k = 0; k < PARTICLE_MAX_REGISTERS; ++k) s_regs[k * PARTICLE_EMIT_BLOCK + threadIdx.x] = k < em.emit_inputs ? in[k] : 0.0f;
+			Lane L;
+			L.ch = d.channels + em.channel_base;
+			L.stride = em.stride;
+			L.slot = job.slot + i;
+			L.regs = s_regs;
+			L.rstride = PARTICLE_EMIT_BLOCK;
+			L.lane = threadIdx.x;
+			L.sysv = d.systems[em.system].values;
+			L.globals = d.globals + d.systems[em.system].globals_at;
+			L.outp = nullptr;
+			L.total_time = L.sysv[PSV_TOTAL_TIME];
+			L.emit_index = float(job.emit_index + i);
+			L.emitting = true;
+			L.seed = d.seed; L.emitter = job.target; L.step = d.step;
+			L.stage = nullptr; L.n_emit = 0;
+			(void)run_scalar(L, prog, em.prog_emit);
+		}
+	}
+}
+
+__global__ void __launch_bounds__(PARTICLE_BLOCK) k_particles_compact(ParticlesDevice d) {
+	const uint32_t e = blockIdx.y;
+	const ParticleEmitterDev em = d.emitters[e];
+	if (d.level != 0xffffffffu && em.local != d.level) return;
+	if (blockIdx.x >= d.n_ops[e]) return;
+	const ParticleCopyOp op = d.ops[em.kill_base + blockIdx.x];
+	if (threadIdx.x >= op.len) return;
+	float* ch = d.channels + em.channel_base;
+	for (uint32_t c = 0; c < em.channels; ++c) ch[(size_t)c * em.stride + op.dst + threadIdx.x] = ch[(size_t)c * em.stride + op.src + threadIdx.x];
+}
+
+__global__ void __launch_bounds__(PARTICLE_SCAN_BLOCK) k_particles_slices(ParticlesDevice d) {
+	__shared__ uint32_t s_sum[PARTICLE_SCAN_BLOCK];
+	const uint32_t t = threadIdx.x;
+	const uint32_t per = (d.n_emitters + PARTICLE_SCAN_BLOCK - 1) / PARTICLE_SCAN_BLOCK;
+	const uint32_t first = min(t * per, d.n_emitters), end = min(first + per, d.n_emitters);
+	uint32_t mine = 0;
+	for (uint32_t e = first; e < end; ++e) mine += ((d.state[e].count + 3u) & ~3u) * d.emitters[e].outputs * 4u;
+	s_sum[t] = mine;
+	__syncthreads();
+	for (uint32_t step = 1; step < PARTICLE_SCAN_BLOCK; step <<= 1) {
+		const uint32_t add = t >= step ? s_sum[t - step] : 0u;
+		__syncthreads();
+		s_sum[t] += add;
+		__syncthreads();
+	}
+	uint32_t offset = s_sum[t] - mine;
+	for (uint32_t e = first; e < end; ++e) {
+		const uint32_t count = d.state[e].count, bytes = ((count + 3u) & ~3u) * d.emitters[e].outputs * 4u;
+		LmxParticleSlice s;
+		s.offset = offset; // a multiple of 16: every slice is a whole number of four-particle rows of floats
+		s.bytes = bytes;
+		s.particles = count;
+		s.outputs_count = d.emitters[e].outputs;
+		d.slices[e] = s;
+		offset += bytes;
+	}
+}
+
+} // namespace
+
+size_t particle_chunk_lds_bytes(uint32_t registers, uint32_t shadow_channels) {
+	return ((size_t)registers + shadow_channels + 1) * PARTICLE_CHUNK * sizeof(float) + 33 * sizeof(uint32_t);
+}
+
+hipError_t launch_particles_emit(hipStream_t s, const ParticlesDevice& d, const ParticleEmitJob* jobs, uint32_t n_jobs, uint32_t max_count) {
+	if (!n_jobs) return hipSuccess;
+	if (max_count) {
+		hipLaunchKernelGGL(k_particles_emit, dim3((max_count + PARTICLE_EMIT_BLOCK - 1) / PARTICLE_EMIT_BLOCK, n_jobs), dim3(PARTICLE_EMIT_BLOCK), 0, s, d, jobs, d.prog);
+		const hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(k_particles_commit, dim3((n_jobs + 255) / 256), dim3(256), 0, s, d, jobs, n_jobs);
+	return hipGetLastError();
+}
+
+template <bool FILL> static hipError_t launch_chunks(hipStream_t s, const ParticlesDevice& d, uint32_t max_chunks, size_t lds) {
+#ifndef LMX_HOSTSIM
+	if (lds > 64 * 1024) { // beyond the default limit of a launch's dynamic LDS (the CU holds 160 KiB)
+		const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_particles_chunk<FILL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+	}
+#endif
+	hipLaunchKernelGGL(k_particles_chunk<FILL>, dim3(max_chunks, d.n_emitters), dim3(PARTICLE_BLOCK), lds, s, d, d.prog, d.gradients);
+	return hipGetLastError();
+}
+
+hipError_t launch_particles_update(hipStream_t s, const ParticlesDevice& d, uint32_t max_chunks, uint32_t max_registers, uint32_t max_shadow, bool sub_emit) {
+	if (!d.n_emitters || !max_chunks) return hipSuccess;
+	hipError_t e = launch_chunks<false>(s, d, max_chunks, particle_chunk_lds_bytes(max_registers, max_shadow));
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k_particles_plan, dim3((d.n_emitters + 63) / 64), dim3(64), 0, s, d);
+	e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k_particles_compact, dim3(max_chunks, d.n_emitters), dim3(PARTICLE_BLOCK), 0, s, d);
+	e = hipGetLastError();
+	if (e != hipSuccess || !sub_emit) return e;
+	hipLaunchKernelGGL(k_particles_subemit, dim3(PARTICLE_SUB_BLOCKS, d.n_emitters), dim3(PARTICLE_EMIT_BLOCK), 0, s, d, d.prog);
+	return hipGetLastError();
+}
+
+hipError_t launch_particles_fill(hipStream_t s, const ParticlesDevice& d, uint32_t max_chunks, uint32_t max_registers) {
+	if (!d.n_emitters) return hipSuccess;
+	hipLaunchKernelGGL(k_particles_slices, dim3(1), dim3(PARTICLE_SCAN_BLOCK), 0, s, d);
+	const hipError_t e = hipGetLastError();
+	if (e != hipSuccess || !max_chunks) return e;
+	return launch_chunks<true>(s, d, max_chunks, particle_chunk_lds_bytes(max_registers, 0));
+}
+
+} // namespace lmx

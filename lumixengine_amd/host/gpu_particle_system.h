@@ -1,0 +1,123 @@
+// gpu_particle_system.h — the ParticleSystem::update / Emitter::fillInstanceData stand-in (C++ host side of include/lumix_mi355.h
+// "particle systems").
+//
+// In the reference RenderModuleImpl::updateParticleSystems calls ParticleSystem::update(dt, page_allocator) for every system and
+// Pipeline::setupParticles (src/renderer/pipeline.cpp:2212-2308) asks every emitter for getParticlesDataSizeBytes() and
+// fillInstanceData(slice.ptr, ...). GpuParticleSystems keeps the same names over lmx_particles_*: add() registers a ParticleSystem with the
+// programs of its resource, update(dt) advances all of them, fillInstanceData() fills every emitter's slice into one device buffer and
+// getEmitters(system) names the slices - offset, bytes, particle count on the device, nothing of it read back. Ribbons, applyTransform /
+// emit_move_distance, autodestroy, MESH / SPLINE programs and the sort-key pairs stay with the engine: add() returns false for a system it
+// cannot take and the engine keeps updating that one itself (a system refused at its programs keeps its index, with empty programs).
+//
+// `System` is ParticleSystem inside the engine (-DLMX_WITH_LUMIX_HEADERS); a standalone build passes any type with getResource(),
+// m_globals, m_world and m_entity (tests/cpp/lumix_compat_particles.h).
+#pragma once
+
+#include <vector>
+
+#include "lumix_mi355.h"
+
+#ifdef LMX_WITH_LUMIX_HEADERS
+	#include "core/math.h"
+	#include "engine/world.h"
+	#include "renderer/particle_system.h"
+#else
+	#include "lumix_compat.h"
+	#include "lumix_compat_particles.h"
+#endif
+
+namespace Lumix {
+
+struct GpuParticleSystems {
+	// What Pipeline::setupParticles needs of an emitter: where its slice lies in the frame buffer. `slice` is a DEVICE pointer into d_slices.
+	struct Emitter {
+		u32 global_index;              // into LmxParticlesDevice::d_slices / d_counts
+		u32 outputs_count;
+		const LmxParticleSlice* slice; // {offset, bytes = getParticlesDataSizeBytes(), particles} of the last fillInstanceData()
+	};
+
+	explicit GpuParticleSystems(LmxContext* ctx) : m_ctx(ctx) { lmx_particles_create(ctx, &m_ps); }
+	~GpuParticleSystems() { lmx_particles_destroy(m_ps); }
+	GpuParticleSystems(const GpuParticleSystems&) = delete;
+	void operator=(const GpuParticleSystems&) = delete;
+
+	// Registers `system` (its resource must be ready) with `capacity` particles per emitter. False: the system stays with the engine.
+	template <typename System> bool add(System& system, u32 capacity, u32* out_index = nullptr) {
+		auto* res = system.getResource();
+		if (!res || !res->isReady()) return false;
+		auto& emitters = res->getEmitters();
+		for (const auto& e : emitters)
+			if (e.max_ribbons > 0) return false; // ribbons: updateRibbons stays with the engine
+		u32 index = 0;
+		if (lmx_particles_add_system(m_ps, (u32)emitters.size(), (u32)system.m_globals.size(), &index) != LMX_OK) return false;
+		m_first.push_back((u32)m_emitters.size());
+		bool ok = true;
+		u32 k = 0;
+		for (const auto& e : emitters) {
+			LmxParticleProgram p;
+			p.instructions = (const uint8_t*)e.instructions.data();
+			p.size = (u32)e.instructions.size();
+			p.emit_offset = e.emit_offset; p.output_offset = e.output_offset;
+			p.channels_count = e.channels_count;
+			p.registers_count = e.update_registers_count > e.output_registers_count ? e.update_registers_count : e.output_registers_count;
+			if (e.emit_registers_count > p.registers_count) p.registers_count = e.emit_registers_count;
+			p.outputs_count = e.outputs_count; p.emit_inputs_count = e.emit_inputs_count;
+			p.init_emit_count = e.init_emit_count; p.emit_per_second = e.emit_per_second;
+			ok = ok && lmx_particles_set_program(m_ps, index, k, &p) == LMX_OK && lmx_particles_reserve(m_ps, index, k, capacity) == LMX_OK;
+			m_emitters.push_back(Emitter{(u32)m_emitters.size(), e.outputs_count, nullptr});
+			++k;
+		}
+		m_positions.resize(3 * (size_t)(index + 1));
+		if (out_index) *out_index = index;
+		if (!ok) { // a program was refused (MESH, SPLINE, malformed): the system stays registered but inert - empty programs, no capacity -
+			// so the others go on; the engine keeps updating this one itself
+			static const uint8_t nothing[3] = {0, 0, 0}; // END | END | END
+			LmxParticleProgram p = {};
+			p.instructions = nothing; p.size = 3; p.emit_offset = 1; p.output_offset = 2;
+			for (u32 e = 0; e < k; ++e) {
+				lmx_particles_set_program(m_ps, index, e, &p);
+				lmx_particles_reserve(m_ps, index, e, 0);
+			}
+		}
+		return ok;
+	}
+
+	// ParticleSystem::m_globals and World::getPosition(entity) of a registered system, before update()
+	template <typename System> bool sync(u32 index, System& system) {
+		const DVec3 pos = system.m_world.getPosition(EntityRef{system.m_entity.index});
+		m_positions[3 * (size_t)index] = pos.x; m_positions[3 * (size_t)index + 1] = pos.y; m_positions[3 * (size_t)index + 2] = pos.z;
+		return lmx_particles_set_globals(m_ps, index, system.m_globals.begin(), (u32)system.m_globals.size()) == LMX_OK;
+	}
+
+	// ParticleSystem::update(dt, page_allocator) of every registered system: enqueues and returns
+	bool update(float dt) {
+		if (lmx_particles_set_entity_positions(m_ps, (u32)(m_positions.size() / 3), m_positions.data()) != LMX_OK) return false;
+		return lmx_particles_step(m_ps, dt) == LMX_OK;
+	}
+
+	// Emitter::fillInstanceData of every emitter into the frame buffer: enqueues and returns; `out` names the buffer
+	bool fillInstanceData(LmxParticlesDevice& out) {
+		if (lmx_particles_fill(m_ps) != LMX_OK || lmx_particles_device_outputs(m_ps, &out) != LMX_OK) return false;
+		for (Emitter& e : m_emitters) e.slice = out.d_slices + e.global_index;
+		return true;
+	}
+
+	// ParticleSystem::getEmitters() of a registered system
+	Span<const Emitter> getEmitters(u32 index) const {
+		const u32 first = m_first[index], end = index + 1 < (u32)m_first.size() ? m_first[index + 1] : (u32)m_emitters.size();
+		return Span<const Emitter>(m_emitters.data() + first, (uint64_t)(end - first));
+	}
+
+	bool reset(u32 index) { return lmx_particles_reset(m_ps, index) == LMX_OK; } // ParticleSystem::reset
+	const char* lastError() const { return lmx_last_error(m_ctx); }
+	LmxParticles* handle() const { return m_ps; }
+
+private:
+	LmxContext* m_ctx;
+	LmxParticles* m_ps = nullptr;
+	std::vector<u32> m_first;
+	std::vector<Emitter> m_emitters;
+	std::vector<double> m_positions;
+};
+
+} // namespace Lumix
