@@ -272,6 +272,27 @@ typedef struct LmxBlendSample {
 	uint32_t looped;
 } LmxBlendSample;
 
+/* One instruction of an Animator's blend stack (anim::BlendStackInstructions, controller.h:58-62), in the controller's emission order. A
+ * SAMPLE record carries the fields of LmxBlendSample. An IK record is what evalBlendStack hands evalIK (controller.cpp:275-281): `alpha` is
+ * the caller's fp32 product alpha * RuntimeContext::weight, `leaf_bone` a bone index of the instance's model (LMX_BONE_NONE: the leaf was
+ * not found in the model - the instruction does nothing, :180-183), `bones_count` the chain length in [1, LMX_IK_MAX_BONES]. sizeof == 48. */
+#define LMX_BLEND_SAMPLE 1u
+#define LMX_BLEND_IK 2u
+#define LMX_BONE_NONE 0xffffffffu
+#define LMX_IK_MAX_BONES 32                  /* evalIK's MAX_BONES_COUNT, controller.cpp:171 */
+typedef struct LmxBlendInstr {
+	uint32_t op;                             /* LMX_BLEND_SAMPLE or LMX_BLEND_IK */
+	uint32_t animation;                      /* SAMPLE */
+	float weight;
+	uint32_t time;
+	uint32_t looped;
+	float alpha;                             /* IK */
+	float target[3];
+	uint32_t leaf_bone;
+	uint32_t bones_count;
+	uint32_t _pad;
+} LmxBlendInstr;
+
 #define LMX_TIME_ONE_SECOND (1u << 15)       /* Time::ONE_SECOND, animation/animation.h:41 */
 #define LMX_ANIM_NONE 0xffffffffu
 

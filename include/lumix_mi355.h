@@ -37,7 +37,7 @@ enum {
 	LMX_ERR_CAPACITY = 5,      /* caller buffer too small / too many views, frusta or types */
 	LMX_ERR_NOT_BUILT = 6,     /* operation needs data that has not been uploaded yet */
 	LMX_ERR_BUSY = 7,          /* every result slot is held by a caller that has not released it (lmx_cull_view_acquire timed out) */
-	LMX_ERR_INVALID = 8,       /* a particle program that is malformed or could leave a buffer (lmx_particles_set_program) */
+	LMX_ERR_INVALID = 8,       /* a particle program that is malformed or could leave a buffer (lmx_particles_set_program); a malformed blend stack (lmx_anim_decode_blend_stack) */
 	LMX_ERR_UNSUPPORTED = 9    /* a well-formed request for something this library does not run on the device */
 };
 
@@ -452,9 +452,28 @@ LMX_API int lmx_anim_update(LmxContext* ctx, float time_delta);
  * into the pose, then evalBlendStack's SAMPLE instructions in order (controller.cpp:267-293, getPose :142-157) - instance i owns
  * samples[first_sample[i] .. first_sample[i + 1]), first_sample has n_instances + 1 entries. An instruction whose animation does not
  * fit the instance's skeleton is skipped, as Animation::getRelativePose does (animation.cpp:120). The controller's node graph that
- * emits the instructions, bone masks and IK instructions stay on the CPU / out of scope. lmx_skin_run then does
- * Pose::computeAbsolute and the palette. Host arrays; copied before the call returns. */
+ * emits the instructions stays on the CPU; bone masks are dead code in the reference (animation.cpp:139-142); programs that hold IK
+ * instructions go through lmx_anim_eval_blend_instrs below. lmx_skin_run then does Pose::computeAbsolute and the palette. Host arrays;
+ * copied before the call returns. */
 LMX_API int lmx_anim_eval_blend_stacks(LmxContext* ctx, uint32_t n_instances, const uint32_t* first_sample, const LmxBlendSample* samples);
+/* The same with everything evalBlendStack can execute: SAMPLE and IK instructions (evalIK, controller.cpp:166-265: FABRIK over the
+ * `bones_count` bones that end in `leaf_bone`, five iterations, rotations rebuilt with Quat::vec3ToVec3, blended into the pose with
+ * alpha), run in order per instance - an IK sees the pose the earlier instructions left, a later SAMPLE blends over what IK wrote.
+ * Instance i owns instrs[first_instr[i] .. first_instr[i + 1]). Bit-exact with the reference's scalar fp32. Everything is validated
+ * before the launch (the kernel carries no checks): LMX_ERR_INVALID_ARGUMENT, and the pose buffers untouched, for every rule of
+ * lmx_anim_eval_blend_stacks on a SAMPLE record, an unknown op, bones_count == 0 or > LMX_IK_MAX_BONES, leaf_bone >= the model's bone
+ * count (other than LMX_BONE_NONE), a leaf with fewer than bones_count - 1 ancestors (the reference would index the pose with -1), a
+ * non-finite alpha or target. Host arrays; copied before the call returns. */
+LMX_API int lmx_anim_eval_blend_instrs(LmxContext* ctx, uint32_t n_instances, const uint32_t* first_instr, const LmxBlendInstr* instrs);
+/* RuntimeContext::blendstack as the controller's nodes write it (controller.cpp:267-293), decoded into LmxBlendInstr records. Bytes:
+ * u8 op (0 END, 1 SAMPLE, 2 IK); SAMPLE: u32 slot, f32 weight, u32 time, u8 looped; IK: f32 alpha, 3 x f32 target, u64 leaf bone name
+ * hash, u32 bone count. `slot_animation[slot]` is the id lmx_anim_add returned for RuntimeContext::animations[slot] (LMX_ANIM_NONE: empty
+ * slot), `bone_hashes` the model's n_bones bone name hashes in bone order, `weight` RuntimeContext::weight (an IK record's alpha is
+ * alpha * weight). A hash that is not in the table gives leaf_bone = LMX_BONE_NONE. LMX_ERR_INVALID: a slot outside the table or empty, a
+ * truncated instruction, no END, an unknown op. LMX_ERR_CAPACITY: more than `capacity` instructions. Bytes behind END are ignored.
+ * Pure host code: no context, no allocation, no read outside [bytes, bytes + n_bytes). */
+LMX_API int lmx_anim_decode_blend_stack(const uint8_t* bytes, uint64_t n_bytes, const uint32_t* slot_animation, uint32_t n_slots, const uint64_t* bone_hashes,
+	uint32_t n_bones, float weight, LmxBlendInstr* out_instrs, uint32_t capacity, uint32_t* out_count);
 LMX_API int lmx_anim_read_times(LmxContext* ctx, uint32_t* time, uint32_t n_instances);
 /* The relative pose of an instance after lmx_anim_update (before lmx_skin_run turns it into the absolute one). */
 LMX_API int lmx_anim_read_pose(LmxContext* ctx, uint32_t instance, float* out_pos, float* out_rot, uint32_t cap_bones);

@@ -46,6 +46,9 @@ ANIM_CONST_TRANSLATION = np.dtype([("value", "<f4", 3), ("bone_index", "<u2"), (
 ANIM_TRANSLATION_TRACK = np.dtype([("min", "<f4", 3), ("to_range", "<f4", 3), ("offset_bits", "<u2"), ("bone_index", "<u2"), ("bitsizes", "u1", 3), ("_pad", "u1")], align=True)
 ANIM_CONST_ROTATION = np.dtype([("value", "<f4", 4), ("bone_index", "<u2"), ("_pad", "<u2")], align=True)
 BLEND_SAMPLE = np.dtype([("animation", "<u4"), ("weight", "<f4"), ("time", "<u4"), ("looped", "<u4")], align=True)  # LmxBlendSample
+BLEND_INSTR = np.dtype([("op", "<u4"), ("animation", "<u4"), ("weight", "<f4"), ("time", "<u4"), ("looped", "<u4"), ("alpha", "<f4"), ("target", "<f4", 3),
+                        ("leaf_bone", "<u4"), ("bones_count", "<u4"), ("_pad", "<u4")], align=True)  # LmxBlendInstr
+BLEND_SAMPLE_OP, BLEND_IK_OP, BONE_NONE, IK_MAX_BONES, ANIM_NONE = 1, 2, 0xFFFFFFFF, 32, 0xFFFFFFFF  # LMX_BLEND_*, LMX_BONE_NONE, LMX_IK_MAX_BONES, LMX_ANIM_NONE
 ANIM_ROTATION_TRACK = np.dtype([("min", "<f4", 3), ("to_range", "<f4", 3), ("offset_bits", "<u2"), ("bone_index", "<u2"), ("bitsizes", "u1", 3), ("skipped_channel", "u1")],
                                align=True)
 
@@ -256,6 +259,8 @@ SYMBOLS = {
     "lmx_anim_set_weight": (_ci, [_vp, _f32]),
     "lmx_anim_update": (_ci, [_vp, _f32]),
     "lmx_anim_eval_blend_stacks": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_anim_eval_blend_instrs": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_anim_decode_blend_stack": (_ci, [_vp, C.c_uint64, _vp, _u32, _vp, _u32, C.c_float, _vp, _u32, _vp]),
     "lmx_anim_read_times": (_ci, [_vp, _vp, _u32]),
     "lmx_anim_read_pose": (_ci, [_vp, _u32, _vp, _vp, _u32]),
     "lmx_keys_set_models": (_ci, [_vp, _vp, _u32, _vp, _u32]),
@@ -1673,6 +1678,46 @@ class Skinning:
                 k += 1
         self._n_animables = len(stacks)
         self.ctx.check(self.lib.lmx_anim_eval_blend_stacks(self.ctx.h, len(stacks), _ptr(first), _ptr(samples)))
+
+    def evalBlendInstrs(self, programs):
+        """evalBlendStack for every instance, IK included (lmx_anim_eval_blend_instrs): `programs[i]` = instance i's instructions in order,
+        each ("sample", animation id, weight, time, looped) or ("ik", alpha, target xyz, leaf bone index or BONE_NONE, bones_count) - or a
+        BLEND_INSTR array, as decodeBlendStack returns."""
+        first = np.zeros(len(programs) + 1, np.uint32)
+        first[1:] = np.cumsum([len(p) for p in programs])
+        instrs = np.zeros(max(int(first[-1]), 1), BLEND_INSTR)
+        k = 0
+        for p in programs:
+            if isinstance(p, np.ndarray):
+                instrs[k : k + len(p)] = p
+                k += len(p)
+                continue
+            for ins in p:
+                if ins[0] == "sample":
+                    instrs[k]["op"], instrs[k]["animation"], instrs[k]["weight"], instrs[k]["time"], instrs[k]["looped"] = BLEND_SAMPLE_OP, ins[1], ins[2], ins[3], 1 if ins[4] else 0
+                elif ins[0] == "ik":
+                    instrs[k]["op"], instrs[k]["alpha"], instrs[k]["target"], instrs[k]["leaf_bone"], instrs[k]["bones_count"] = BLEND_IK_OP, ins[1], ins[2], ins[3], ins[4]
+                else:
+                    instrs[k]["op"] = int(ins[0])  # (an unknown op, passed through for the library to refuse)
+                k += 1
+        self._n_animables = len(programs)
+        self.ctx.check(self.lib.lmx_anim_eval_blend_instrs(self.ctx.h, len(programs), _ptr(first), _ptr(instrs)))
+
+    @staticmethod
+    def decodeBlendStack(blendstack: bytes, slot_animation, bone_hashes, weight: float = 1.0, capacity: int = 64) -> np.ndarray:
+        """RuntimeContext::blendstack bytes -> BLEND_INSTR records (lmx_anim_decode_blend_stack; host only, no context). `slot_animation[slot]`
+        = the library's animation id of RuntimeContext::animations[slot] (ANIM_NONE: empty), `bone_hashes` = the model's bone name hashes."""
+        lib = load_library()
+        raw = np.frombuffer(bytes(blendstack), np.uint8)
+        slots = np.ascontiguousarray(slot_animation, np.uint32)
+        hashes = np.ascontiguousarray(bone_hashes, np.uint64)
+        out = np.zeros(max(capacity, 1), BLEND_INSTR)
+        n = C.c_uint32(0)
+        rc = lib.lmx_anim_decode_blend_stack(_ptr(raw) if len(raw) else None, len(raw), _ptr(slots) if len(slots) else None, len(slots),
+                                             _ptr(hashes) if len(hashes) else None, len(hashes), float(weight), _ptr(out), int(capacity), C.byref(n))
+        if rc != 0:
+            raise LumixError(rc, "the blend stack could not be decoded")
+        return out[: n.value].copy()
 
     def readTimes(self) -> np.ndarray:
         out = np.zeros(self._n_animables, np.uint32)

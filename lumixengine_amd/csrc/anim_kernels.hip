@@ -163,7 +163,7 @@ __global__ __launch_bounds__(64) void k_anim_update(const SkinInstance* __restri
 // updateAnimator's pose work for one Animator per block (animation_module.cpp:602-636): Model::getRelativePose into the pose, then
 // evalBlendStack's SAMPLE instructions in order (controller.cpp:267-293; getPose :142-157 wraps or clamps the time, then
 // Animation::getRelativePose with the instruction's weight). A bone's tracks of different layers only meet in that bone, so a lane
-// carries its bone through every layer in registers and the pose is written once. IK instructions are not on the path.
+// carries its bone through every layer in registers and the pose is written once. Programs with IK instructions: k_anim_blend_instrs.
 __global__ __launch_bounds__(64) void k_anim_blend_stack(const SkinInstance* __restrict__ inst, uint32_t n_inst, const AnimDevice* __restrict__ anims, AnimTables t,
 	uint32_t n_anims, const LmxBlendSample* __restrict__ samples, const uint32_t* __restrict__ first_sample, const float* __restrict__ model_rel_pos,
 	const float4* __restrict__ model_rel_rot, float* __restrict__ pose_pos, float4* __restrict__ pose_rot) {
@@ -200,7 +200,189 @@ __global__ __launch_bounds__(64) void k_anim_blend_stack(const SkinInstance* __r
 	}
 }
 
+// ---- evalBlendStack with IK (controller.cpp:267-293, evalIK :166-265) ----
+// The chain of one IK instruction, in LDS: every array is indexed by run-time values (private arrays would go to scratch).
+struct IkChain {
+	uint32_t indices[LMX_IK_MAX_BONES];
+	V3 pos[LMX_IK_MAX_BONES];     // transforms[i].pos
+	Q4 rot[LMX_IK_MAX_BONES];     // transforms[i].rot
+	V3 old_pos[LMX_IK_MAX_BONES];
+	float len[LMX_IK_MAX_BONES];
+	V3 out_pos[LMX_IK_MAX_BONES]; // ik_out
+	Q4 out_rot[LMX_IK_MAX_BONES];
+	uint16_t ancestors[LMX_MAX_BONES]; // the chain root's parent and its ancestors, nearest first
+};
+
+__device__ __forceinline__ Q4 q4_of(float4 v) { return Q4{v.x, v.y, v.z, v.w}; }
+__device__ __forceinline__ float4 f4_of(Q4 q) { return make_float4(q.x, q.y, q.z, q.w); }
+
+// evalIK up to ik_out (controller.cpp:174-258), one lane: the FABRIK passes are serial recurrences along the chain. `pp` / `pr`: the
+// instance's relative pose in LDS as the earlier instructions left it; `parents`: the model's bone parents. Validated by the host:
+// 1 <= n <= LMX_IK_MAX_BONES, the leaf is a bone of the model with at least n - 1 ancestors.
+__device__ __forceinline__ void ik_solve(const LmxBlendInstr& ins, const int16_t* __restrict__ parents, const V3* pp, const float4* pr, IkChain& c) {
+	const uint32_t n = ins.bones_count;
+	V3 target = V3{ins.target[0], ins.target[1], ins.target[2]};
+	c.indices[n - 1] = ins.leaf_bone;
+	for (uint32_t i = 1; i < n; ++i) c.indices[n - 1 - i] = (uint32_t)parents[c.indices[n - i]];
+	// getAbsolutePosition(first_bone_parent), :159-164: the recursion composes root-down, ((root * b1) * b2) ...
+	const int32_t first_bone_parent = parents[c.indices[0]];
+	Rigid roots_parent = Rigid{V3{0, 0, 0}, Q4{0, 0, 0, 1}};
+	if (first_bone_parent >= 0) {
+		uint32_t depth = 0;
+		for (int32_t b = first_bone_parent; b >= 0; b = parents[b]) c.ancestors[depth++] = (uint16_t)b;
+		roots_parent = Rigid{pp[c.ancestors[depth - 1]], q4_of(pr[c.ancestors[depth - 1]])};
+		for (uint32_t k = depth - 1; k-- > 0;) {
+			const uint32_t b = c.ancestors[k];
+			roots_parent = rigid_mul(roots_parent, Rigid{pp[b], q4_of(pr[b])});
+		}
+	}
+	Rigid parent_tr = roots_parent;
+	float len_sum = 0;
+	for (uint32_t i = 0; i < n; ++i) { // :201-210
+		const uint32_t b = c.indices[i];
+		const Rigid tr = rigid_mul(parent_tr, Rigid{pp[b], q4_of(pr[b])});
+		c.pos[i] = tr.pos;
+		c.rot[i] = tr.rot;
+		c.old_pos[i] = tr.pos;
+		if (i > 0) {
+			c.len[i - 1] = length(sub(tr.pos, parent_tr.pos));
+			len_sum += c.len[i - 1];
+		}
+		parent_tr = tr;
+	}
+	V3 to_target = sub(target, c.pos[0]); // :212-216
+	if (len_sum * len_sum < squared_length(to_target)) {
+		to_target = normalize(to_target);
+		target = add(c.pos[0], mul(to_target, len_sum));
+	}
+	for (uint32_t iteration = 0; iteration < 5; ++iteration) { // max_iterations, :170
+		c.pos[n - 1] = target;
+		for (int32_t i = (int32_t)n - 1; i > 1; --i) {
+			const V3 dir = normalize(sub(c.pos[i - 1], c.pos[i]));
+			c.pos[i - 1] = add(c.pos[i], mul(dir, c.len[i - 1]));
+		}
+		for (uint32_t i = 1; i < n; ++i) {
+			const V3 dir = normalize(sub(c.pos[i], c.pos[i - 1]));
+			c.pos[i] = add(c.pos[i - 1], mul(dir, c.len[i - 1]));
+		}
+	}
+	for (int32_t i = (int32_t)n - 2; i >= 0; --i) { // rotations from the new positions, :233-239
+		const V3 old_d = sub(c.old_pos[i + 1], c.old_pos[i]);
+		const V3 new_d = sub(c.pos[i + 1], c.pos[i]);
+		c.rot[i] = qmul(vec3_to_vec3(old_d, new_d), c.rot[i]);
+	}
+	for (int32_t i = (int32_t)n - 1; i > 0; --i) { // object space back to bone space, :243-249 (transforms[i - 1] is still absolute)
+		const Rigid local = rigid_mul(rigid_inverted(Rigid{c.pos[i - 1], c.rot[i - 1]}), Rigid{c.pos[i], c.rot[i]});
+		c.pos[i] = local.pos;
+		c.rot[i] = local.rot;
+		c.out_pos[i] = local.pos;
+		c.out_rot[i] = local.rot;
+	}
+	c.out_rot[n - 1] = q4_of(pr[c.indices[n - 1]]);
+	c.out_rot[0] = first_bone_parent >= 0 ? qmul(conjugated(roots_parent.rot), c.rot[0]) : c.rot[0];
+	c.out_pos[0] = pp[c.indices[0]];
+}
+
+// One Animator per 64-lane block, every instruction of its program in order. A program without IK takes k_anim_blend_stack's
+// register-carried path (a block-uniform branch). One with IK stages the relative pose in LDS (<= 196 bones x 28 B), since evalIK
+// reads other lanes' bones: the loop is instruction-major over all 64-bone tiles, SAMPLE updates a lane's bones in LDS, IK runs the
+// serial solve in lane 0 and blends the chain bones with a lane each. __syncthreads() orders the lanes through LDS (one wave per block).
+__global__ __launch_bounds__(64) void k_anim_blend_instrs(const SkinInstance* __restrict__ inst, uint32_t n_inst, const AnimDevice* __restrict__ anims, AnimTables t,
+	uint32_t n_anims, const LmxBlendInstr* __restrict__ instrs, const uint32_t* __restrict__ first_instr, const int16_t* __restrict__ parents,
+	const float* __restrict__ model_rel_pos, const float4* __restrict__ model_rel_rot, float* __restrict__ pose_pos, float4* __restrict__ pose_rot) {
+	const uint32_t ii = blockIdx.x;
+	if (ii >= n_inst) return;
+	const SkinInstance in = inst[ii];
+	const uint32_t s0 = first_instr[ii], s1 = first_instr[ii + 1];
+	bool has_ik = false;
+	for (uint32_t s = s0; s < s1; ++s) has_ik = has_ik || instrs[s].op == LMX_BLEND_IK;
+	if (!has_ik) {
+		for (uint32_t b0 = 0; b0 < in.n_bones; b0 += 64) {
+			const uint32_t b = b0 + threadIdx.x;
+			const bool live = b < in.n_bones;
+			V3 p = V3{0, 0, 0};
+			float4 r = make_float4(0, 0, 0, 1);
+			if (live) { // Model::getRelativePose, model.cpp:226-237
+				const float* mp = model_rel_pos + 3 * (size_t)(in.model_offset + b);
+				p = V3{mp[0], mp[1], mp[2]};
+				r = model_rel_rot[in.model_offset + b];
+			}
+			for (uint32_t s = s0; s < s1; ++s) {
+				const LmxBlendInstr ins = instrs[s];
+				if (ins.animation >= n_anims) continue;
+				const AnimDevice a = anims[ins.animation];
+				if (a.max_bone >= in.n_bones) continue; // skeletons do not match, animation.cpp:120
+				const uint32_t time = ins.looped ? ins.time % a.length : (ins.time < a.length ? ins.time : a.length); // controller.cpp:148
+				uint32_t sample_idx;
+				float f;
+				anim_sample_point(a, time, sample_idx, f);
+				if (live && b <= a.max_bone) anim_apply_bone(a, t, b, sample_idx, f, ins.weight, p, r);
+			}
+			if (live) {
+				float* gp = pose_pos + 3 * (size_t)(in.bone_offset + b);
+				gp[0] = p.x; gp[1] = p.y; gp[2] = p.z;
+				pose_rot[in.bone_offset + b] = r;
+			}
+		}
+		return;
+	}
+	__shared__ V3 s_pos[LMX_MAX_BONES];
+	__shared__ float4 s_rot[LMX_MAX_BONES];
+	__shared__ IkChain s_chain;
+	for (uint32_t b = threadIdx.x; b < in.n_bones; b += 64) { // Model::getRelativePose
+		const float* mp = model_rel_pos + 3 * (size_t)(in.model_offset + b);
+		s_pos[b] = V3{mp[0], mp[1], mp[2]};
+		s_rot[b] = model_rel_rot[in.model_offset + b];
+	}
+	__syncthreads();
+	const int16_t* model_parents = parents + in.model_offset;
+	for (uint32_t s = s0; s < s1; ++s) {
+		const LmxBlendInstr ins = instrs[s];
+		if (ins.op == LMX_BLEND_SAMPLE) {
+			if (ins.animation >= n_anims) continue;
+			const AnimDevice a = anims[ins.animation];
+			if (a.max_bone >= in.n_bones) continue;
+			const uint32_t time = ins.looped ? ins.time % a.length : (ins.time < a.length ? ins.time : a.length);
+			uint32_t sample_idx;
+			float f;
+			anim_sample_point(a, time, sample_idx, f);
+			for (uint32_t b = threadIdx.x; b <= a.max_bone; b += 64) { // a lane touches its own bones only
+				V3 p = s_pos[b];
+				float4 r = s_rot[b];
+				anim_apply_bone(a, t, b, sample_idx, f, ins.weight, p, r);
+				s_pos[b] = p;
+				s_rot[b] = r;
+			}
+			__syncthreads(); // a following IK reads every lane's bones
+		} else {
+			if (ins.alpha < 0.001f || ins.leaf_bone == LMX_BONE_NONE) continue; // controller.cpp:167, :180-183
+			if (threadIdx.x == 0) ik_solve(ins, model_parents, s_pos, s_rot, s_chain);
+			__syncthreads();
+			if (threadIdx.x < ins.bones_count) { // :260-264, a lane per chain bone (the chain's bones are distinct)
+				const uint32_t idx = s_chain.indices[threadIdx.x];
+				s_pos[idx] = lerp(s_pos[idx], s_chain.out_pos[threadIdx.x], ins.alpha);
+				s_rot[idx] = f4_of(nlerp(q4_of(s_rot[idx]), s_chain.out_rot[threadIdx.x], ins.alpha));
+			}
+			__syncthreads();
+		}
+	}
+	for (uint32_t b = threadIdx.x; b < in.n_bones; b += 64) {
+		float* gp = pose_pos + 3 * (size_t)(in.bone_offset + b);
+		gp[0] = s_pos[b].x; gp[1] = s_pos[b].y; gp[2] = s_pos[b].z;
+		pose_rot[in.bone_offset + b] = s_rot[b];
+	}
+}
+
 } // namespace
+
+hipError_t launch_anim_blend_instrs(hipStream_t s, const SkinInstance* inst, uint32_t n_inst, const AnimDevice* anims, const AnimTables& t, uint32_t n_anims,
+	const LmxBlendInstr* instrs, const uint32_t* first_instr, const int16_t* parents, const float* model_rel_pos, const float4* model_rel_rot, float* pose_pos,
+	float4* pose_rot) {
+	if (!n_inst) return hipSuccess;
+	hipLaunchKernelGGL(k_anim_blend_instrs, dim3(n_inst), dim3(64), 0, s, inst, n_inst, anims, t, n_anims, instrs, first_instr, parents, model_rel_pos, model_rel_rot,
+		pose_pos, pose_rot);
+	return hipGetLastError();
+}
 
 hipError_t launch_anim_update(hipStream_t s, const SkinInstance* inst, uint32_t n_inst, const AnimDevice* anims, const AnimTables& t,
 	const uint32_t* anim_of_instance, uint32_t* time_of_instance, float time_delta, float weight, const float* model_rel_pos,

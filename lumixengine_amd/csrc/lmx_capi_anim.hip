@@ -1,6 +1,8 @@
 // lmx_capi_anim.hip — animation sampling entry points (include/lumix_mi355.h, "animation" section): Animation resources are
 // flattened into concatenated device tables, every skinned instance is an Animable {animation, time}, and lmx_anim_update is
 // AnimationModuleImpl::updateAnimable for all of them at once; its output is the relative pose lmx_skin_run consumes.
+#include <cmath>
+
 #include "lmx_context.h"
 
 using namespace lmx;
@@ -203,6 +205,81 @@ int lmx_anim_eval_blend_stacks(LmxContext* ctx, uint32_t n_instances, const uint
 	ProfScope ps(ctx, LMX_K_ANIM_UPDATE);
 	LMX_HIP(ctx, launch_anim_blend_stack(ctx->stream, sk.d_inst.p, (uint32_t)sk.inst.size(), an.d_anims.p, t, (uint32_t)an.anims.size(), an.d_samples.p,
 		an.d_first_sample.p, an.d_rel_pos.p, an.d_rel_rot.p, sk.d_pose_pos.p, sk.d_pose_rot.p));
+	sk.borrowed_pos = nullptr;
+	sk.borrowed_rot = nullptr;
+	sk.poses_uploaded = true;
+	sk.pose_is_absolute = false;
+	return LMX_OK;
+}
+
+int lmx_anim_eval_blend_instrs(LmxContext* ctx, uint32_t n_instances, const uint32_t* first_instr, const LmxBlendInstr* instrs) {
+	LMX_CHECK_CTX(ctx);
+	SkinState& sk = ctx->skin;
+	AnimState& an = ctx->anim;
+	if (n_instances != sk.inst.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "the skin instance table has %zu instances", sk.inst.size());
+	if (!n_instances) return LMX_OK;
+	if (!first_instr) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null first_instr");
+	if (an.rel_rot.size() != sk.parents.size()) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_anim_set_model_pose is missing for a model added later");
+	for (uint32_t i = 0; i < n_instances; ++i)
+		if (first_instr[i + 1] < first_instr[i]) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "first_instr decreases at instance %u", i);
+	const uint32_t n_instrs = first_instr[n_instances];
+	if (first_instr[0] != 0 || (n_instrs && !instrs)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "first_instr[0] must be 0 and instrs non-null");
+	// the kernel carries no checks of its own: everything it indexes with is validated here
+	// (one pass over the records: a call without IK runs k_anim_blend_stack on the SAMPLE fields, gathered here into their 16-byte form)
+	bool any_ik = false;
+	an.samples_scratch.resize(n_instrs);
+	for (uint32_t i = 0; i < n_instances; ++i) {
+		for (uint32_t k = first_instr[i]; k < first_instr[i + 1]; ++k) {
+			const LmxBlendInstr& ins = instrs[k];
+			if (ins.op == LMX_BLEND_SAMPLE) {
+				if (ins.animation >= an.anims.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instruction %u: unknown animation %u", k, ins.animation);
+				if (!(ins.weight >= 0.f && ins.weight <= 1.f)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instruction %u: weight %g outside [0, 1]", k, (double)ins.weight);
+				if (!any_ik) an.samples_scratch[k] = LmxBlendSample{ins.animation, ins.weight, ins.time, ins.looped};
+			} else if (ins.op == LMX_BLEND_IK) {
+				const SkinInstance& in = sk.inst[i];
+				any_ik = true;
+				if (!std::isfinite(ins.alpha) || !std::isfinite(ins.target[0]) || !std::isfinite(ins.target[1]) || !std::isfinite(ins.target[2]))
+					return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instruction %u: non-finite IK alpha or target", k);
+				if (!ins.bones_count || ins.bones_count > LMX_IK_MAX_BONES)
+					return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instruction %u: IK bones_count %u not in [1, %d] (MAX_BONES_COUNT, controller.cpp:171)", k, ins.bones_count, LMX_IK_MAX_BONES);
+				if (ins.leaf_bone == LMX_BONE_NONE) continue; // leaf not found: the instruction does nothing (controller.cpp:180-183)
+				if (ins.leaf_bone >= in.n_bones) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instruction %u: IK leaf bone %u, the model of instance %u has %u bones", k, ins.leaf_bone, i, in.n_bones);
+				int32_t b = (int32_t)ins.leaf_bone;
+				for (uint32_t up = 1; up < ins.bones_count; ++up) {
+					b = sk.parents[in.model_offset + (uint32_t)b];
+					if (b < 0) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instruction %u: IK chain of %u bones walks past the root (bone %u has %u ancestors)", k, ins.bones_count, ins.leaf_bone, up - 1);
+				}
+			} else return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "instruction %u: unknown op %u", k, ins.op);
+		}
+	}
+	if (int rc = anim_upload_tables(ctx)) return rc;
+	AnimTables t;
+	t.src = an.d_src.p; t.const_translations = an.d_ct.p; t.translations = an.d_tt.p; t.const_rotations = an.d_cr.p; t.rotations = an.d_rt.p;
+	t.translation_stream = an.d_tstream.p; t.rotation_stream = an.d_rstream.p; t.root_translations = an.d_root_t.p; t.root_rotations = an.d_root_r.p;
+	LMX_HIP(ctx, an.d_first_sample.reserve((size_t)n_instances + 1));
+	if (!any_ik) { // SAMPLE records only: k_anim_blend_stack on their 16-byte form
+		LMX_HIP(ctx, an.d_samples.reserve(std::max<size_t>(n_instrs, 1)));
+		LMX_HIP(ctx, upload_on_stream(an.d_first_sample.p, first_instr, (size_t)n_instances + 1, ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(an.d_samples.p, an.samples_scratch.data(), n_instrs, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		ProfScope ps(ctx, LMX_K_ANIM_UPDATE);
+		LMX_HIP(ctx, launch_anim_blend_stack(ctx->stream, sk.d_inst.p, (uint32_t)sk.inst.size(), an.d_anims.p, t, (uint32_t)an.anims.size(), an.d_samples.p,
+			an.d_first_sample.p, an.d_rel_pos.p, an.d_rel_rot.p, sk.d_pose_pos.p, sk.d_pose_rot.p));
+	} else {
+		LMX_HIP(ctx, an.d_instrs.reserve(std::max<size_t>(n_instrs, 1)));
+		if (an.parents_uploaded != sk.parents.size()) { // models only append; the previous frame's kernel may still read the old copy
+			LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+			LMX_HIP(ctx, upload_blocking(an.d_parents, sk.parents.data(), sk.parents.size()));
+			an.parents_uploaded = sk.parents.size();
+		}
+		// pageable host arrays: the copies complete before this returns, ordered by the stream against the previous frame's kernel
+		LMX_HIP(ctx, upload_on_stream(an.d_first_sample.p, first_instr, (size_t)n_instances + 1, ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(an.d_instrs.p, instrs, n_instrs, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		ProfScope ps(ctx, LMX_K_ANIM_UPDATE);
+		LMX_HIP(ctx, launch_anim_blend_instrs(ctx->stream, sk.d_inst.p, (uint32_t)sk.inst.size(), an.d_anims.p, t, (uint32_t)an.anims.size(), an.d_instrs.p,
+			an.d_first_sample.p, an.d_parents.p, an.d_rel_pos.p, an.d_rel_rot.p, sk.d_pose_pos.p, sk.d_pose_rot.p));
+	}
 	sk.borrowed_pos = nullptr;
 	sk.borrowed_rot = nullptr;
 	sk.poses_uploaded = true;

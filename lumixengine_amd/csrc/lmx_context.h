@@ -593,6 +593,10 @@ struct AnimState {
 	DevBuf<uint32_t> d_anim_of, d_time_of;
 	DevBuf<LmxBlendSample> d_samples; // lmx_anim_eval_blend_stacks: the frame's SAMPLE instructions and their per-instance ranges
 	DevBuf<uint32_t> d_first_sample;
+	DevBuf<LmxBlendInstr> d_instrs;   // lmx_anim_eval_blend_instrs: the frame's SAMPLE and IK instructions
+	DevBuf<int16_t> d_parents;        // SkinState::parents for evalIK's chain walk; uploaded when a call holds IK and models were added since
+	size_t parents_uploaded = 0;
+	std::vector<LmxBlendSample> samples_scratch; // a call without IK runs k_anim_blend_stack on its SAMPLE fields
 };
 
 struct ProfSlot { hipEvent_t a, b; int kernel; };

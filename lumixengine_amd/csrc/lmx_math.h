@@ -6,6 +6,7 @@
 // (no FMA contraction); nothing here may be rewritten with fmaf()/__fmaf_rn or reassociated.
 #pragma once
 
+#include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -67,6 +68,60 @@ LMX_HD DV3 rotate(Q4 q, DV3 v) {                                                
 	uv = mul(uv, 2.0 * (double)q.w);
 	uuv = mul(uuv, 2.0);
 	return add(add(v, uv), uuv);
+}
+
+// ---- evalIK's arithmetic (animation/controller.cpp:159-265): the scalar fp32 forms of core/math.cpp, one rounding per operation ----
+LMX_HD float squared_length(V3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }            // math.cpp:395
+LMX_HD float length(V3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }              // math.cpp:392
+LMX_HD V3 normalize(V3 a) {                                                                 // math.cpp:367-376: 1 / sqrtf, then three multiplies
+	const float inv_len = 1 / sqrtf(a.x * a.x + a.y * a.y + a.z * a.z);
+	return V3{a.x * inv_len, a.y * inv_len, a.z * inv_len};
+}
+LMX_HD V3 lerp(V3 a, V3 b, float t) {                                                       // math.cpp:194-201
+	const float invt = 1.0f - t;
+	return V3{a.x * invt + b.x * t, a.y * invt + b.y * t, a.z * invt + b.z * t};
+}
+LMX_HD Q4 nlerp(Q4 q1, Q4 q2, float t) {                                                    // math.cpp:677-691 (not simd_nlerp: sums left to right)
+	const float inv = 1.0f - t;
+	if (q1.x * q2.x + q1.y * q2.y + q1.z * q2.z + q1.w * q2.w < 0) t = -t;
+	Q4 r = Q4{q1.x * inv + q2.x * t, q1.y * inv + q2.y * t, q1.z * inv + q2.z * t, q1.w * inv + q2.w * t};
+	const float l = 1 / sqrtf(r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w);
+	return Q4{r.x * l, r.y * l, r.z * l, r.w * l};
+}
+struct Rigid { V3 pos; Q4 rot; };                                                           // LocalRigidTransform
+LMX_HD Rigid rigid_mul(const Rigid& a, const Rigid& rhs) {                                  // operator*, math.cpp:859-861
+	return Rigid{add(rotate(a.rot, rhs.pos), a.pos), qmul(a.rot, rhs.rot)};
+}
+LMX_HD Rigid rigid_inverted(const Rigid& a) {                                               // math.cpp:836-841
+	Rigid r;
+	r.rot = conjugated(a.rot);
+	r.pos = rotate(r.rot, neg(a.pos));
+	return r;
+}
+// Quat(axis, PI), math.cpp:570-578: half_angle is the constant PI * 0.5f (PI = 3.14159265f), so s and w are the two fp32 values the
+// reference's libm returns for it - sinf gives exactly 1, cosf the residual of the rounded argument. No device sine or cosine.
+constexpr float IK_SIN_HALF_PI = 1.0f;
+constexpr float IK_COS_HALF_PI = -4.37113883e-08f; // 0xb33bbd2e
+LMX_HD Q4 quat_axis_pi(V3 axis) { return Q4{axis.x * IK_SIN_HALF_PI, axis.y * IK_SIN_HALF_PI, axis.z * IK_SIN_HALF_PI, IK_COS_HALF_PI}; }
+// Quat::vec3ToVec3, math.cpp:581-606. `which` (optional) reports the branch: 0 half-vector, 1 antiparallel with n = (0, z, -y), 2 with
+// the fallback n = (y, -x, 0). squaredLength(n) < 0.01 compares against a double constant.
+LMX_HD Q4 vec3_to_vec3(V3 v0, V3 v1, int* which = nullptr) {
+	const V3 from = normalize(v0);
+	const V3 to = normalize(v1);
+	const float cos_angle = dot(from, to);
+	if (cos_angle > -1.0005f && cos_angle < -0.9995f) {
+		V3 n = V3{0, from.z, -from.y};
+		int w = 1;
+		if ((double)squared_length(n) < 0.01) {
+			n = V3{from.y, -from.x, 0};
+			w = 2;
+		}
+		if (which) *which = w;
+		return quat_axis_pi(normalize(n));
+	}
+	if (which) *which = 0;
+	const V3 half = normalize(add(from, to));
+	return Q4{from.y * half.z - from.z * half.y, from.z * half.x - from.x * half.z, from.x * half.y - from.y * half.x, dot(from, half)};
 }
 
 // ---- Transform::compose, math.cpp:801-807 ---------------------------------------------------------------
