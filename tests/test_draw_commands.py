@@ -1,6 +1,8 @@
 """createCommands (renderer/pipeline.cpp:2747-3320) without a GPU: the numpy oracle (tests/draw_oracle.py) on the hand-made pair
 sequences of tests/draw_cases.py - run boundaries derived by hand from the reference's while loops - plus the layout of the records it
-writes, and the ISA of draw_kernels.hip (bit-exact: no fused multiply-add)."""
+writes, and the ISA of draw_kernels.hip (bit-exact: no fused multiply-add). The built sequences of draw_cases.SEAM_SEQUENCES - a chosen
+scan state placed on the first pair behind a wave, tile or scan-round edge of the device's scan - are held the same way: the walk must
+cut the runs the builder predicts, and a tracker of the state confirms that every edge class meets every situation."""
 import numpy as np
 import pytest
 
@@ -115,6 +117,56 @@ def test_group_fill():
     for j, (e, first_mesh) in enumerate([(4, 1), (5, 1), (6, 1), (7, 0), (1, 0)]):  # Mesh::lod and the mesh index come from the group's FIRST renderable
         assert rec[j, 7] == np.float32(lod[e] - dt["mesh_lod"][first_mesh]).view(np.uint32)
         assert rec[j, 11] == dt["material_index"][sc["material_offset"][e] + first_mesh]
+
+
+@pytest.mark.parametrize("name", list(DC.SEAM_SEQUENCES))
+def test_seam_sequences_cut_where_the_builder_predicts(name):
+    keys, values, windows, filler = DC.SEAM_SEQUENCES[name]()
+    sc, dt, lod, tr = DC.tables()
+    go, gv = DC.instancer()
+    T = DO.Tables(sc, dt, lod, tr, go, gv)
+    for n_batches in (1, 8):
+        DC.check_windows(name, DO.walk(keys, values, n_batches, [0, 0, 1, 1], T), windows, filler, len(keys), n_batches)
+    runs, data, groups = DO.create_commands(keys, values, DC.view(), 1, T)
+    DC.check_windows(name, runs, windows, filler, len(keys))
+    big = [f for f in filler if f[2] in (DC.DECAL, DC.CURVE)]
+    assert sorted(f[2] for f in big) == [DC.DECAL, DC.CURVE] and all(f[1] >= 3 * 256 + 255 for f in big)  # three whole tiles inside each
+    for first, count, kind, front in big:
+        r = runs[runs["first_pair"] == first][0]
+        assert (int(r["pair_count"]), int(r["front_count"])) == (count, front) and 0 < front < count
+    assert {DC.MESH, DC.MOVED} <= {f[2] for f in filler} and any(f[2] == DC.MOVED and f[1] % 2 for f in filler)
+
+
+def test_seam_sequences_cover_every_situation_at_every_seam_class():
+    """scan_trace follows {streak, blocked} pair by pair; it only counts what the sequences reach, the expected runs never come from it."""
+    seen = {"wave": set(), "tile": set(), "round": set(), "carry": set(), 63: set(), 1: set(), 255: set(), 257: set()}
+    buckets = {}
+    for name, build in DC.SEAM_SEQUENCES.items():
+        keys, values, windows, _ = build()
+        trace = DC.scan_trace(keys, values)
+        for b, s, c, k, *_ in windows:
+            assert trace[b] == (s, c, k), f"{name}: pair {b} meets {trace[b]}, not {DC.situation_name(s, c, k)}"
+            buckets.setdefault((s, c, k), set()).add(int(keys[b]) >> 56 >= DC.DEPTH)
+        if name.startswith("round carry"):  # the state set up in front of the round seam reaches pair 65 792 through a whole tile that leaves it alone
+            b, s = windows[0][:2]
+            assert b == DC.CARRY_AT and all(t[0] == s for t in trace[DC.ROUND - 1:b + 1]), name
+            seen["carry"].add(trace[b])
+        for b in range(1, len(keys)):
+            cls = DC.seam_class(b)
+            if cls:
+                seen[cls].add(trace[b])
+        for lane, mod in ((63, 64), (1, 64), (255, 256), (257, 256)):  # the shifted copies: the last lane in front of a seam, the second behind it
+            seen[lane] |= {trace[b] for b, *_ in windows if b % mod == lane % mod and (mod == 256 or (b - lane) % 256)}
+    want = set(DC.SITUATIONS)
+    assert len(want) == 36
+    for cls in ("wave", "tile", 63, 1, 255, 257):
+        assert seen[cls] >= want, f"{cls}: missing {[DC.situation_name(*x) for x in sorted(want - seen[cls])]}"
+    assert len(DC.ROUND_SITUATIONS) == 12 and {(s, c) for s, c, k in DC.ROUND_SITUATIONS} == {(s, c) for s in range(4) for c in range(3)}
+    assert {k for s, c, k in DC.ROUND_SITUATIONS} == {DC.ONE, DC.UNMOVED, DC.OTHER}
+    for cls in ("round", "carry"):
+        assert seen[cls] >= set(DC.ROUND_SITUATIONS), f"{cls}: missing {[DC.situation_name(*x) for x in sorted(set(DC.ROUND_SITUATIONS) - seen[cls])]}"
+    # every situation meets a plain and a depth-sorted bucket (the masked key is another there)
+    assert all(buckets[x] == {False, True} for x in want), [DC.situation_name(*x) for x in want if buckets[x] != {False, True}]
 
 
 def test_draw_kernels_contain_no_fused_multiply_add(tmp_path):

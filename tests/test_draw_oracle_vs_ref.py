@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from lumixengine_amd import api, scenes
+from tests import draw_cases as DC
 from tests import draw_oracle as DO
 from tests.test_im_oracle_vs_ref import FLAGS, REF, _block
 
@@ -318,14 +319,14 @@ def make_pairs(rng, n_ent, n, depth_sorted):
     return keys[order], values[order]
 
 
-def run_ref(ref_harness, sc, dt, lod, tr, keys, values, view, n_batches, gvalues, first_mesh_idx, first_mesh_lod):
+def run_ref(ref_harness, sc, dt, lod, tr, keys, values, view, n_batches, gvalues, first_mesh_idx, first_mesh_lod, mpm=MPM):
     exe, d = ref_harness
     n_ent = len(lod)
     v = np.ascontiguousarray(view, api.DRAW_VIEW).reshape(-1)[0]
     dec = np.concatenate([dt["half_extents"], dt["uv_scale"]], axis=1).astype(np.float32)
     cur = np.concatenate([dt["curve_half_extents"], dt["curve_uv_scale"], dt["curve_bezier"]], axis=1).astype(np.float32)
     bones = np.stack([dt["bones_handle"], dt["bones_offset"]], axis=1).astype(np.uint32)
-    parts = [np.array([n_ent, MPM, len(sc["models"]), len(keys), n_batches, len(gvalues)], np.uint32), np.ascontiguousarray(tr, api.TRANSFORM),
+    parts = [np.array([n_ent, mpm, len(sc["models"]), len(keys), n_batches, len(gvalues)], np.uint32), np.ascontiguousarray(tr, api.TRANSFORM),
              np.ascontiguousarray(dt["prev"], api.TRANSFORM), lod.astype(np.float32), sc["flags"], sc["model"], dt["mesh_lod"].astype(np.float32),
              dt["material_index"].astype(np.uint32), bones, dec, dt["decal_material"].astype(np.uint32), cur, dt["curve_material"].astype(np.uint32),
              keys, values, np.ascontiguousarray(v["bucket_depth_sorted"], np.uint8), np.ascontiguousarray(v["camera_pos"], np.float64),
@@ -384,5 +385,41 @@ def test_runs_and_records_match_the_reference(ref_harness, seed, n_batches):
             assert len(dr) == 1 and dr["offset"][0] == r["data_offset"]
     decal = own[np.isin(own["kind"], (DO.DECAL, DO.CURVE_DECAL))]
     assert ((decal["front_count"] > 0) & (decal["front_count"] < decal["pair_count"])).any()
+    assert data.tobytes() == odata.tobytes()
+    assert gdata.tobytes() == ogroups.tobytes()
+
+
+@pytest.mark.parametrize("name,n_batches", [("wave seams", 1), ("tile seams", 1), ("wave seams", 8), ("tile seams", 8)])
+def test_seam_sequences_match_the_reference(ref_harness, name, n_batches):
+    """The 36 situations of tests/draw_cases.py, each on the first pair behind a wave / a tile edge of the device's scan, through the
+    reference's own walk: where it cuts the runs, and every byte it writes."""
+    keys, values, windows, filler = DC.SEAM_SEQUENCES[name]()
+    assert sorted((s, c, k) for b, s, c, k, *_ in windows) == DC.SITUATIONS
+    sc, dt, lod, tr = DC.tables()  # one model of two meshes
+    view = DC.view()
+    gvalues = DC.instancer()[1]
+    fe, fm = int(gvalues[0]) & 0xFFFFFF, int(gvalues[0]) >> 40
+    allocs, draws, autos, data, gdata = run_ref(ref_harness, sc, dt, lod, tr, keys, values, view, n_batches, gvalues, fm, dt["mesh_lod"][fm], mpm=2)
+    T = DO.Tables(sc, dt, lod, tr, np.array([0, len(gvalues)], np.uint32), gvalues)
+    runs, odata, ogroups = DO.create_commands(keys, values, view, n_batches, T)
+    own = runs[(runs["kind"] != DO.AUTOINSTANCED) & (runs["stride"] != 0)]  # a type the switch does not know allocates nothing
+    assert len(allocs) == len(own)
+    assert np.array_equal(allocs[:, 0], own["data_offset"]) and np.array_equal(allocs[:, 1], own["pair_count"] * own["stride"])
+    auto = runs[runs["kind"] == DO.AUTOINSTANCED]
+    assert np.array_equal(autos[:, 1], auto["first_pair"]) and np.all(auto["pair_count"] == 1)
+    # the reference's run list around every placed pair is the one the builder predicts (runs of unknown types leave no trace in it)
+    ref_first = set(int(x) for x in autos[:, 1])
+    first_of = dict(zip((int(x) for x in own["data_offset"]), (int(x) for x in own["first_pair"])))
+    ref_runs = {first_of[int(a)]: int(size) for a, size in allocs}
+    for b, s, c, k, first, end, want in windows:
+        for f, count, kind in want:
+            if kind == DO.AUTOINSTANCED:
+                assert f in ref_first, (name, b, DC.situation_name(s, c, k))
+            elif kind in DO.STRIDE:
+                assert ref_runs.get(f) == count * DO.STRIDE[kind], (name, b, DC.situation_name(s, c, k), f)
+    for r_i, r in enumerate(own):
+        if r["kind"] in (DO.DECAL, DO.CURVE_DECAL):
+            dr = draws[draws["alloc"] == r_i]
+            assert int(dr["count"][dr["back"] == 0].sum()) == int(r["front_count"])
     assert data.tobytes() == odata.tobytes()
     assert gdata.tobytes() == ogroups.tobytes()

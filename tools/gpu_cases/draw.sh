@@ -1,6 +1,6 @@
 # Draw runs + instance buffers: parity on the GPU, the dense 10 M workload's chain keys -> sort -> draw timed warm and behind a scrub,
 # then rocprofv3 kernel stats of the same workload in a run of its own
-timeout 900 python -m pytest tests/test_gpu_draw_commands.py -m gpu -x -q > "$OUT/draw_tests.log" 2>&1; rc=$?; echo "draw tests rc=$rc" | tee -a "$OUT/draw_tests.log"; tail -n 3 "$OUT/draw_tests.log"
+timeout 900 python -m pytest tests/test_gpu_draw_commands.py tests/test_gpu_draw_boundaries.py -m gpu -x -q > "$OUT/draw_tests.log" 2>&1; rc=$?; echo "draw tests rc=$rc" | tee -a "$OUT/draw_tests.log"; tail -n 3 "$OUT/draw_tests.log"
 [ $rc -eq 0 ] || return 1
 timeout 400 python tools/draw_time.py --steps 20 > "$OUT/draw_time.json" 2> "$OUT/draw_time.err"; rc=$?; echo "draw_time rc=$rc"; cat "$OUT/draw_time.json"
 [ $rc -eq 0 ] || return 1
