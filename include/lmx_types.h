@@ -380,6 +380,72 @@ typedef struct LmxRaySceneHit {
 	float t;
 } LmxRaySceneHit;
 
+/* ---- terrain grass: Terrain::createGrass (renderer/terrain.cpp:26-139) and the quad loop of PipelineImpl::renderGrass
+ * (renderer/pipeline.cpp:2119-2209) ---- */
+#define LMX_GRASS_ROTATION_Y_UP 0u           /* GrassRotationMode::Y_UP */
+#define LMX_GRASS_ROTATION_ALL_RANDOM 1u     /* GrassRotationMode::ALL_RANDOM */
+enum {
+	LMX_GRASS_MAX_TERRAINS = 64,
+	LMX_GRASS_MAX_TYPES = 16,                /* per terrain: (splat >> 16) holds 16 bits, a type past them is never accepted */
+	LMX_GRASS_SAMPLES = 1024,                /* iterations per quad */
+	LMX_GRASS_SLOT_INSTANCES = 2048          /* records of one pool slot: every accepted sample is stored twice */
+};
+/* Terrain::GrassType. sizeof == 16. */
+typedef struct LmxGrassType {
+	float spacing;                           /* m_spacing; <= 0: createGrass skips the type */
+	float distance;                          /* m_distance */
+	uint32_t rotation_mode;                  /* LMX_GRASS_ROTATION_* */
+	uint32_t usable;                         /* m_grass_model && m_grass_model->isReady(): 0 = renderGrass skips the type */
+} LmxGrassType;
+/* One terrain of lmx_grass_set_terrains; every array is copied at the call. sizeof == 80. */
+typedef struct LmxGrassTerrain {
+	LmxRayTerrain heightmap;                 /* entity, m_width / m_height, format, m_scale, ready, texels */
+	uint32_t splat_width, splat_height;
+	uint32_t splat_format;                   /* LMX_RAY_TERRAIN_RGBA8, or anything else: getPixelNearest gives 0 (texture.cpp:90-95) */
+	uint32_t splat_ready;                    /* m_splatmap && m_splatmap->isReady(); 0: createGrass does nothing */
+	const void* splat_texels;                /* RGBA8 texels; NULL (`data.empty()`): nothing is accepted */
+	const LmxGrassType* types;
+	uint32_t n_types;
+	uint32_t _pad;
+} LmxGrassTerrain;
+/* One instance of a quad as the reference's vertex buffer holds it. sizeof == 32. */
+typedef struct LmxGrassInstance {
+	float position[3];
+	float scale;
+	float rotation[4];
+} LmxGrassInstance;
+/* Terrain::GrassQuad. An empty quad has instances_count 0 and aabb (FLT_MAX, -FLT_MAX). sizeof == 48. */
+typedef struct LmxGrassQuad {
+	float aabb_min[3], aabb_max[3];
+	int32_t ij[2];
+	uint32_t type;
+	uint32_t instances_count;                /* twice the accepted samples */
+	uint32_t terrain;                        /* index in the table of lmx_grass_set_terrains */
+	uint32_t slot;                           /* the quad's slice of the pool: LMX_GRASS_SLOT_INSTANCES records from slot * LMX_GRASS_SLOT_INSTANCES */
+} LmxGrassQuad;
+/* A view of renderGrass. sizeof == 288. */
+typedef struct LmxGrassView {
+	LmxShiftedFrustum frustum;               /* cp.frustum */
+	double viewport_pos[3];                  /* m_viewport.pos: the pipeline's main viewport, also for shadow views */
+	float lod_multiplier;                    /* Renderer::getLODMultiplier */
+	uint32_t _pad;
+} LmxGrassView;
+/* One drawIndexedInstanced of renderGrass's quad loop (per mesh of LOD 0 the engine replays it). sizeof == 24. */
+typedef struct LmxGrassDraw {
+	uint32_t quad;                           /* index in the live-quad list (lmx_grass_read_quads) */
+	uint32_t slot;
+	uint32_t terrain, type;
+	uint32_t instance_count;
+	float distance;                          /* drawcall_data.dist */
+} LmxGrassDraw;
+/* What renderGrass pushes to the profiler, per view and per mesh. sizeof == 16. */
+typedef struct LmxGrassCounts {
+	uint32_t draws;                          /* "Quad count" */
+	uint32_t culled;                         /* "Culled" */
+	uint32_t instances;                      /* "Instances" */
+	uint32_t live;                           /* live quads the launch went over */
+} LmxGrassCounts;
+
 #ifdef __cplusplus
 }
 #endif

@@ -1075,6 +1075,46 @@ LMX_API int lmx_particles_read_slices(LmxParticles* ps, LmxParticleSlice* slices
 /* Device pointers for GPU consumers, valid until the next reserve or set_program; stream-ordered behind lmx_particles_fill */
 LMX_API int lmx_particles_device_outputs(LmxParticles* ps, LmxParticlesDevice* out);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * Terrain grass: Terrain::createGrass (renderer/terrain.cpp:26-139) for every terrain and the quad loop of PipelineImpl::renderGrass
+ * (renderer/pipeline.cpp:2119-2209) for every view of a frame (lumixengine_amd/host/gpu_grass.h). The bookkeeping of createGrass - which
+ * quads exist, last_used_frame, the eviction - stays on the host; the instances of every new quad and the per-view verdicts come from the
+ * device. One pool slot of LMX_GRASS_SLOT_INSTANCES records per cached quad, empty quads included.
+ * ------------------------------------------------------------------------------------------------------------------------------------ */
+typedef struct LmxGrass LmxGrass;
+typedef struct LmxGrassDevice {
+	const LmxGrassInstance* d_pool;    /* slot s: records [s * LMX_GRASS_SLOT_INSTANCES, + instances_count) */
+	const LmxGrassQuad* d_quads;       /* by slot */
+	const LmxGrassDraw* d_draws;       /* view v: records [v * draw_stride, + d_counts[v].draws) of the last lmx_grass_cull */
+	const LmxGrassCounts* d_counts;    /* one per view of the last lmx_grass_cull */
+	uint32_t n_slots, draw_stride, n_views, n_live;
+} LmxGrassDevice;
+LMX_API int lmx_grass_create(LmxContext* ctx, LmxGrass** out);
+LMX_API void lmx_grass_destroy(LmxGrass* g);
+/* The terrain table (at most LMX_GRASS_MAX_TERRAINS, LMX_GRASS_MAX_TYPES types each). Every cached quad is dropped (m_is_grass_dirty). */
+LMX_API int lmx_grass_set_terrains(LmxGrass* g, uint32_t n, const LmxGrassTerrain* terrains);
+/* Terrain::setGrassDirty of one terrain, or of all with terrain == 0xffffffff */
+LMX_API int lmx_grass_invalidate(LmxGrass* g, uint32_t terrain);
+/* World::getPosition of every terrain's entity: n x 3 doubles */
+LMX_API int lmx_grass_set_positions(LmxGrass* g, uint32_t n, const double* pos_xyz);
+/* The pool: `slots` quads can be cached. Drops every cached quad. */
+LMX_API int lmx_grass_reserve(LmxGrass* g, uint32_t slots);
+/* createGrass(center, frame) of every terrain: n x 2 floats. LMX_ERR_CAPACITY when the new quads need more slots than are free (nothing is
+ * launched or changed); LMX_ERR_INVALID_ARGUMENT for a non-finite centre or a quad index outside int. Does not wait for the device. */
+LMX_API int lmx_grass_update(LmxGrass* g, uint32_t frame, uint32_t n, const float* center_xz);
+/* renderGrass's quad loop for n_views views over every cached quad, in one launch; n_views == 0 does nothing. Does not wait. */
+LMX_API int lmx_grass_cull(LmxGrass* g, uint32_t n_views, const LmxGrassView* views);
+/* Read-backs (they wait for the stream). quads: the live list in (terrain, type, i, j) order; *out_n: its length. */
+LMX_API int lmx_grass_read_quads(LmxGrass* g, LmxGrassQuad* out, uint32_t cap, uint32_t* out_n);
+/* all LMX_GRASS_SLOT_INSTANCES records of a slot, written or not */
+LMX_API int lmx_grass_read_instances(LmxGrass* g, uint32_t slot, LmxGrassInstance* out, uint32_t cap);
+LMX_API int lmx_grass_read_draws(LmxGrass* g, uint32_t view, LmxGrassDraw* out, uint32_t cap, uint32_t* out_n);
+LMX_API int lmx_grass_counts(LmxGrass* g, LmxGrassCounts* out, uint32_t cap_views);
+/* Tests: overwrite a slot's records (a quad that is only touched keeps them) */
+LMX_API int lmx_grass_write_instances(LmxGrass* g, uint32_t slot, const LmxGrassInstance* in, uint32_t n);
+/* Device pointers for GPU consumers, valid until the next reserve / set_terrains / cull with more views or quads; stream-ordered */
+LMX_API int lmx_grass_device_outputs(LmxGrass* g, LmxGrassDevice* out);
+
 LMX_API const char* lmx_version(void);
 
 #ifdef __cplusplus

@@ -373,6 +373,20 @@ SYMBOLS = {
     "lmx_particles_read_channels": (_ci, [_vp, _u32, _u32, _vp, _u32, C.POINTER(_u32)]),
     "lmx_particles_read_slices": (_ci, [_vp, _vp, _u32, _vp, _u32]),
     "lmx_particles_device_outputs": (_ci, [_vp, _vp]),
+    "lmx_grass_create": (_ci, [_vp, C.POINTER(_vp)]),
+    "lmx_grass_destroy": (None, [_vp]),
+    "lmx_grass_set_terrains": (_ci, [_vp, _u32, _vp]),
+    "lmx_grass_invalidate": (_ci, [_vp, _u32]),
+    "lmx_grass_set_positions": (_ci, [_vp, _u32, _vp]),
+    "lmx_grass_reserve": (_ci, [_vp, _u32]),
+    "lmx_grass_update": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_grass_cull": (_ci, [_vp, _u32, _vp]),
+    "lmx_grass_read_quads": (_ci, [_vp, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_grass_read_instances": (_ci, [_vp, _u32, _vp, _u32]),
+    "lmx_grass_read_draws": (_ci, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_grass_counts": (_ci, [_vp, _vp, _u32]),
+    "lmx_grass_write_instances": (_ci, [_vp, _u32, _vp, _u32]),
+    "lmx_grass_device_outputs": (_ci, [_vp, _vp]),
     "lmx_version": (C.c_char_p, []),
 }
 
@@ -1862,3 +1876,133 @@ class ParticleSystems:
         data = np.zeros(d.frame_bytes // 4 + PARTICLES_GUARD_FLOATS, np.float32)
         self.ctx.check(self.lib.lmx_particles_read_slices(self.h, _ptr(slices) if len(slices) else None, len(slices), _ptr(data), data.nbytes))
         return slices, data
+
+
+GRASS_TYPE = np.dtype([("spacing", "<f4"), ("distance", "<f4"), ("rotation_mode", "<u4"), ("usable", "<u4")])  # LmxGrassType
+GRASS_TERRAIN = np.dtype([("heightmap", RAY_TERRAIN), ("splat_width", "<u4"), ("splat_height", "<u4"), ("splat_format", "<u4"), ("splat_ready", "<u4"),
+                          ("splat_texels", "<u8"), ("types", "<u8"), ("n_types", "<u4"), ("_pad", "<u4")])  # LmxGrassTerrain
+GRASS_INSTANCE = np.dtype([("position", "<f4", 3), ("scale", "<f4"), ("rotation", "<f4", 4)])  # LmxGrassInstance
+GRASS_QUAD = np.dtype([("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3), ("ij", "<i4", 2), ("type", "<u4"), ("instances_count", "<u4"), ("terrain", "<u4"), ("slot", "<u4")])  # LmxGrassQuad
+GRASS_VIEW = np.dtype([("frustum", SHIFTED_FRUSTUM), ("viewport_pos", "<f8", 3), ("lod_multiplier", "<f4"), ("_pad", "<u4")])  # LmxGrassView
+GRASS_DRAW = np.dtype([("quad", "<u4"), ("slot", "<u4"), ("terrain", "<u4"), ("type", "<u4"), ("instance_count", "<u4"), ("distance", "<f4")])  # LmxGrassDraw
+GRASS_COUNTS = np.dtype([("draws", "<u4"), ("culled", "<u4"), ("instances", "<u4"), ("live", "<u4")])  # LmxGrassCounts
+GRASS_ROTATION_Y_UP, GRASS_ROTATION_ALL_RANDOM = 0, 1  # LMX_GRASS_ROTATION_*
+GRASS_MAX_TERRAINS, GRASS_MAX_TYPES, GRASS_SAMPLES, GRASS_SLOT_INSTANCES = 64, 16, 1024, 2048  # LMX_GRASS_*
+GRASS_WINDOW = 64  # lmx_grass.h: texels per side of the splat window k_grass_quads stages in LDS
+GRASS_CULL_BLOCK = 256
+GRASS_ALL = 0xFFFFFFFF
+
+
+class LmxGrassDevice(C.Structure):
+    _fields_ = [("d_pool", C.c_void_p), ("d_quads", C.c_void_p), ("d_draws", C.c_void_p), ("d_counts", C.c_void_p), ("n_slots", _u32), ("draw_stride", _u32),
+                ("n_views", _u32), ("n_live", _u32)]
+
+
+class Grass:
+    """Terrain::createGrass of every terrain and renderGrass's quad loop of every view on the device (lmx_grass_*).
+
+    A terrain is a dict: entity, heightmap (2-D uint16 = R16 or uint32 = RGBA8), scale (3), optional ready / format; splatmap (2-D uint32, or
+    None), optional splat_format / splat_ready; types: a list of (spacing, distance, rotation_mode, usable)."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(self.lib.lmx_grass_create(ctx.h, C.byref(h)))
+        self.h = h
+        self.n_terrains = 0
+        self.n_views = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.lib.lmx_grass_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setTerrains(self, terrains):
+        recs = np.zeros(len(terrains), GRASS_TERRAIN)
+        keep = []
+        for r, t in zip(recs, terrains):
+            h = np.ascontiguousarray(t["heightmap"])
+            keep.append(h)
+            hm = r["heightmap"]
+            hm["entity"] = t.get("entity", 0)
+            hm["height"], hm["width"] = h.shape
+            hm["format"] = t.get("format", RAY_TERRAIN_R16 if h.dtype == np.uint16 else RAY_TERRAIN_RGBA8)
+            hm["scale"] = t["scale"]
+            hm["ready"] = 1 if t.get("ready", True) else 0
+            hm["texels"] = h.ctypes.data
+            s = t.get("splatmap")
+            if s is not None:
+                s = np.ascontiguousarray(s, np.uint32)
+                keep.append(s)
+                r["splat_height"], r["splat_width"] = s.shape
+                r["splat_texels"] = s.ctypes.data
+            r["splat_format"] = t.get("splat_format", RAY_TERRAIN_RGBA8)
+            r["splat_ready"] = 1 if t.get("splat_ready", True) else 0
+            ty = np.zeros(len(t["types"]), GRASS_TYPE)
+            for k, v in enumerate(t["types"]):
+                ty[k] = tuple(v)
+            keep.append(ty)
+            r["types"] = ty.ctypes.data if len(ty) else 0
+            r["n_types"] = len(ty)
+        self.ctx.check(self.lib.lmx_grass_set_terrains(self.h, len(recs), _ptr(recs) if len(recs) else None))
+        self.n_terrains = len(recs)
+
+    def invalidate(self, terrain: int = GRASS_ALL):
+        self.ctx.check(self.lib.lmx_grass_invalidate(self.h, terrain))
+
+    def setPositions(self, pos):
+        p = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        self.ctx.check(self.lib.lmx_grass_set_positions(self.h, len(p), _ptr(p) if len(p) else None))
+
+    def reserve(self, slots: int):
+        self.ctx.check(self.lib.lmx_grass_reserve(self.h, slots))
+        self.n_slots = slots
+
+    def update(self, frame: int, centers):
+        c = np.ascontiguousarray(centers, np.float32).reshape(-1, 2)
+        self.ctx.check(self.lib.lmx_grass_update(self.h, frame & 0xFFFFFFFF, len(c), _ptr(c) if len(c) else None))
+
+    def cull(self, views):
+        v = np.ascontiguousarray(views, GRASS_VIEW).reshape(-1)
+        self.ctx.check(self.lib.lmx_grass_cull(self.h, len(v), _ptr(v) if len(v) else None))
+        if len(v):
+            self.n_views = len(v)
+
+    def readQuads(self) -> np.ndarray:
+        n = _u32()
+        out = np.zeros(max(getattr(self, "n_slots", 0), 1), GRASS_QUAD)
+        self.ctx.check(self.lib.lmx_grass_read_quads(self.h, _ptr(out), len(out), C.byref(n)))
+        return out[: n.value]
+
+    def readInstances(self, slot: int) -> np.ndarray:
+        out = np.zeros(GRASS_SLOT_INSTANCES, GRASS_INSTANCE)
+        self.ctx.check(self.lib.lmx_grass_read_instances(self.h, slot, _ptr(out), len(out)))
+        return out
+
+    def writeInstances(self, slot: int, records):
+        r = np.ascontiguousarray(records, GRASS_INSTANCE).reshape(-1)
+        self.ctx.check(self.lib.lmx_grass_write_instances(self.h, slot, _ptr(r) if len(r) else None, len(r)))
+
+    def readDraws(self, view: int) -> np.ndarray:
+        n = _u32()
+        out = np.zeros(max(getattr(self, "n_slots", 0), 1), GRASS_DRAW)
+        self.ctx.check(self.lib.lmx_grass_read_draws(self.h, view, _ptr(out), len(out), C.byref(n)))
+        return out[: n.value]
+
+    def counts(self) -> np.ndarray:
+        out = np.zeros(max(self.n_views, 1), GRASS_COUNTS)
+        self.ctx.check(self.lib.lmx_grass_counts(self.h, _ptr(out), len(out)))
+        return out[: self.n_views]
+
+    def deviceOutputs(self) -> LmxGrassDevice:
+        d = LmxGrassDevice()
+        self.ctx.check(self.lib.lmx_grass_device_outputs(self.h, C.byref(d)))
+        return d

@@ -22,6 +22,7 @@
 #include "lmx_kernels.h"
 #include "lmx_entity_tr.h"
 #include "lmx_ray_math.h"
+#include "lmx_terrain_height.h" // both Terrain::getHeight, shared with grass_kernels.hip
 
 namespace lmx {
 
@@ -30,11 +31,6 @@ namespace {
 constexpr unsigned long long RAY_NONE = ~0ull;
 constexpr uint32_t WAVE = 64;
 static_assert(RAY_TERRAIN_CHUNK == WAVE && RAY_BLOCK % WAVE == 0, "one step of a chunk per lane");
-
-__device__ __forceinline__ int32_t clamp_i(int32_t v, int32_t lo, int32_t hi) {                     // core/math.h:520-522
-	const int32_t m = v > lo ? v : lo;
-	return m < hi ? m : hi;
-}
 
 // the filter of castRay(ray, ignored), :2603-2607: `hit.entity != ignored || !ignored.isValid()`
 __device__ __forceinline__ bool refused(const LmxRay& ray, int32_t entity) { return ray.ignore >= 0 && entity == ray.ignore; }
@@ -180,40 +176,6 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_pgray_write(SceneRaysDevice q) {
 }
 
 // ---- terrain ----
-
-// (int)v as x86's cvttss2si gives it: NaN and values outside int32 are INT32_MIN (lmx::trunc_i32 for floats)
-__device__ __forceinline__ int32_t trunc_i32f(float v) { return (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : (int32_t)0x80000000u; }
-
-struct TerrainView { const uint8_t* texels; int32_t w, h; uint32_t format; float sx, sy, sz; };
-
-// Terrain::getHeight(int, int), terrain.cpp:430-447
-__device__ __forceinline__ float terrain_texel_height(const TerrainView& tv, int32_t x, int32_t z) {
-	const float DIV64K = 1.0f / 65535.0f;
-	const float DIV255 = 1.0f / 255.0f;
-	const int32_t idx = clamp_i(x, 0, tv.w - 1) + clamp_i(z, 0, tv.h - 1) * tv.w; // (>= 0 and < w * h <= 2^30: checked when the table was set)
-	if (tv.format == LMX_RAY_TERRAIN_R16) return tv.sy * DIV64K * (float)(int32_t)reinterpret_cast<const uint16_t*>(tv.texels)[idx];
-	return tv.sy * DIV255 * (float)(reinterpret_cast<const uint32_t*>(tv.texels)[idx] & 0xffu);
-}
-
-// Terrain::getHeight(float, float), terrain.cpp:402-427
-__device__ __forceinline__ float terrain_height(const TerrainView& tv, float x, float z) {
-	const float inv_scale = 1.0f / tv.sx;
-	const int32_t int_x = trunc_i32f(x * inv_scale);
-	const int32_t int_z = trunc_i32f(z * inv_scale);
-	const float dec_x = (x - ((float)int_x * tv.sx)) * inv_scale;
-	const float dec_z = (z - ((float)int_z * tv.sx)) * inv_scale;
-	if (dec_z == 0 && dec_x == 0) return terrain_texel_height(tv, int_x, int_z);
-	if (dec_x > dec_z) {
-		const float h0 = terrain_texel_height(tv, int_x, int_z);
-		const float h1 = terrain_texel_height(tv, int_x + 1, int_z);
-		const float h2 = terrain_texel_height(tv, int_x + 1, int_z + 1);
-		return h0 + (h1 - h0) * dec_x + (h2 - h1) * dec_z;
-	}
-	const float h0 = terrain_texel_height(tv, int_x, int_z);
-	const float h1 = terrain_texel_height(tv, int_x + 1, int_z + 1);
-	const float h2 = terrain_texel_height(tv, int_x, int_z + 1);
-	return h0 + (h2 - h0) * dec_z + (h1 - h2) * dec_x;
-}
 
 __device__ __forceinline__ float abs_of(float v) { return __uint_as_float(__float_as_uint(v) & 0x7fffffffu); } // fabsf
 
