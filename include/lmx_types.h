@@ -241,7 +241,13 @@ typedef struct LmxAnimRotationTrack { /* Animation::RotationTrack: 3 packed chan
 	uint8_t skipped_channel;
 } LmxAnimRotationTrack;
 
-/* What AnimationSampler reads of an Animation resource. Streams hold frame_count + 1 frames (animation.cpp:464). */
+/* What AnimationSampler reads of an Animation resource. Streams hold frame_count + 1 frames (animation.cpp:464), the root-motion arrays
+ * frame_count + 1 entries; the library copies exactly those bits. The clip's end: the sample point is clamped to frame_count - 0.00001f,
+ * which in fp32 is frame_count itself from 257 frames on, so a sample at or past the end of such a clip decodes frames frame_count and
+ * frame_count + 1 (times f == 0) - in the engine, whatever lies behind the streams. Here the frame after the last reads as zero bits
+ * (and the root-motion entry after the last as zeros); against the engine this can differ in the sign of a zero only.
+ * lmx_anim_add refuses a clip whose frame_size_bits * (frame_count + 2) + 64 does not fit 32 bits, for either stream, and a frame_count
+ * above 2^24 (there (float)frame_count can round up, and the clamp with it, past the frames a clip has). */
 typedef struct LmxAnimation {
 	float fps;                               /* m_fps */
 	uint32_t frame_count;                    /* m_frame_count */

@@ -447,6 +447,8 @@ LMX_API int lmx_anim_set_model_pose(LmxContext* ctx, uint32_t model, const LmxLo
  * Animable::time in Time units (1 / 32768 s, animation/animation.h:17-41). Times then live and advance on the device. */
 LMX_API int lmx_anim_set_animables(LmxContext* ctx, uint32_t n_instances, const uint32_t* animation, const uint32_t* time);
 LMX_API int lmx_anim_set_weight(LmxContext* ctx, float weight); /* SampleContext::weight, default 1 */
+/* time_delta in seconds; LMX_ERR_INVALID_ARGUMENT if it is not finite or |time_delta| * 32768 reaches 2^32 (Time::fromSeconds is u32(seconds *
+ * ONE_SECOND): undefined from there on). */
 LMX_API int lmx_anim_update(LmxContext* ctx, float time_delta);
 /* AnimationModuleImpl::updateAnimator's pose work for every instance in one launch (animation_module.cpp:602-636): Model::getRelativePose
  * into the pose, then evalBlendStack's SAMPLE instructions in order (controller.cpp:267-293, getPose :142-157) - instance i owns

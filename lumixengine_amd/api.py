@@ -64,14 +64,15 @@ class LmxAnimation(C.Structure):
 
 
 def animation_struct(a: dict):
-    """(LmxAnimation, keep-alive list) from a lumixengine_amd.scenes.animation dict."""
+    """(LmxAnimation, keep-alive list) from a lumixengine_amd.scenes.animation dict. Optional keys translation_stream_size /
+    rotation_stream_size declare fewer bytes than the arrays hold (default: all of them)."""
     keep = [np.ascontiguousarray(a["const_translations"], ANIM_CONST_TRANSLATION), np.ascontiguousarray(a["translations"], ANIM_TRANSLATION_TRACK),
             np.ascontiguousarray(a["const_rotations"], ANIM_CONST_ROTATION), np.ascontiguousarray(a["rotations"], ANIM_ROTATION_TRACK),
             np.ascontiguousarray(a["translation_stream"], np.uint8), np.ascontiguousarray(a["rotation_stream"], np.uint8),
             np.ascontiguousarray(a["root_pose_translations"], np.float32), np.ascontiguousarray(a["root_pose_rotations"], np.float32)]
     st = LmxAnimation(float(a["fps"]), int(a["frame_count"]), int(a["length"]), int(a["translations_frame_size_bits"]), int(a["rotations_frame_size_bits"]),
                       len(keep[0]), len(keep[1]), len(keep[2]), len(keep[3]), _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(keep[4]),
-                      len(keep[4]), _ptr(keep[5]), len(keep[5]), int(a["root_translation_track"]), int(a["root_rotation_track"]), _ptr(keep[6]), _ptr(keep[7]))
+                      int(a.get("translation_stream_size", len(keep[4]))), _ptr(keep[5]), int(a.get("rotation_stream_size", len(keep[5]))), int(a["root_translation_track"]), int(a["root_rotation_track"]), _ptr(keep[6]), _ptr(keep[7]))
     return st, keep
 
 

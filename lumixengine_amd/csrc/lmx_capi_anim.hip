@@ -40,7 +40,17 @@ int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation
 	if ((a->n_const_translations && !a->const_translations) || (a->n_translations && !a->translations) || (a->n_const_rotations && !a->const_rotations) ||
 		(a->n_rotations && !a->rotations))
 		return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null track array");
-	const uint64_t t_need = ((uint64_t)a->translations_frame_size_bits * (a->frame_count + 1) + 7) / 8, r_need = ((uint64_t)a->rotations_frame_size_bits * (a->frame_count + 1) + 7) / 8;
+	// all stream arithmetic in 64 bits. The caller holds frame_count + 1 frames (animation.cpp:464); the tables store frame_count + 2 (below), and
+	// the kernel addresses a frame's bits with a 32-bit offset and reads 64 bits from it
+	const uint64_t frames_in = (uint64_t)a->frame_count + 1, frames_stored = (uint64_t)a->frame_count + 2;
+	const uint64_t t_bits = (uint64_t)a->translations_frame_size_bits * frames_in, r_bits = (uint64_t)a->rotations_frame_size_bits * frames_in;
+	if ((uint64_t)a->translations_frame_size_bits * frames_stored + 64 > 0xFFFFFFFFull || (uint64_t)a->rotations_frame_size_bits * frames_stored + 64 > 0xFFFFFFFFull)
+		return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "frame size %u / %u bits x (frame_count %u + 2) frames does not fit a 32-bit bit offset", a->translations_frame_size_bits,
+			a->rotations_frame_size_bits, a->frame_count);
+	// The sample point's upper clamp is (float)frame_count - 0.00001f (anim_kernels.hip, animation.cpp:132). Up to 2^24 every count is an fp32 number
+	// and the clamp is at most frame_count; above, (float)frame_count can round up and sample_idx would pass the frames stored here
+	if (a->frame_count > (1u << 24)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "frame_count %u exceeds 2^24: the sample point is computed in fp32", a->frame_count);
+	const uint64_t t_need = (t_bits + 7) / 8, r_need = (r_bits + 7) / 8;
 	if ((a->n_translations && (!a->translation_stream || a->translation_stream_size < t_need)) || (a->n_rotations && (!a->rotation_stream || a->rotation_stream_size < r_need)))
 		return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "track streams must hold frame_count + 1 frames (animation.cpp:464): need %llu / %llu bytes", (unsigned long long)t_need, (unsigned long long)r_need);
 	if ((a->root_translation_track >= 0 && ((uint32_t)a->root_translation_track >= a->n_translations || !a->root_pose_translations)) ||
@@ -53,6 +63,10 @@ int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation
 	for (uint32_t i = 0; i < a->n_const_rotations; ++i) max_bone = std::max<uint32_t>(max_bone, a->const_rotations[i].bone_index);
 	for (uint32_t i = 0; i < a->n_rotations; ++i) max_bone = std::max<uint32_t>(max_bone, a->rotations[i].bone_index);
 	if (max_bone >= LMX_MAX_BONES) return fail(ctx, LMX_ERR_CAPACITY, "track bone index %u >= %d (Model::Bone::MAX_COUNT)", max_bone, LMX_MAX_BONES);
+	const uint64_t t_store = a->n_translations ? ((uint64_t)a->translations_frame_size_bits * frames_stored + 7) / 8 : 0;
+	const uint64_t r_store = a->n_rotations ? ((uint64_t)a->rotations_frame_size_bits * frames_stored + 7) / 8 : 0;
+	if (an.tstream.size() + t_store + 24 > 0xFFFFFFFFull || an.rstream.size() + r_store + 24 > 0xFFFFFFFFull || an.root_r.size() + frames_stored > 0xFFFFFFFFull)
+		return fail(ctx, LMX_ERR_CAPACITY, "the animation tables are addressed with 32-bit offsets: no room for this clip");
 	// per-bone sources: the reference runs the four track lists in order; with at most one translation and one rotation source per
 	// bone the order is irrelevant and a lane can look its bone up directly
 	std::vector<int32_t> src(2 * (size_t)(max_bone + 1), -1);
@@ -93,18 +107,28 @@ int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation
 	an.tt.insert(an.tt.end(), a->translations, a->translations + a->n_translations);
 	an.cr.insert(an.cr.end(), a->const_rotations, a->const_rotations + a->n_const_rotations);
 	an.rt.insert(an.rt.end(), a->rotations, a->rotations + a->n_rotations);
-	auto append_stream = [](std::vector<uint8_t>& dst, const uint8_t* src_bytes, uint64_t need) { // 8-byte aligned start, 16 bytes of slack for the 64-bit reads
-		if (need) dst.insert(dst.end(), src_bytes, src_bytes + need);
+	// The frame after the last reads as zero bits: a sample at the clip's end (sample_idx == frame_count, f == 0, every frame_count >= 257: the
+	// sample point's upper clamp frame_count - 0.00001f is frame_count in fp32) decodes frames frame_count and frame_count + 1, which the
+	// reference leaves to whatever follows its stream. So: the caller's frame_count + 1 frames to the bit (the tail of their last byte is
+	// cleared), one more frame of zero bits, then 16 bytes of slack for the 64-bit reads; every clip starts 8-byte aligned.
+	auto append_stream = [](std::vector<uint8_t>& dst, const uint8_t* src_bytes, uint64_t bits, uint64_t need, uint64_t store) {
+		const size_t start = dst.size();
+		if (store) {
+			dst.insert(dst.end(), src_bytes, src_bytes + need);
+			if (bits & 7) dst.back() &= (uint8_t)((1u << (bits & 7)) - 1u);
+			dst.resize(start + store, 0);
+		}
 		dst.resize((dst.size() + 16 + 7) & ~(size_t)7, 0);
 	};
-	append_stream(an.tstream, a->translation_stream, a->n_translations ? t_need : 0);
-	append_stream(an.rstream, a->rotation_stream, a->n_rotations ? r_need : 0);
-	const size_t frames = (size_t)a->frame_count + 1;
-	for (size_t f = 0; f < frames; ++f) {
+	append_stream(an.tstream, a->translation_stream, t_bits, t_need, t_store);
+	append_stream(an.rstream, a->rotation_stream, r_bits, r_need, r_store);
+	for (size_t f = 0; f < (size_t)frames_in; ++f) { // frame_count + 1 entries of the caller's, then one of zeros (the same definition)
 		for (int k = 0; k < 3; ++k) an.root_t.push_back(a->root_translation_track >= 0 ? a->root_pose_translations[3 * f + k] : 0.f);
 		an.root_r.push_back(a->root_rotation_track >= 0 ? make_float4(a->root_pose_rotations[4 * f], a->root_pose_rotations[4 * f + 1], a->root_pose_rotations[4 * f + 2], a->root_pose_rotations[4 * f + 3])
 		                                                : make_float4(0.f, 0.f, 0.f, 1.f));
 	}
+	for (int k = 0; k < 3; ++k) an.root_t.push_back(0.f);
+	an.root_r.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
 	*out_animation = (uint32_t)an.anims.size();
 	an.anims.push_back(d);
 	an.tables_dirty = true;
@@ -157,6 +181,9 @@ int lmx_anim_update(LmxContext* ctx, float time_delta) {
 	LMX_CHECK_CTX(ctx);
 	SkinState& sk = ctx->skin;
 	AnimState& an = ctx->anim;
+	// Time::fromSeconds is u32(seconds * ONE_SECOND): out of range the conversion is undefined and differs between the host and the device
+	if (!std::isfinite(time_delta) || !(std::fabs(time_delta) * (float)LMX_TIME_ONE_SECOND < 4294967296.f))
+		return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "time_delta %g: not finite, or more than 2^32 ticks of 1 / %u s", (double)time_delta, LMX_TIME_ONE_SECOND);
 	if (sk.inst.empty()) return LMX_OK;
 	if (an.n_animables != sk.inst.size()) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_anim_set_animables has not been called for this instance table");
 	if (an.rel_rot.size() != sk.parents.size()) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_anim_set_model_pose is missing for a model added later");

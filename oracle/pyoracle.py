@@ -317,6 +317,12 @@ class Oracle:
         f(_ptr(q1), _ptr(q2), _ptr(t), _ptr(out), len(q1))
         return out
 
+    def anim_pads_root_motion(self) -> bool:
+        """Whether a sample at a clip's end reads a defined root-motion entry frame_count + 1 (zeros, include/lmx_types.h). The port oracle reads
+        the caller's arrays; the reference sampler reads vectors of the shim's own, padded only by a shim that says so (oracle/ref/anim_shim.cpp) -
+        a prebuilt oracle/_ref may be older."""
+        return self.kind != "reference" or hasattr(self.lib, "ref_anim_pads_root_motion")
+
     def update_animables(self, anims, anim_of_instance, times, time_delta, weight, model_relative):
         """AnimationModuleImpl::updateAnimable per instance (animation_module.cpp:439-472): returns (pos [n, bones, 3], rot [n, bones, 4],
         new times). `anims` = list of lumixengine_amd.scenes.animation dicts, anim_of_instance < 0 or 0xffffffff = no animation."""

@@ -132,6 +132,10 @@ static void sample_onto(const LmxAnimation* a, uint32_t time, float weight, uint
 			if (a->root_pose_rotations)
 				for (u32 f = 0; f <= a->frame_count; ++f)
 					m_root_motion.pose_rotations.v.push_back(Quat(a->root_pose_rotations[4 * f], a->root_pose_rotations[4 * f + 1], a->root_pose_rotations[4 * f + 2], a->root_pose_rotations[4 * f + 3]));
+			// a sample at the clip's end reads entry frame_count + 1 (times f == 0): past the engine's arrays, and so past these vectors. The
+			// library defines it as zeros (include/lmx_types.h, LmxAnimation); the same entry here keeps the read inside the vector
+			m_root_motion.pose_translations.v.push_back(Vec3(0, 0, 0));
+			m_root_motion.pose_rotations.v.push_back(Quat(0, 0, 0, 0));
 		}
 	} anim;
 	anim.fill(a);
@@ -147,6 +151,11 @@ static void sample_onto(const LmxAnimation* a, uint32_t time, float weight, uint
 	ctx.weight = weight;
 	anim.getRelativePose(ctx);
 }
+
+// Says that this build appends the zero root-motion entry above. A liblmx_ref.so without this symbol was built from an earlier shim: its
+// sampler reads behind the root-motion vectors at a clip's end, so its values there are not to be compared (oracle/pyoracle.py,
+// Oracle.anim_pads_root_motion).
+extern "C" __attribute__((visibility("default"))) uint32_t ref_anim_pads_root_motion(void) { return 1; }
 
 // One SAMPLE instruction of evalBlendStack (animation/controller.cpp:282-289) onto an existing pose: getPose's time wrap / clamp
 // (controller.cpp:148, one line, restated - getPose itself is a static function over the controller's RuntimeContext) and then the

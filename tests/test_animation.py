@@ -30,78 +30,141 @@ def py_bits(stream, byte_offset):
     return int.from_bytes(bytes(stream[byte_offset : byte_offset + 8]), "little")
 
 
-def py_update_animable(a, time, time_delta, weight, rel):
+def u64_to_f32(x):
+    """(float)(u64): ONE rounding. f32(python int) goes through double and rounds twice (2**55 + 2**31 + 1 differs)."""
+    return np.array([x], np.uint64).astype(f32)[0]
+
+
+def note(cov, *what):
+    if cov is not None:
+        cov.add(what)
+
+
+def py_sample_point(a, time, cov=None):
+    """clamp(time.toFrame(fps), 0, frame_count - 0.00001f), animation.cpp:132-134"""
+    sample = f32(time / float(ONE_SECOND) * float(a["fps"]))
+    hi = f32(f32(a["frame_count"]) - f32(0.00001))
+    sample = min(max(sample, f32(0)), hi)
+    idx = int(sample)
+    t = f32(sample - f32(idx))
+    if idx == int(a["frame_count"]):
+        note(cov, "sample_idx == frame_count")
+    note(cov, "f == 0" if t == 0 else "f != 0")
+    return idx, t
+
+
+def py_field_offset(cov, stream, frame_bits, frame, tr, total_bits):
+    """Bit position of a track's fields in a frame; records which path of the 8-byte read (load_u64_unaligned) it takes."""
+    off = frame_bits * frame + int(tr["offset_bits"])
+    note(cov, "pair", stream, (off // 8) % 8, off & 7)
+    note(cov, "stitch", stream, "one word" if (off // 8) % 8 == 0 else "two words")
+    if (off & 7) + total_bits == 64:
+        note(cov, "ends on bit 63", stream, "one word" if (off // 8) % 8 == 0 else "two words")
+    for c in range(3):
+        note(cov, "width", stream, int(tr["bitsizes"][c]))
+    return off
+
+
+def py_sample_onto(a, time, weight, pos, rot, cov=None):
+    """Animation::getRelativePose of `a` at `time` with `weight` onto the pose (pos, rot), in place."""
+    bones = [int(x) for k in ("const_translations", "translations", "const_rotations", "rotations") for x in a[k]["bone_index"]]
+    if max(bones) >= len(pos):
+        note(cov, "skeleton mismatch")
+        return
+    use_w = f32(weight) < f32(0.9999)
+    w, invw = f32(weight), f32(f32(1.0) - f32(weight))
+    idx, t = py_sample_point(a, time, cov)
+
+    def blend_pos(b, v, kind):
+        note(cov, "use_weight", kind, bool(use_w))
+        pos[b] = [f32(f32(p * invw) + f32(x * w)) for p, x in zip(pos[b], v)] if use_w else v
+
+    for c in a["const_translations"]:
+        blend_pos(int(c["bone_index"]), c["value"], "const translation")
+    for i, tr in enumerate(a["translations"]):
+        vals = []
+        for frame in (idx, idx + 1):
+            if i == a["root_translation_track"]:
+                note(cov, "root translation entry", "frame_count + %d" % (frame - int(a["frame_count"])) if frame >= int(a["frame_count"]) else "inside")
+                vals.append(a["root_pose_translations"][frame])
+                continue
+            off = py_field_offset(cov, "translation", a["translations_frame_size_bits"], frame, tr, sum(int(x) for x in tr["bitsizes"]))
+            tmp = py_bits(a["translation_stream"], off // 8) >> (off & 7)
+            v = []
+            for c in range(3):
+                nb = int(tr["bitsizes"][c])
+                v.append(f32(float(tr["min"][c]) + float(tr["to_range"][c]) * float(tmp & ((1 << nb) - 1))))  # fp64: float(int) rounds once
+                tmp >>= nb
+            vals.append(v)
+        invt = f32(f32(1.0) - t)
+        blend_pos(int(tr["bone_index"]), [f32(f32(x * invt) + f32(y * t)) for x, y in zip(vals[0], vals[1])], "translation")
+
+    def blend_rot(b, v, kind):
+        note(cov, "use_weight", kind, bool(use_w))
+        rot[b] = py_nlerp(rot[b], v, w) if use_w else v
+
+    for c in a["const_rotations"]:
+        blend_rot(int(c["bone_index"]), c["value"], "const rotation")
+    for i, tr in enumerate(a["rotations"]):
+        if i == a["root_rotation_track"]:
+            note(cov, "root rotation entry", "frame_count + %d" % (idx + 1 - int(a["frame_count"])) if idx + 1 >= int(a["frame_count"]) else "inside")
+            v = py_nlerp(a["root_pose_rotations"][idx], a["root_pose_rotations"][idx + 1], t)
+        else:
+            qs = []
+            for frame in (idx, idx + 1):
+                off = py_field_offset(cov, "rotation", a["rotations_frame_size_bits"], frame, tr, 1 + sum(int(x) for x in tr["bitsizes"]))
+                packed = (py_bits(a["rotation_stream"], off // 8) >> (off & 7)) & ((1 << 64) - 1)
+                neg = packed & 1
+                packed >>= 1
+                v3 = []
+                for c in range(3):
+                    nb = int(tr["bitsizes"][c])
+                    v3.append(f32(tr["min"][c] + f32(tr["to_range"][c] * u64_to_f32(packed & ((1 << nb) - 1)))))
+                    packed >>= nb
+                dot = f32(f32(f32(v3[0] * v3[0]) + f32(v3[1] * v3[1])) + f32(v3[2] * v3[2]))
+                rest = f32(f32(1) - dot)
+                note(cov, "rest", "== 0" if rest == 0 else ("< 0" if rest < 0 else "> 0"), "negative" if neg else "positive")
+                note(cov, "skipped_channel", int(tr["skipped_channel"]))
+                skipped = f32(np.sqrt(max(rest, f32(0))) * f32(-1 if neg else 1))
+                q = list(v3)
+                q.insert(int(tr["skipped_channel"]), skipped)
+                qs.append(q)
+            p = [f32(f32(x) * f32(y)) for x, y in zip(qs[0], qs[1])]
+            d = f32(f32(p[0] + p[1]) + f32(p[2] + p[3]))
+            note(cov, "frame pair", "d < 0" if d < 0 else ("d == 0" if d == 0 else "d > 0"))
+            v = py_nlerp(qs[0], qs[1], t)
+        blend_rot(int(tr["bone_index"]), v, "rotation")
+
+
+def py_advance(a, time, time_delta, cov=None):
+    """animation_module.cpp:458-470 on u32 Time values: every sum wraps at 32 bits."""
+    l = int(a["length"])
+    M = 0xFFFFFFFF
+    if time_delta > 0:
+        note(cov, "advance", "forward")
+        return ((time + int(f32(f32(time_delta) * f32(ONE_SECOND)))) & M) % l
+    note(cov, "advance", "backward")
+    dt = int(f32(f32(-time_delta) * f32(ONE_SECOND))) % l
+    return ((time + l - dt) & M) % l
+
+
+def py_update_animable(a, time, time_delta, weight, rel, cov=None):
     pos = np.array(rel["pos"], f32)
     rot = np.array(rel["rot"], f32)
     if a is None:
         return pos, rot, time
-    bones = [int(x) for k in ("const_translations", "translations", "const_rotations", "rotations") for x in a[k]["bone_index"]]
-    if max(bones) < len(pos):
-        use_w = f32(weight) < f32(0.9999)
-        w, invw = f32(weight), f32(f32(1.0) - f32(weight))
-        sample = f32(time / float(ONE_SECOND) * float(a["fps"]))
-        hi = f32(f32(a["frame_count"]) - f32(0.00001))
-        sample = min(max(sample, f32(0)), hi)
-        idx = int(sample)
-        t = f32(sample - f32(idx))
+    py_sample_onto(a, time, weight, pos, rot, cov)
+    return pos, rot, py_advance(a, time, time_delta, cov)
 
-        def blend_pos(b, v):
-            pos[b] = [f32(f32(p * invw) + f32(x * w)) for p, x in zip(pos[b], v)] if use_w else v
 
-        for c in a["const_translations"]:
-            blend_pos(int(c["bone_index"]), c["value"])
-        for i, tr in enumerate(a["translations"]):
-            vals = []
-            for frame in (idx, idx + 1):
-                if i == a["root_translation_track"]:
-                    vals.append(a["root_pose_translations"][frame])
-                    continue
-                off = a["translations_frame_size_bits"] * frame + int(tr["offset_bits"])
-                tmp = py_bits(a["translation_stream"], off // 8) >> (off & 7)
-                v = []
-                for c in range(3):
-                    nb = int(tr["bitsizes"][c])
-                    v.append(f32(float(tr["min"][c]) + float(tr["to_range"][c]) * float(tmp & ((1 << nb) - 1))))
-                    tmp >>= nb
-                vals.append(v)
-            invt = f32(f32(1.0) - t)
-            blend_pos(int(tr["bone_index"]), [f32(f32(x * invt) + f32(y * t)) for x, y in zip(vals[0], vals[1])])
-
-        def blend_rot(b, v):
-            rot[b] = py_nlerp(rot[b], v, w) if use_w else v
-
-        for c in a["const_rotations"]:
-            blend_rot(int(c["bone_index"]), c["value"])
-        for i, tr in enumerate(a["rotations"]):
-            if i == a["root_rotation_track"]:
-                v = py_nlerp(a["root_pose_rotations"][idx], a["root_pose_rotations"][idx + 1], t)
-            else:
-                qs = []
-                for frame in (idx, idx + 1):
-                    off = a["rotations_frame_size_bits"] * frame + int(tr["offset_bits"])
-                    packed = (py_bits(a["rotation_stream"], off // 8) >> (off & 7)) & ((1 << 64) - 1)
-                    neg = packed & 1
-                    packed >>= 1
-                    v3 = []
-                    for c in range(3):
-                        nb = int(tr["bitsizes"][c])
-                        v3.append(f32(tr["min"][c] + f32(tr["to_range"][c] * f32(packed & ((1 << nb) - 1)))))
-                        packed >>= nb
-                    dot = f32(f32(f32(v3[0] * v3[0]) + f32(v3[1] * v3[1])) + f32(v3[2] * v3[2]))
-                    rest = f32(f32(1) - dot)
-                    skipped = f32(np.sqrt(max(rest, f32(0))) * f32(-1 if neg else 1))
-                    q = list(v3)
-                    q.insert(int(tr["skipped_channel"]), skipped)
-                    qs.append(q)
-                v = py_nlerp(qs[0], qs[1], t)
-            blend_rot(int(tr["bone_index"]), v)
-    l = int(a["length"])
-    if time_delta > 0:
-        nt = (time + int(f32(f32(time_delta) * f32(ONE_SECOND)))) % l
-    else:
-        dt = int(f32(f32(-time_delta) * f32(ONE_SECOND))) % l
-        nt = (time + l - dt) % l
-    return pos, rot, nt
+def py_blend_stack(anims, stack, rel, cov=None):
+    """evalBlendStack's SAMPLE instructions (controller.cpp:267-293; getPose :142-157): stack = [(clip index, weight, time, looped)]."""
+    pos = np.array(rel["pos"], f32)
+    rot = np.array(rel["rot"], f32)
+    for (k, w, t, looped) in stack:
+        l = int(anims[k]["length"])
+        py_sample_onto(anims[k], t % l if looped else min(t, l), w, pos, rot, cov)
+    return pos, rot
 
 
 def test_nlerp_matches_second_restatement_and_normalises(oracle_port):
