@@ -1003,7 +1003,7 @@ LMX_API int lmx_rays_device_scene_outputs(LmxContext* ctx, const LmxRaySceneHit*
 
 /* ---- particle systems: emit, update, kill and fill ---------------------------------------------------------------------------------
  * ParticleSystem::update (renderer/particle_system.cpp:1620-1656, per emitter :1456-1572) and Emitter::fillInstanceData (:1664-1686) for
- * every non-ribbon emitter of every registered system, in a fixed number of launches per step and with no host wait inside a step. The
+ * every emitter of every registered system, ribbon emitters included (below), in a fixed number of launches per step and with no host wait inside a step. The
  * programs are the engine's bytecode, decoded and validated once on the host; particle counts live on the device.
  *
  * An LmxParticles object uses its context's device and stream; destroy it before the context. Systems are numbered in the order they are
@@ -1017,7 +1017,7 @@ LMX_API int lmx_rays_device_scene_outputs(LmxContext* ctx, const LmxRaySceneHit*
  *     outside a conditional block, NOT outside one, BLEND / GRADIENT inside one, a conditional inside the true arm of a CMP_ELSE, a
  *     destination of type LITERAL, GLOBAL or SYSTEM_VALUE.
  *     Also: more than 8 EMIT instructions in one update program.
- *   LMX_ERR_UNSUPPORTED: MESH and SPLINE (they need the entity's mesh, pose and spline); ribbons stay with the engine.
+ *   LMX_ERR_UNSUPPORTED: MESH and SPLINE (they need the entity's mesh, pose and spline).
  * Sub-emission (EMIT inside a conditional block) runs on the device: the records are drained in the reference's order at the end of the
  *   emitter's update, before the system's next emitter updates, and the target's emit program runs init_emit_count times per record.
  * lmx_particles_reserve sets an emitter's capacity (rounded up to a multiple of four). An emission past it is counted and not written:
@@ -1027,7 +1027,37 @@ LMX_API int lmx_rays_device_scene_outputs(LmxContext* ctx, const LmxRaySceneHit*
  *   ((count + 3) & ~3) * outputs_count * 4 bytes at a 16-byte-aligned offset; rows between count and the next multiple of four are
  *   written and unspecified. Both enqueue and return
  *   (a step waits at most for the host-to-device copies of the step before the last).
- * RAND draws are counter based: keyed by (lmx_particles_set_seed, global emitter, step number, particle slot, instruction). */
+ * RAND draws are counter based: keyed by (lmx_particles_set_seed, global emitter, step number, particle slot, instruction).
+ *
+ * Ribbon emitters (updateRibbons :1405-1454, emitRibbonPoints :358-409, emitRibbons, killRibbon, applyTransform :1377-1403).
+ * lmx_particles_set_emitter_options gives an emitter what ParticleSystemResource::Emitter keeps next to its program; an emitter that never
+ *   gets options behaves as one with all of them zero. With max_ribbons > 0 it is a ribbon emitter: its channels are max_ribbons rings of
+ *   max_ribbon_length slots (rounded up to a multiple of four, as the resource loader does), its capacity is their product and is fixed.
+ *   Options and program may arrive in either order; what needs both is checked by the later call, what needs another emitter's options by
+ *   lmx_particles_step (or whichever call lays the buffers out first). Like set_program it lays the buffers out anew and resets every system.
+ *   LMX_ERR_UNSUPPORTED: max_ribbon_length > 1024 (past it the reference's chunk loop leaves its register pages and updates slots twice:
+ *     there is nothing to match); EMIT in a ribbon emitter's update program (ribbon-to-ribbon sub-emission is not run on the device).
+ *   LMX_ERR_INVALID: KILL in a ribbon emitter's update program (updateRibbons has no kill counter); an EMIT of a non-ribbon emitter that
+ *     targets a ribbon emitter (the reference drains it as if the rings were one flat array) - this one from lmx_particles_step;
+ *     max_ribbons x max_ribbon_length that overflows or exceeds 2^26 slots; lmx_particles_reserve on a ribbon emitter.
+ *   A refused call changes nothing: the object stays usable.
+ * A ribbon's {offset, length, emit_index} follows from counts the host computes, so ribbon state lives on the host: lmx_particles_ribbons
+ *   answers without touching the stream. LmxParticlesCounts::particles of a ribbon emitter is the sum of its ribbons' lengths.
+ * lmx_particles_step: the first frame is emitRibbons(init_ribbons_count); then emit_per_second's points go to EVERY ribbon and the update
+ *   program runs over ring slots [0, length) of every ribbon (it does not follow `offset`, as the reference's does not).
+ * lmx_particles_emit_ribbons / lmx_particles_kill_ribbon are enqueued in stream order; TOTAL_TIME and TIME_DELTA are what the last step left.
+ *   After a kill the ribbons above the killed one move down one index; an index past the ribbons does nothing.
+ * lmx_particles_apply_transforms is ParticleSystem::applyTransform of every system (only the transform's position is used) and also sets
+ *   the entity positions. An emitter with emit_move_distance > 0 whose squaredLength(pos - last_emit_point) exceeds emit_move_distance (fp64;
+ *   a squared length against an unsquared distance, as the reference compares) takes pos as its last_emit_point and emits: one point into
+ *   every ribbon, or one particle for a non-ribbon emitter, time step 0. last_emit_point starts at the origin and survives a reset.
+ * lmx_particles_fill packs a ribbon emitter's slice per ribbon: ribbon r's rows are its ring slots 0 .. length_r - 1 in slot order, from row
+ *   sum(length_q, q < r); LmxParticleRibbon::points_offset is that row x outputs_count x 4, what the renderer's ribbon loops
+ *   (pipeline.cpp:2876, :2932) assume. The slice has ((sum of lengths + 3) & ~3) x outputs_count x 4 bytes; the rows behind the sum are not written.
+ * RIBBON_INDEX reads the lane's own ribbon index in the emit, update and output programs of a ribbon emitter, 0 elsewhere. RAND's particle
+ *   slot is ribbon x max_ribbon_length + ring slot.
+ * lmx_particles_read_channels of a ribbon emitter returns ribbon r's ring at [r x max_ribbon_length, (r + 1) x max_ribbon_length) of every
+ *   channel; ring slots that hold no live point are unspecified. */
 typedef struct LmxParticles LmxParticles;
 typedef struct LmxParticleProgram {
 	const uint8_t* instructions;
@@ -1054,6 +1084,13 @@ typedef struct LmxParticlesDevice {
 	const LmxParticlesCounts* d_counts;/* one per emitter, current after every step */
 	uint32_t n_emitters, frame_bytes;  /* frame_bytes: what the buffer holds (every emitter at capacity) */
 } LmxParticlesDevice;
+typedef struct LmxParticleEmitterOptions {
+	uint32_t max_ribbons;          /* 0: not a ribbon emitter */
+	uint32_t max_ribbon_length;    /* rounded up to a multiple of 4, as the resource loader does (particle_system.cpp:189) */
+	uint32_t init_ribbons_count, tube_segments;
+	float emit_move_distance;      /* <= 0: no emission on movement; applies to ribbon and non-ribbon emitters */
+} LmxParticleEmitterOptions;
+typedef struct LmxParticleRibbon { uint32_t offset, length, emit_index, points_offset; } LmxParticleRibbon; /* points_offset: bytes from the start of the emitter's slice */
 enum { LMX_PARTICLES_GUARD_FLOATS = 64 }; /* behind every channel and behind the frame buffer: filled with 0xA5 bytes, never written by a kernel */
 LMX_API int lmx_particles_create(LmxContext* ctx, LmxParticles** out);
 LMX_API void lmx_particles_destroy(LmxParticles* ps);
@@ -1074,7 +1111,15 @@ LMX_API int lmx_particles_counts(LmxParticles* ps, LmxParticlesCounts* out, uint
 LMX_API int lmx_particles_read_channels(LmxParticles* ps, uint32_t system, uint32_t emitter, float* out, uint32_t cap_floats, uint32_t* out_stride);
 /* slices: one per emitter (cap_slices >= emitters); data (may be NULL): the frame buffer and its guard, cap_bytes >= frame_bytes + guard */
 LMX_API int lmx_particles_read_slices(LmxParticles* ps, LmxParticleSlice* slices, uint32_t cap_slices, void* data, uint32_t cap_bytes);
-/* Device pointers for GPU consumers, valid until the next reserve or set_program; stream-ordered behind lmx_particles_fill */
+/* Ribbon emitters (above). set_emitter_options resets every system, like set_program. */
+LMX_API int lmx_particles_set_emitter_options(LmxParticles* ps, uint32_t system, uint32_t emitter, const LmxParticleEmitterOptions* options);
+LMX_API int lmx_particles_emit_ribbons(LmxParticles* ps, uint32_t system, uint32_t emitter, uint32_t n);
+LMX_API int lmx_particles_kill_ribbon(LmxParticles* ps, uint32_t system, uint32_t emitter, uint32_t ribbon);
+/* ParticleSystem::applyTransform of every system: n_systems x 3 doubles */
+LMX_API int lmx_particles_apply_transforms(LmxParticles* ps, uint32_t n_systems, const double* pos_xyz);
+/* Emitter::ribbons as the calls so far left them (host state: no wait); *n: how many there are, LMX_ERR_CAPACITY when cap is less */
+LMX_API int lmx_particles_ribbons(LmxParticles* ps, uint32_t system, uint32_t emitter, LmxParticleRibbon* out, uint32_t cap, uint32_t* n);
+/* Device pointers for GPU consumers, valid until the next reserve, set_program or set_emitter_options; stream-ordered behind lmx_particles_fill */
 LMX_API int lmx_particles_device_outputs(LmxParticles* ps, LmxParticlesDevice* out);
 
 /* ------------------------------------------------------------------------------------------------------------------------------------

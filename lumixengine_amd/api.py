@@ -374,6 +374,11 @@ SYMBOLS = {
     "lmx_particles_read_channels": (_ci, [_vp, _u32, _u32, _vp, _u32, C.POINTER(_u32)]),
     "lmx_particles_read_slices": (_ci, [_vp, _vp, _u32, _vp, _u32]),
     "lmx_particles_device_outputs": (_ci, [_vp, _vp]),
+    "lmx_particles_set_emitter_options": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_particles_emit_ribbons": (_ci, [_vp, _u32, _u32, _u32]),
+    "lmx_particles_kill_ribbon": (_ci, [_vp, _u32, _u32, _u32]),
+    "lmx_particles_apply_transforms": (_ci, [_vp, _u32, _vp]),
+    "lmx_particles_ribbons": (_ci, [_vp, _u32, _u32, _vp, _u32, C.POINTER(_u32)]),
     "lmx_grass_create": (_ci, [_vp, C.POINTER(_vp)]),
     "lmx_grass_destroy": (None, [_vp]),
     "lmx_grass_set_terrains": (_ci, [_vp, _u32, _vp]),
@@ -1774,12 +1779,17 @@ class Skinning:
 
 PARTICLES_COUNTS = np.dtype([("particles", "<u4"), ("emit_index", "<u4"), ("overflow", "<u4"), ("killed", "<u4")])  # LmxParticlesCounts
 PARTICLE_SLICE = np.dtype([("offset", "<u4"), ("bytes", "<u4"), ("particles", "<u4"), ("outputs_count", "<u4")])  # LmxParticleSlice
+PARTICLE_RIBBON = np.dtype([("offset", "<u4"), ("length", "<u4"), ("emit_index", "<u4"), ("points_offset", "<u4")])  # LmxParticleRibbon
 PARTICLES_GUARD_FLOATS = 64
 
 
 class LmxParticleProgram(C.Structure):
     _fields_ = [("instructions", C.c_void_p), ("size", _u32), ("emit_offset", _u32), ("output_offset", _u32), ("channels_count", _u32), ("registers_count", _u32),
                 ("outputs_count", _u32), ("emit_inputs_count", _u32), ("init_emit_count", _u32), ("emit_per_second", _f32)]
+
+
+class LmxParticleEmitterOptions(C.Structure):
+    _fields_ = [("max_ribbons", _u32), ("max_ribbon_length", _u32), ("init_ribbons_count", _u32), ("tube_segments", _u32), ("emit_move_distance", _f32)]
 
 
 class LmxParticlesDevice(C.Structure):
@@ -1800,6 +1810,7 @@ class ParticleSystems:
         self.emitters = []  # (system, emitter) by global emitter index
         self.capacity = {}
         self.outputs = {}
+        self._ribbon = {}
 
     def close(self):
         if getattr(self, "h", None):
@@ -1838,6 +1849,36 @@ class ParticleSystems:
     def reserve(self, system: int, emitter: int, capacity: int):
         self.ctx.check(self.lib.lmx_particles_reserve(self.h, system, emitter, capacity))
         self.capacity[(system, emitter)] = (capacity + 3) & ~3
+
+    def setEmitterOptions(self, system: int, emitter: int, max_ribbons: int = 0, max_ribbon_length: int = 0, init_ribbons_count: int = 0, tube_segments: int = 0,
+                          emit_move_distance: float = 0.0):
+        """What ParticleSystemResource::Emitter keeps next to its program; max_ribbons > 0 makes a ribbon emitter of fixed capacity."""
+        o = LmxParticleEmitterOptions(max_ribbons, max_ribbon_length, init_ribbons_count, tube_segments, emit_move_distance)
+        self.ctx.check(self.lib.lmx_particles_set_emitter_options(self.h, system, emitter, C.byref(o)))
+        if max_ribbons:
+            self.capacity[(system, emitter)] = max_ribbons * ((max_ribbon_length + 3) & ~3)
+        elif self._ribbon.get((system, emitter)):
+            self.capacity[(system, emitter)] = 0
+        self._ribbon[(system, emitter)] = max_ribbons > 0
+
+    def emitRibbons(self, system: int, emitter: int, n: int):
+        self.ctx.check(self.lib.lmx_particles_emit_ribbons(self.h, system, emitter, n))
+
+    def killRibbon(self, system: int, emitter: int, ribbon: int):
+        self.ctx.check(self.lib.lmx_particles_kill_ribbon(self.h, system, emitter, ribbon))
+
+    def applyTransforms(self, pos):
+        """ParticleSystem::applyTransform of every system (positions only): emission on movement, and the entity positions."""
+        p = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        self.ctx.check(self.lib.lmx_particles_apply_transforms(self.h, len(p), _ptr(p) if len(p) else None))
+
+    def ribbons(self, system: int, emitter: int) -> np.ndarray:
+        """Emitter::ribbons with each ribbon's points_offset into the emitter's slice: host state, no wait."""
+        n = _u32()
+        self.lib.lmx_particles_ribbons(self.h, system, emitter, None, 0, C.byref(n))
+        out = np.zeros(n.value, PARTICLE_RIBBON)
+        self.ctx.check(self.lib.lmx_particles_ribbons(self.h, system, emitter, _ptr(out) if len(out) else None, len(out), C.byref(n)))
+        return out
 
     def reset(self, system: int = ALL):
         self.ctx.check(self.lib.lmx_particles_reset(self.h, system))

@@ -140,6 +140,7 @@ struct Decoder {
 				case P_KILL:
 					if (section != SEC_UPDATE || in_emit_block) return bad(at, "KILL outside a conditional block of the update program");
 					if (kills) *kills = true;
+					out.has_kill = true;
 					out.recs.push_back(r);
 					break;
 				case P_MESH: case P_SPLINE:
@@ -158,6 +159,7 @@ struct Decoder {
 					if (depth + 1 > PARTICLE_MAX_NESTING) return bad(at, "nesting deeper than the interpreter's stack");
 					if (out.emit_count >= PARTICLE_MAX_EMITS) return bad(at, "more than 8 EMIT instructions");
 					r.b = out.emit_count;
+					out.emit_target[out.emit_count] = r.a;
 					out.emit_group[out.emit_count++] = (uint8_t)(group < 255 ? group : 255);
 					out.has_emit = true;
 					out.recs.push_back(r);

@@ -65,7 +65,9 @@ struct ParticleProgram {
 	uint16_t shadow_mask = 0; // union of the wmasks: channels that need a snapshot while a killing block runs
 	uint32_t emit_count = 0;                      // EMIT instructions of the update program
 	uint8_t emit_group[PARTICLE_MAX_EMITS] = {};   // the whole-chunk conditional each sits in, counted from 0: records are drained block by block
+	uint32_t emit_target[PARTICLE_MAX_EMITS] = {}; // ... and the emitter of its system it emits into
 	bool has_emit = false, has_mesh_or_spline = false;
+	bool has_kill = false;                        // a KILL anywhere in the update program (refused for ribbon emitters)
 };
 
 enum ParticleDecodeResult { PD_OK = 0, PD_INVALID = 1 };

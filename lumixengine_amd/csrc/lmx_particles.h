@@ -30,6 +30,31 @@ struct ParticleEmitterDev {
 	uint32_t job_base;      // first of capacity x n_emit sub-emission jobs
 	uint64_t stage_base;    // word index of the staging records [slot][n_emit] of PARTICLE_STAGE_WORDS words
 	uint8_t emit_group[PARTICLE_MAX_EMITS];
+	// A ribbon emitter: capacity = max_ribbons rings of ribbon_len slots, ring p of channel c at c * stride + p * ribbon_len
+	uint32_t ribbon_len;    // max_ribbon_length, a multiple of four, <= 1024; 0: not a ribbon emitter
+	uint32_t max_ribbons;
+	uint32_t ribbon_base;   // first of max_ribbons ParticleRibbonDev records
+	uint32_t ribbon_ord;    // index among the ribbon emitters (ParticleRibbonCount)
+};
+
+// One live ribbon, by its index in Emitter::ribbons. The ring map: a ribbon keeps its physical ring for life, so killRibbon moves no bytes.
+struct ParticleRibbonDev {
+	uint32_t ring;          // physical ring of the emitter's channels
+	uint32_t length;
+	uint32_t row;           // first row of the packed slice: the lengths of the ribbons before it
+	uint32_t pad;
+};
+
+struct ParticleRibbonCount { // per ribbon emitter
+	uint32_t emitter, n_ribbons, total, pad; // total: the sum of the lengths = Emitter::particles_count
+};
+
+// One call of ParticleSystem::emitRibbonPoints. Its lanes are [first_lane, first_lane + min(count, ribbon_len)): one per ring slot that is hit
+struct ParticleRibbonJob {
+	uint32_t emitter, ribbon, ring;
+	uint32_t offset0, length0, emit_index0; // the ribbon before the call
+	uint32_t count, first_lane;
+	float total_time, time_step;
 };
 
 struct ParticleSystemDev {
@@ -72,6 +97,9 @@ struct ParticlesDevice {
 	float* frame;
 	uint32_t n_emitters, seed, step, frame_floats;
 	uint32_t level;          // only emitters with this index in their system take part; 0xffffffff: all
+	const ParticleRibbonDev* ribbons;         // the live ribbons of every ribbon emitter, as the host's last call left them
+	const ParticleRibbonCount* ribbon_counts; // per ribbon emitter
+	uint32_t n_ribbon_emitters;
 };
 
 size_t particle_chunk_lds_bytes(uint32_t registers, uint32_t shadow_channels);
@@ -82,5 +110,16 @@ hipError_t launch_particles_emit(hipStream_t s, const ParticlesDevice& d, const 
 hipError_t launch_particles_update(hipStream_t s, const ParticlesDevice& d, uint32_t max_chunks, uint32_t max_registers, uint32_t max_shadow, bool sub_emit);
 // slice offsets, then processChunk with the output program
 hipError_t launch_particles_fill(hipStream_t s, const ParticlesDevice& d, uint32_t max_chunks, uint32_t max_registers);
+
+// Ribbon emitters (particle_kernels.hip, k_particles_ribbon_*). `max_groups`: the largest number of 1024-lane blocks one ribbon emitter needs,
+// each holding floor(1024 / ribbon_len) whole ribbons.
+// emitRibbonPoints of every job: total_lanes = the sum of min(count, ribbon_len) over the jobs
+hipError_t launch_particles_ribbon_emit(hipStream_t s, const ParticlesDevice& d, const ParticleRibbonJob* jobs, uint32_t n_jobs, uint32_t total_lanes);
+// Emitter::particles_count of every ribbon emitter into the state records
+hipError_t launch_particles_ribbon_commit(hipStream_t s, const ParticlesDevice& d);
+// the update program over ring slots [0, length) of every ribbon (updateRibbons' chunk loop)
+hipError_t launch_particles_ribbon_update(hipStream_t s, const ParticlesDevice& d, uint32_t max_groups, uint32_t max_registers);
+// the output program into the packed rows of every ribbon; behind launch_particles_fill, which lays out the slices
+hipError_t launch_particles_ribbon_fill(hipStream_t s, const ParticlesDevice& d, uint32_t max_groups, uint32_t max_registers);
 
 } // namespace lmx

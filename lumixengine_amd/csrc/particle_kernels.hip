@@ -82,6 +82,8 @@ __device__ __forceinline__ float p_rand(uint32_t seed, uint32_t emitter, uint32_
 struct Lane {
 	float* ch;            // channel 0, slot 0 of the emitter
 	uint32_t stride, slot;
+	uint32_t rslot;       // the particle slot RAND is keyed by: `slot`, or ribbon x ribbon_len + ring slot where `ch` is a ribbon's ring
+	float ribbon_index;   // RIBBON_INDEX: the lane's own ribbon; 0 outside ribbon emitters
 	float* regs;          // LDS register pages
 	uint32_t rstride, lane;
 	const float* sysv;
@@ -101,6 +103,7 @@ __device__ __forceinline__ float lane_read(const Lane& L, const ParticleOperand&
 		case PS_SYSTEM_VALUE:
 			if (L.emitting && o.index == PSV_TOTAL_TIME) return L.total_time;
 			if (o.index == PSV_EMIT_INDEX) return L.emit_index;
+			if (o.index == PSV_RIBBON_INDEX) return L.ribbon_index;
 			return L.sysv[o.index];
 		case PS_GLOBAL: return L.globals[o.index];
 		case PS_OUT: return L.outp[o.index];
@@ -141,7 +144,7 @@ __device__ __forceinline__ bool run_scalar(Lane L, const ParticleRec* prog, uint
 			case P_CMP: case P_CMP_ELSE:
 				if (!(lane_read(L, r.o[0]) != 0.0f)) next = r.a;
 				break;
-			case P_RAND: lane_write(L, r.o[0], p_rand(L.seed, L.emitter, L.step, L.slot, r.a, r.o[1].value, r.o[2].value)); break;
+			case P_RAND: lane_write(L, r.o[0], p_rand(L.seed, L.emitter, L.step, L.rslot, r.a, r.o[1].value, r.o[2].value)); break;
 			case P_MULTIPLY_ADD: lane_write(L, r.o[0], f_add(f_mul(lane_read(L, r.o[1]), lane_read(L, r.o[2])), lane_read(L, r.o[3]))); break;
 			case P_MIX: { // lerp of core/math.cpp:190
 				const float a = lane_read(L, r.o[1]), b = lane_read(L, r.o[2]), t = lane_read(L, r.o[3]);
@@ -188,7 +191,7 @@ __device__ __forceinline__ void run_whole(const Lane& L, const ParticleRec& r, c
 		case P_COS: v = f_cos(lane_read(L, r.o[1])); break;
 		case P_SQRT: v = f_sqrt(lane_read(L, r.o[1])); break;
 		case P_NOISE: v = p_gnoise(lane_read(L, r.o[1])); break;
-		case P_RAND: v = p_rand(L.seed, L.emitter, L.step, L.slot, r.a, r.o[1].value, r.o[2].value); break;
+		case P_RAND: v = p_rand(L.seed, L.emitter, L.step, L.rslot, r.a, r.o[1].value, r.o[2].value); break;
 		case P_GRADIENT: {
 			const ParticleGradient& g = gradients[r.a];
 			const float arg = lane_read(L, r.o[1]);
@@ -248,6 +251,7 @@ __global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_emit(Particle
 	L.ch = d.channels + em.channel_base;
 	L.stride = em.stride;
 	L.slot = slot;
+	L.rslot = slot; L.ribbon_index = 0.0f;
 	L.regs = s_regs;
 	L.rstride = PARTICLE_EMIT_BLOCK;
 	L.lane = threadIdx.x;
@@ -290,7 +294,8 @@ template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particl
 	if (from >= st.count) return;
 	const ParticleEmitterDev em = d.emitters[e];
 	if (!FILL && d.level != 0xffffffffu && em.local != d.level) return;
-	const uint32_t n = min(PARTICLE_CHUNK, st.count - from), n4 = (n + 3u) & ~3u;
+	// (a ribbon emitter's points are k_particles_ribbon_chunk's: here its chunks have no particle, every lane idles through the program)
+	const uint32_t n = em.ribbon_len ? 0u : min(PARTICLE_CHUNK, st.count - from), n4 = (n + 3u) & ~3u;
 	const uint32_t lane = threadIdx.x;
 	const bool active = lane < n4;
 	const uint32_t n_shadow = FILL ? 0u : (uint32_t)__popc(em.shadow_mask);
@@ -305,6 +310,7 @@ template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particl
 	L.ch = d.channels + em.channel_base;
 	L.stride = em.stride;
 	L.slot = from + lane;
+	L.rslot = L.slot; L.ribbon_index = 0.0f;
 	L.regs = s_lds;
 	L.rstride = PARTICLE_CHUNK;
 	L.lane = lane;
@@ -393,6 +399,7 @@ __global__ void k_particles_plan(ParticlesDevice d) {
 	ParticleStateDev st = d.state[e];
 	const ParticleEmitterDev& em = d.emitters[e]; // (read in place: emit_group is indexed by a loop counter)
 	if (d.level != 0xffffffffu && em.local != d.level) return;
+	if (em.ribbon_len) return; // no kills, no EMIT: nothing to plan
 	uint32_t n_ops = 0, n_sub = 0;
 	const uint32_t updated = st.count; // what the chunk kernel ran over
 	st.killed = 0;
@@ -485,6 +492,7 @@ __global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_subemit(Parti
 			L.ch = d.channels + em.channel_base;
 			L.stride = em.stride;
 			L.slot = job.slot + i;
+			L.rslot = L.slot; L.ribbon_index = 0.0f;
 			L.regs = s_regs;
 			L.rstride = PARTICLE_EMIT_BLOCK;
 			L.lane = threadIdx.x;
@@ -540,6 +548,122 @@ __global__ void __launch_bounds__(PARTICLE_SCAN_BLOCK) k_particles_slices(Partic
 	}
 }
 
+// ---- ribbon emitters ----------------------------------------------------------------------------------------------------
+// A ribbon's {offset, length, emit_index} is host state (every count that moves it is known there); the device gets it in the jobs and in
+// the ParticleRibbonDev table and needs neither counters nor atomics.
+
+// ParticleSystem::emitRibbonPoints (:358-409) of every job of a pass. Point i of a call lands in ring slot (offset0 + length0 + i) % ribbon_len,
+// so lane j of a job owns the slot of points j, j + ribbon_len, ... and runs them in order: no two lanes write one slot. (The reference
+// takes the modulus of a u32 sum; the two agree until offset + length passes 2^32, which is where the slots are computed as it does.)
+__global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_ribbon_emit(ParticlesDevice d, const ParticleRibbonJob* __restrict__ jobs, uint32_t n_jobs, uint32_t total_lanes, const ParticleRec* __restrict__ prog) {
+	__shared__ float s_regs[PARTICLE_MAX_REGISTERS * PARTICLE_EMIT_BLOCK];
+	const uint32_t g = blockIdx.x * PARTICLE_EMIT_BLOCK + threadIdx.x;
+	if (g >= total_lanes) return;
+	uint32_t lo = 0, hi = n_jobs; // the last job whose first lane is <= g
+	while (hi - lo > 1) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (jobs[mid].first_lane <= g) lo = mid;
+		else hi = mid;
+	}
+	const ParticleRibbonJob job = jobs[lo];
+	const ParticleEmitterDev em = d.emitters[job.emitter];
+	const uint32_t len = em.ribbon_len;
+	if (!len || job.ring >= em.max_ribbons || job.length0 > len) return;
+	const uint32_t room = len - job.length0; // points that still grow the ribbon; the rest advance its offset
+	Lane L;
+	L.ch = d.channels + em.channel_base + (size_t)job.ring * len;
+	L.stride = em.stride;
+	L.ribbon_index = float(job.ribbon);
+	L.regs = s_regs;
+	L.rstride = PARTICLE_EMIT_BLOCK;
+	L.lane = threadIdx.x;
+	L.sysv = d.systems[em.system].values;
+	L.globals = d.globals + d.systems[em.system].globals_at;
+	L.outp = nullptr;
+	L.emitting = true;
+	L.seed = d.seed; L.emitter = job.emitter; L.step = d.step;
+	L.stage = nullptr; L.n_emit = 0;
+	float t = job.total_time; // the repeated sum c1 + d + d + ..., restarted for every ribbon
+	uint64_t summed = 0;
+	for (uint64_t i = g - job.first_lane; i < job.count; i += len) {
+		if (job.time_step != 0.0f)
+			for (; summed < i; ++summed) t += job.time_step;
+		const uint32_t length = i < room ? job.length0 + (uint32_t)i + 1u : len;
+		const uint32_t offset = i < room ? job.offset0 : job.offset0 + ((uint32_t)i + 1u - room);
+		L.slot = (offset + length - 1u) % len;
+		L.rslot = job.ribbon * len + L.slot;
+		for (uint32_t r = 0; r < PARTICLE_MAX_REGISTERS; ++r) s_regs[r * PARTICLE_EMIT_BLOCK + threadIdx.x] = 0.0f;
+		L.total_time = t;
+		L.emit_index = float(job.emit_index0 + (uint32_t)i);
+		(void)run_scalar(L, prog, em.prog_emit);
+	}
+}
+
+__global__ void k_particles_ribbon_commit(ParticlesDevice d) {
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= d.n_ribbon_emitters) return;
+	const ParticleRibbonCount rc = d.ribbon_counts[k];
+	d.state[rc.emitter].count = rc.total;
+}
+
+// processChunk over the ribbons of every ribbon emitter: a block takes floor(1024 / ribbon_len) whole ribbons, lane -> (ribbon, ring slot)
+// is fixed per emitter. <false>: the update program over ring slots [0, (length + 3) & ~3) as updateRibbons' chunk covers them (:1431-1439;
+// it does not follow `offset`). <true>: the output program over [0, length), each slot into its row of the ribbon's packed rows. Ribbon
+// emitters hold no KILL and no EMIT (refused when the program is set), so a conditional block is the per-lane interpreter and nothing more.
+template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particles_ribbon_chunk(ParticlesDevice d, const ParticleRec* __restrict__ prog, const ParticleGradient* __restrict__ gradients) {
+	LMX_DYNAMIC_LDS(float, s_lds); // [registers][1024] register pages
+	const ParticleRibbonCount rc = d.ribbon_counts[blockIdx.y];
+	const ParticleEmitterDev em = d.emitters[rc.emitter];
+	const uint32_t len = em.ribbon_len;
+	if (!len) return;
+	const uint32_t per = PARTICLE_CHUNK / len, first = blockIdx.x * per;
+	if (first >= rc.n_ribbons) return;
+	const uint32_t lane = threadIdx.x;
+	const uint32_t rl = lane / len, slot = lane - rl * len, ribbon = first + rl;
+	const bool live = rl < per && ribbon < rc.n_ribbons && ribbon < em.max_ribbons;
+	ParticleRibbonDev rb;
+	rb.ring = rb.length = rb.row = rb.pad = 0;
+	if (live) rb = d.ribbons[em.ribbon_base + ribbon];
+	const uint32_t n = min(rb.length, len);
+	const bool active = live && rb.ring < em.max_ribbons && slot < (FILL ? n : (n + 3u) & ~3u);
+	for (uint32_t r = 0; r < em.registers; ++r) s_lds[r * PARTICLE_CHUNK + lane] = 0.0f;
+
+	Lane L;
+	L.ch = d.channels + em.channel_base + (size_t)rb.ring * len;
+	L.stride = em.stride;
+	L.slot = slot;
+	L.rslot = ribbon * len + slot;
+	L.ribbon_index = float(ribbon);
+	L.regs = s_lds;
+	L.rstride = PARTICLE_CHUNK;
+	L.lane = lane;
+	L.sysv = d.systems[em.system].values;
+	L.globals = d.globals + d.systems[em.system].globals_at;
+	L.outp = FILL ? d.frame + d.slices[rc.emitter].offset / 4 + (size_t)(rb.row + slot) * em.outputs : nullptr;
+	L.total_time = 0.0f;
+	L.emit_index = L.sysv[PSV_EMIT_INDEX];
+	L.emitting = false;
+	L.seed = d.seed; L.emitter = rc.emitter; L.step = d.step;
+	L.stage = d.stage; L.n_emit = 0; // never used: no program of a ribbon emitter holds an EMIT (a null pointer here crashes ROCm 7.2's clang in SimplifyCFG)
+
+	uint32_t ip = FILL ? em.prog_output : em.prog_update;
+	for (;;) {
+		const ParticleRec& r = prog[ip];
+		const uint32_t op = r.op;
+		if (op == P_END) break;
+		if (op != P_CMP && op != P_CMP_ELSE) {
+			if (active) run_whole(L, r, gradients);
+			++ip;
+			continue;
+		}
+		if (active) {
+			const bool is_true = (f_bits(lane_read(L, r.o[0])) & 0x80000000u) && slot < n;
+			if (is_true || op == P_CMP_ELSE) (void)run_scalar(L, prog, is_true ? ip + 1 : r.a);
+		}
+		ip = r.c;
+	}
+}
+
 } // namespace
 
 size_t particle_chunk_lds_bytes(uint32_t registers, uint32_t shadow_channels) {
@@ -589,5 +713,33 @@ hipError_t launch_particles_fill(hipStream_t s, const ParticlesDevice& d, uint32
 	if (e != hipSuccess || !max_chunks) return e;
 	return launch_chunks<true>(s, d, max_chunks, particle_chunk_lds_bytes(max_registers, 0));
 }
+
+hipError_t launch_particles_ribbon_emit(hipStream_t s, const ParticlesDevice& d, const ParticleRibbonJob* jobs, uint32_t n_jobs, uint32_t total_lanes) {
+	if (!n_jobs || !total_lanes) return hipSuccess;
+	hipLaunchKernelGGL(k_particles_ribbon_emit, dim3((total_lanes + PARTICLE_EMIT_BLOCK - 1) / PARTICLE_EMIT_BLOCK), dim3(PARTICLE_EMIT_BLOCK), 0, s, d, jobs, n_jobs, total_lanes, d.prog);
+	return hipGetLastError();
+}
+
+hipError_t launch_particles_ribbon_commit(hipStream_t s, const ParticlesDevice& d) {
+	if (!d.n_ribbon_emitters) return hipSuccess;
+	hipLaunchKernelGGL(k_particles_ribbon_commit, dim3((d.n_ribbon_emitters + 255) / 256), dim3(256), 0, s, d);
+	return hipGetLastError();
+}
+
+template <bool FILL> static hipError_t launch_ribbon_chunks(hipStream_t s, const ParticlesDevice& d, uint32_t max_groups, uint32_t max_registers) {
+	if (!d.n_ribbon_emitters || !max_groups) return hipSuccess;
+	const size_t lds = (size_t)max_registers * PARTICLE_CHUNK * sizeof(float);
+#ifndef LMX_HOSTSIM
+	if (lds > 64 * 1024) {
+		const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_particles_ribbon_chunk<FILL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+	}
+#endif
+	hipLaunchKernelGGL(k_particles_ribbon_chunk<FILL>, dim3(max_groups, d.n_ribbon_emitters), dim3(PARTICLE_BLOCK), lds, s, d, d.prog, d.gradients);
+	return hipGetLastError();
+}
+
+hipError_t launch_particles_ribbon_update(hipStream_t s, const ParticlesDevice& d, uint32_t max_groups, uint32_t max_registers) { return launch_ribbon_chunks<false>(s, d, max_groups, max_registers); }
+hipError_t launch_particles_ribbon_fill(hipStream_t s, const ParticlesDevice& d, uint32_t max_groups, uint32_t max_registers) { return launch_ribbon_chunks<true>(s, d, max_groups, max_registers); }
 
 } // namespace lmx

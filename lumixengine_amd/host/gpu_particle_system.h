@@ -5,9 +5,13 @@
 // Pipeline::setupParticles (src/renderer/pipeline.cpp:2212-2308) asks every emitter for getParticlesDataSizeBytes() and
 // fillInstanceData(slice.ptr, ...). GpuParticleSystems keeps the same names over lmx_particles_*: add() registers a ParticleSystem with the
 // programs of its resource, update(dt) advances all of them, fillInstanceData() fills every emitter's slice into one device buffer and
-// getEmitters(system) names the slices - offset, bytes, particle count on the device, nothing of it read back. Ribbons, applyTransform /
-// emit_move_distance, autodestroy, MESH / SPLINE programs and the sort-key pairs stay with the engine: add() returns false for a system it
-// cannot take and the engine keeps updating that one itself (a system refused at its programs keeps its index, with empty programs).
+// getEmitters(system) names the slices - offset, bytes, particle count on the device, nothing of it read back. Ribbon emitters are taken
+// with their options; emitRibbons, killRibbon and applyTransforms forward ParticleSystem's calls of those names, and mirrorRibbons copies
+// the ribbon records (host state of the library: no wait) into Emitter::ribbons and particles_count, so that the ribbon loops of
+// Pipeline's createCommands (pipeline.cpp:2865, :2919) draw from the device slice unchanged - the slice is packed per ribbon, which is
+// the layout those loops assume. Autodestroy, MESH / SPLINE programs and the sort-key pairs stay with the engine: add() returns false for
+// a system it cannot take and the engine keeps updating that one itself (a system refused at its programs keeps its index, with empty
+// programs).
 //
 // `System` is ParticleSystem inside the engine (-DLMX_WITH_LUMIX_HEADERS); a standalone build passes any type with getResource(),
 // m_globals, m_world and m_entity (tests/cpp/lumix_compat_particles.h).
@@ -47,7 +51,7 @@ struct GpuParticleSystems {
 		if (!res || !res->isReady()) return false;
 		auto& emitters = res->getEmitters();
 		for (const auto& e : emitters)
-			if (e.max_ribbons > 0) return false; // ribbons: updateRibbons stays with the engine
+			if (e.max_ribbons > 0 && !hasRibbonFields(e, 0)) return false; // a resource type without the ribbon fields: stays with the engine
 		u32 index = 0;
 		if (lmx_particles_add_system(m_ps, (u32)emitters.size(), (u32)system.m_globals.size(), &index) != LMX_OK) return false;
 		m_first.push_back((u32)m_emitters.size());
@@ -63,7 +67,12 @@ struct GpuParticleSystems {
 			if (e.emit_registers_count > p.registers_count) p.registers_count = e.emit_registers_count;
 			p.outputs_count = e.outputs_count; p.emit_inputs_count = e.emit_inputs_count;
 			p.init_emit_count = e.init_emit_count; p.emit_per_second = e.emit_per_second;
-			ok = ok && lmx_particles_set_program(m_ps, index, k, &p) == LMX_OK && lmx_particles_reserve(m_ps, index, k, capacity) == LMX_OK;
+			LmxParticleEmitterOptions o = {};
+			o.max_ribbons = e.max_ribbons;
+			ribbonOptions(e, o, 0);
+			ok = ok && lmx_particles_set_program(m_ps, index, k, &p) == LMX_OK && lmx_particles_set_emitter_options(m_ps, index, k, &o) == LMX_OK;
+			if (e.max_ribbons == 0) ok = ok && lmx_particles_reserve(m_ps, index, k, capacity) == LMX_OK; // (a ribbon emitter's capacity is max_ribbons x max_ribbon_length)
+			checkStride(e, 0);
 			m_emitters.push_back(Emitter{(u32)m_emitters.size(), e.outputs_count, nullptr});
 			++k;
 		}
@@ -74,7 +83,9 @@ struct GpuParticleSystems {
 			static const uint8_t nothing[3] = {0, 0, 0}; // END | END | END
 			LmxParticleProgram p = {};
 			p.instructions = nothing; p.size = 3; p.emit_offset = 1; p.output_offset = 2;
+			const LmxParticleEmitterOptions none = {};
 			for (u32 e = 0; e < k; ++e) {
+				lmx_particles_set_emitter_options(m_ps, index, e, &none);
 				lmx_particles_set_program(m_ps, index, e, &p);
 				lmx_particles_reserve(m_ps, index, e, 0);
 			}
@@ -108,11 +119,55 @@ struct GpuParticleSystems {
 		return Span<const Emitter>(m_emitters.data() + first, (uint64_t)(end - first));
 	}
 
+	// ParticleSystem::emitRibbons / killRibbon of a registered system: enqueued in stream order
+	bool emitRibbons(u32 index, u32 emitter, u32 num_ribbons) { return lmx_particles_emit_ribbons(m_ps, index, emitter, num_ribbons) == LMX_OK; }
+	bool killRibbon(u32 index, u32 emitter, u32 ribbon) { return lmx_particles_kill_ribbon(m_ps, index, emitter, ribbon) == LMX_OK; }
+
+	// ParticleSystem::applyTransform of every registered system with the positions of the last sync(): emission on movement
+	bool applyTransforms() { return lmx_particles_apply_transforms(m_ps, (u32)(m_positions.size() / 3), m_positions.data()) == LMX_OK; }
+
+	// Emitter::ribbons and particles_count of every ribbon emitter of a registered system, as the calls so far left them (no wait): the
+	// engine's ribbon loops read ribbon.length and advance by length x stride, which is LmxParticleRibbon::points_offset.
+	// `emitters` is the system's own Array<Emitter> (ParticleSystem keeps it private: the engine build befriends the caller).
+	template <typename Emitters> bool mirrorRibbons(u32 index, Emitters& emitters) {
+		bool ok = true;
+		u32 k = 0;
+		for (auto& e : emitters) {
+			if (e.resource_emitter.max_ribbons > 0) {
+				u32 n = 0;
+				m_ribbons.resize(e.resource_emitter.max_ribbons);
+				ok = ok && lmx_particles_ribbons(m_ps, index, k, m_ribbons.data(), (u32)m_ribbons.size(), &n) == LMX_OK;
+				e.ribbons.resize(ok ? n : 0);
+				u32 total = 0;
+				for (u32 r = 0; r < (u32)e.ribbons.size(); ++r) {
+					e.ribbons[r].offset = m_ribbons[r].offset; e.ribbons[r].length = m_ribbons[r].length; e.ribbons[r].emit_index = m_ribbons[r].emit_index;
+					total += m_ribbons[r].length;
+				}
+				e.particles_count = total;
+			}
+			++k;
+		}
+		return ok;
+	}
+
 	bool reset(u32 index) { return lmx_particles_reset(m_ps, index) == LMX_OK; } // ParticleSystem::reset
 	const char* lastError() const { return lmx_last_error(m_ctx); }
 	LmxParticles* handle() const { return m_ps; }
 
 private:
+	// The ribbon fields of ParticleSystemResource::Emitter, where the resource type has them (the engine's does)
+	template <typename E> static auto hasRibbonFields(const E& e, int) -> decltype(e.max_ribbon_length, e.init_ribbons_count, e.emit_move_distance, true) { return true; }
+	template <typename E> static bool hasRibbonFields(const E&, long) { return false; }
+	template <typename E> static auto ribbonOptions(const E& e, LmxParticleEmitterOptions& o, int) -> decltype(e.max_ribbon_length, e.init_ribbons_count, e.tube_segments, e.emit_move_distance, void()) {
+		o.max_ribbon_length = e.max_ribbon_length; o.init_ribbons_count = e.init_ribbons_count; o.tube_segments = e.tube_segments;
+		o.emit_move_distance = e.emit_move_distance;
+	}
+	template <typename E> static void ribbonOptions(const E&, LmxParticleEmitterOptions&, long) {}
+	// the renderer reads the slice with the emitter's vertex declaration: one float per output
+	template <typename E> static auto checkStride(const E& e, int) -> decltype(e.vertex_decl.getStride(), void()) { ASSERT(e.vertex_decl.getStride() == e.outputs_count * sizeof(float)); }
+	template <typename E> static void checkStride(const E&, long) {}
+
+	std::vector<LmxParticleRibbon> m_ribbons;
 	LmxContext* m_ctx;
 	LmxParticles* m_ps = nullptr;
 	std::vector<u32> m_first;
