@@ -1016,8 +1016,23 @@ LMX_API int lmx_rays_device_scene_outputs(LmxContext* ctx, const LmxRaySceneHit*
  *     past the program, nesting deeper than 4, a GRADIENT with < 2 or > 8 keys, an EMIT target out of range, a missing END, KILL / EMIT
  *     outside a conditional block, NOT outside one, BLEND / GRADIENT inside one, a conditional inside the true arm of a CMP_ELSE, a
  *     destination of type LITERAL, GLOBAL or SYSTEM_VALUE.
- *     Also: more than 8 EMIT instructions in one update program.
- *   LMX_ERR_UNSUPPORTED: MESH and SPLINE (they need the entity's mesh, pose and spline).
+ *     Also: more than 8 EMIT instructions in one update program; a MESH / SPLINE subindex above 2; a MESH index that is a GLOBAL, a
+ *     SYSTEM_VALUE or a negative LITERAL (it could not take the drawn vertex).
+ *   LMX_ERR_UNSUPPORTED: MESH (SPLINE) in a system that has not declared its mesh source (spline), see below; MESH outside a conditional
+ *     block or the emit program and whole-chunk SPLINE into a channel or register (the reference asserts); MESH / SPLINE inside an EMIT block.
+ * MESH and SPLINE (run :741-798, processChunk :1189-1219) read what the entity of the system carries, declared per system
+ *   BEFORE lmx_particles_set_program: lmx_particles_set_mesh_source names a mesh of lmx_particles_add_mesh (shared between systems;
+ *   0xffffffff: no model instance, model not ready or no mesh - the run of a particle that reaches a MESH ends there with its verdict so
+ *   far), the skin instance whose palette the last lmx_skin_run left (0xffffffff: no pose) and flags, bit 0 = the model has bones (then the
+ *   mesh must carry a skin: LMX_ERR_INVALID_ARGUMENT otherwise; bones and no pose: the index is drawn, then the run ends).
+ *   lmx_particles_set_spline gives the spline's points; n_points = 0: no spline component (a scalar run ends at a SPLINE, a whole-chunk
+ *   program stops for the whole chunk and what its remaining instructions would have written is unspecified); 1 or 2 points:
+ *   LMX_ERR_INVALID_ARGUMENT (the reference reads outside its array). Later calls of either setter change the tables in stream order - the
+ *   next step or fill reads them - and neither lay the buffers out anew nor reset a system. lmx_particles_step / lmx_particles_fill answer
+ *   LMX_ERR_NOT_BUILT while a declared skin instance is past the skinning module's instances or no lmx_skin_run has left a palette.
+ *   lmx_particles_clear_meshes forgets every mesh; a source that named one then has no mesh until it is set again.
+ *   A MESH whose index is negative draws float(r % n_vertices) into it, r keyed by (seed, global emitter, step, particle slot,
+ *   0x80000000 + the MESH's ordinal by byte offset); u32(index + 0.5f) converts as x86-64 does and an index >= n_vertices reads vertex 0.
  * Sub-emission (EMIT inside a conditional block) runs on the device: the records are drained in the reference's order at the end of the
  *   emitter's update, before the system's next emitter updates, and the target's emit program runs init_emit_count times per record.
  * lmx_particles_reserve sets an emitter's capacity (rounded up to a multiple of four). An emission past it is counted and not written:
@@ -1091,6 +1106,12 @@ typedef struct LmxParticleEmitterOptions {
 	float emit_move_distance;      /* <= 0: no emission on movement; applies to ribbon and non-ribbon emitters */
 } LmxParticleEmitterOptions;
 typedef struct LmxParticleRibbon { uint32_t offset, length, emit_index, points_offset; } LmxParticleRibbon; /* points_offset: bytes from the start of the emitter's slice */
+typedef struct LmxParticleMeshSource {
+	uint32_t mesh;          /* of lmx_particles_add_mesh; 0xffffffff: none */
+	uint32_t skin_instance; /* of lmx_skin_set_instances; 0xffffffff: no pose */
+	uint32_t flags;         /* LMX_PARTICLE_MESH_HAS_BONES */
+} LmxParticleMeshSource;
+enum { LMX_PARTICLE_MESH_HAS_BONES = 1 };
 enum { LMX_PARTICLES_GUARD_FLOATS = 64 }; /* behind every channel and behind the frame buffer: filled with 0xA5 bytes, never written by a kernel */
 LMX_API int lmx_particles_create(LmxContext* ctx, LmxParticles** out);
 LMX_API void lmx_particles_destroy(LmxParticles* ps);
@@ -1119,6 +1140,11 @@ LMX_API int lmx_particles_kill_ribbon(LmxParticles* ps, uint32_t system, uint32_
 LMX_API int lmx_particles_apply_transforms(LmxParticles* ps, uint32_t n_systems, const double* pos_xyz);
 /* Emitter::ribbons as the calls so far left them (host state: no wait); *n: how many there are, LMX_ERR_CAPACITY when cap is less */
 LMX_API int lmx_particles_ribbons(LmxParticles* ps, uint32_t system, uint32_t emitter, LmxParticleRibbon* out, uint32_t cap, uint32_t* n);
+/* What MESH and SPLINE read (above). positions_xyz: n_verts x 3 floats; skin: n_verts records or NULL */
+LMX_API int lmx_particles_add_mesh(LmxParticles* ps, uint32_t n_verts, const float* positions_xyz, const LmxSkin* skin, uint32_t* out_mesh);
+LMX_API int lmx_particles_clear_meshes(LmxParticles* ps);
+LMX_API int lmx_particles_set_mesh_source(LmxParticles* ps, uint32_t system, const LmxParticleMeshSource* source);
+LMX_API int lmx_particles_set_spline(LmxParticles* ps, uint32_t system, const float* points_xyz, uint32_t n_points);
 /* Device pointers for GPU consumers, valid until the next reserve, set_program or set_emitter_options; stream-ordered behind lmx_particles_fill */
 LMX_API int lmx_particles_device_outputs(LmxParticles* ps, LmxParticlesDevice* out);
 

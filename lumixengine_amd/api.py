@@ -379,6 +379,10 @@ SYMBOLS = {
     "lmx_particles_kill_ribbon": (_ci, [_vp, _u32, _u32, _u32]),
     "lmx_particles_apply_transforms": (_ci, [_vp, _u32, _vp]),
     "lmx_particles_ribbons": (_ci, [_vp, _u32, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_particles_add_mesh": (_ci, [_vp, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "lmx_particles_clear_meshes": (_ci, [_vp]),
+    "lmx_particles_set_mesh_source": (_ci, [_vp, _u32, _vp]),
+    "lmx_particles_set_spline": (_ci, [_vp, _u32, _vp, _u32]),
     "lmx_grass_create": (_ci, [_vp, C.POINTER(_vp)]),
     "lmx_grass_destroy": (None, [_vp]),
     "lmx_grass_set_terrains": (_ci, [_vp, _u32, _vp]),
@@ -1792,6 +1796,13 @@ class LmxParticleEmitterOptions(C.Structure):
     _fields_ = [("max_ribbons", _u32), ("max_ribbon_length", _u32), ("init_ribbons_count", _u32), ("tube_segments", _u32), ("emit_move_distance", _f32)]
 
 
+class LmxParticleMeshSource(C.Structure):
+    _fields_ = [("mesh", _u32), ("skin_instance", _u32), ("flags", _u32)]
+
+
+PARTICLE_MESH_HAS_BONES = 1
+
+
 class LmxParticlesDevice(C.Structure):
     _fields_ = [("d_frame", C.c_void_p), ("d_slices", C.c_void_p), ("d_counts", C.c_void_p), ("n_emitters", _u32), ("frame_bytes", _u32)]
 
@@ -1879,6 +1890,33 @@ class ParticleSystems:
         out = np.zeros(n.value, PARTICLE_RIBBON)
         self.ctx.check(self.lib.lmx_particles_ribbons(self.h, system, emitter, _ptr(out) if len(out) else None, len(out), C.byref(n)))
         return out
+
+    # ---- what MESH and SPLINE read: declared per system before setProgram ----
+    NONE = 0xFFFFFFFF
+
+    def addMesh(self, positions, skin=None) -> int:
+        """Mesh 0 of a model (positions [n, 3], optionally SKIN records); shared by every system whose source names it."""
+        positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        sk = np.ascontiguousarray(skin, SKIN) if skin is not None else None
+        assert sk is None or len(sk) == len(positions)
+        out = _u32()
+        self.ctx.check(self.lib.lmx_particles_add_mesh(self.h, len(positions), _ptr(positions) if len(positions) else None, _ptr(sk) if sk is not None else None,
+                                                       C.byref(out)))
+        return out.value
+
+    def clearMeshes(self):
+        self.ctx.check(self.lib.lmx_particles_clear_meshes(self.h))
+
+    def setMeshSource(self, system: int, mesh: int = NONE, skin_instance: int = NONE, flags: int = 0):
+        """The entity's model for MESH: a mesh of addMesh (NONE: no model), the skin instance whose palette Skinning.run left (NONE: no pose),
+        PARTICLE_MESH_HAS_BONES."""
+        src = LmxParticleMeshSource(mesh, skin_instance, flags)
+        self.ctx.check(self.lib.lmx_particles_set_mesh_source(self.h, system, C.byref(src)))
+
+    def setSpline(self, system: int, points=None):
+        """The entity's spline for SPLINE ([n, 3], n >= 3); None or empty: no spline component."""
+        p = np.ascontiguousarray(points if points is not None else [], np.float32).reshape(-1, 3)
+        self.ctx.check(self.lib.lmx_particles_set_spline(self.h, system, _ptr(p) if len(p) else None, len(p)))
 
     def reset(self, system: int = ALL):
         self.ctx.check(self.lib.lmx_particles_reset(self.h, system))

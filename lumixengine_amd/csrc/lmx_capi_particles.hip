@@ -34,7 +34,19 @@ struct LmxParticles {
 		std::vector<float> globals;
 		double pos[3] = {0, 0, 0};
 		float total_time = 0.0f; // ParticleSystem::m_total_time
+		// what MESH / SPLINE read. A declaration, "none" included, is what lets set_program accept the instruction
+		bool mesh_declared = false, spline_declared = false;
+		LmxParticleMeshSource source = {PARTICLE_NO_SOURCE, PARTICLE_NO_SOURCE, 0};
+		std::vector<float> spline; // xyz per point; empty: no spline component
 	};
+	struct Mesh { uint32_t vert_at, n_verts, skin_at; }; // skin_at = PARTICLE_NO_SOURCE: no skin
+	std::vector<Mesh> meshes; // shared between the systems
+	std::vector<float> mesh_positions;
+	std::vector<LmxSkin> mesh_skins;
+	bool meshes_changed = false, splines_changed = false; // the device arrays are older than the host's
+	bool any_source = false; // a system has declared a source: until then the table is all "none" and a call has nothing to resolve
+	std::vector<ParticleSourceDev> src_host, src_up[2]; // the table the device holds; what a call uploads (as sys_up)
+	std::vector<float> spline_up[2];
 	std::vector<System> systems;
 	std::vector<Emitter> emitters;
 	bool dirty = true; // the device tables and buffers are older than the registered programs / capacities
@@ -73,6 +85,9 @@ struct LmxParticles {
 	DevBuf<ParticleRibbonJob> d_rjobs_first, d_rjobs_rate;
 	DevBuf<ParticleRibbonDev> d_ribbons;
 	DevBuf<ParticleRibbonCount> d_ribbon_counts;
+	DevBuf<ParticleSourceDev> d_sources;
+	DevBuf<float> d_mesh_positions, d_spline;
+	DevBuf<LmxSkin> d_mesh_skins;
 
 	ParticlesDevice dev() const {
 		ParticlesDevice d;
@@ -80,6 +95,8 @@ struct LmxParticles {
 		d.channels = d_channels.p; d.state = d_state.p; d.kill = d_kill.p; d.ops = d_ops.p; d.n_ops = d_n_ops.p; d.slices = d_slices.p; d.frame = d_frame.p;
 		d.stage = d_stage.p; d.sub_jobs = d_sub_jobs.p; d.n_sub = d_n_sub.p; d.level = 0xffffffffu;
 		d.ribbons = d_ribbons.p; d.ribbon_counts = d_ribbon_counts.p; d.n_ribbon_emitters = n_ribbon_emitters;
+		d.sources = d_sources.p; d.mesh_positions = d_mesh_positions.p; d.mesh_skins = d_mesh_skins.p; d.spline_points = d_spline.p;
+		d.palette = ctx->skin.d_palette.p;
 		d.n_emitters = (uint32_t)emitters.size(); d.seed = seed; d.step = step; d.frame_floats = frame_floats;
 		return d;
 	}
@@ -193,6 +210,80 @@ int upload_ribbons(LmxParticles* ps, uint32_t set) {
 	LMX_HIP(ctx, launch_particles_ribbon_commit(ctx->stream, ps->dev()));
 	ps->ribbons_changed = false;
 	return LMX_OK;
+}
+
+// The per-system source records as this moment's host state gives them: the mesh and spline tables, and the palette the last lmx_skin_run
+// left for the declared skin instance (read as k_ray_narrow reads it: the instance's bone range of the one palette buffer).
+int resolve_sources(LmxParticles* ps, std::vector<ParticleSourceDev>& out) {
+	LmxContext* ctx = ps->ctx;
+	const SkinState& sk = ctx->skin;
+	out.assign(ps->systems.size(), ParticleSourceDev{0, 0, PARTICLE_NO_SOURCE, PARTICLE_NO_SOURCE, 0, 0, 0, 0});
+	uint32_t spline_at = 0;
+	for (size_t s = 0; s < ps->systems.size(); ++s) {
+		const LmxParticles::System& sy = ps->systems[s];
+		ParticleSourceDev& r = out[s];
+		r.spline_at = spline_at;
+		r.n_points = (uint32_t)(sy.spline.size() / 3);
+		spline_at += r.n_points;
+		if (!sy.mesh_declared) continue;
+		if (sy.source.mesh != PARTICLE_NO_SOURCE) { // (< meshes.size(): checked by the setter, reset by clear_meshes)
+			const LmxParticles::Mesh& m = ps->meshes[sy.source.mesh];
+			r.mesh_at = m.vert_at; r.n_verts = m.n_verts; r.skin_at = m.skin_at;
+		}
+		r.flags = sy.source.flags & PARTICLE_SOURCE_BONES;
+		if (sy.source.skin_instance != PARTICLE_NO_SOURCE) {
+			if (!sk.palette_valid || !sk.d_palette.p) return fail(ctx, LMX_ERR_NOT_BUILT, "particle system %zu reads the pose of skin instance %u: no lmx_skin_run has left a palette", s, sy.source.skin_instance);
+			if (sy.source.skin_instance >= sk.inst.size()) return fail(ctx, LMX_ERR_NOT_BUILT, "particle system %zu reads the pose of skin instance %u: the skinning module has %zu", s, sy.source.skin_instance, sk.inst.size());
+			r.palette_at = sk.inst[sy.source.skin_instance].bone_offset;
+			r.n_bones = sk.inst[sy.source.skin_instance].n_bones;
+		}
+	}
+	return LMX_OK;
+}
+
+// Uploads what of the source tables changed, inside a begin_upload / end_upload pair (`set`): in stream order, no buffer of the particles is
+// touched. The mesh arrays change only when a mesh is added or all are cleared: that copy is waited for.
+int upload_sources(LmxParticles* ps, uint32_t set, const std::vector<ParticleSourceDev>& now) {
+	LmxContext* ctx = ps->ctx;
+	if (ps->meshes_changed) {
+		LMX_HIP(ctx, upload_on_stream(ps->d_mesh_positions, ps->mesh_positions, ctx->stream));
+		LMX_HIP(ctx, upload_on_stream(ps->d_mesh_skins, ps->mesh_skins, ctx->stream));
+		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		ps->meshes_changed = false;
+	}
+	if (ps->splines_changed) {
+		std::vector<float>& up = ps->spline_up[set];
+		up.clear();
+		for (const LmxParticles::System& sy : ps->systems) up.insert(up.end(), sy.spline.begin(), sy.spline.end());
+		LMX_HIP(ctx, upload_on_stream(ps->d_spline, up, ctx->stream));
+		ps->splines_changed = false;
+	}
+	if (now.size() != ps->src_host.size() || (!now.empty() && memcmp(now.data(), ps->src_host.data(), now.size() * sizeof(ParticleSourceDev)) != 0)) {
+		ps->src_up[set] = now;
+		LMX_HIP(ctx, upload_on_stream(ps->d_sources, ps->src_up[set], ctx->stream));
+		ps->src_host = now;
+	}
+	return LMX_OK;
+}
+// nothing declared anywhere and the device holds the all-"none" table of this many systems: a step or fill spends nothing on the sources
+bool sources_quiet(const LmxParticles* ps) {
+	return !ps->any_source && !ps->meshes_changed && !ps->splines_changed && ps->src_host.size() == ps->systems.size();
+}
+bool sources_stale(const LmxParticles* ps, const std::vector<ParticleSourceDev>& now) {
+	return ps->meshes_changed || ps->splines_changed || now.size() != ps->src_host.size() ||
+	       (!now.empty() && memcmp(now.data(), ps->src_host.data(), now.size() * sizeof(ParticleSourceDev)) != 0);
+}
+
+// ... for a call that runs programs and has no upload of its own to put them in
+int sync_sources(LmxParticles* ps) {
+	if (sources_quiet(ps)) return LMX_OK;
+	std::vector<ParticleSourceDev> now;
+	if (int rc = resolve_sources(ps, now)) return rc;
+	if (!sources_stale(ps, now)) return LMX_OK;
+	uint32_t set;
+	if (int rc = begin_upload(ps, &set)) return rc;
+	if (int rc = upload_sources(ps, set, now)) return rc;
+	return end_upload(ps, set);
 }
 
 // What a ribbon emitter's program may not hold (include/lumix_mi355.h): checked by whichever of set_program / set_emitter_options comes later
@@ -371,10 +462,12 @@ int lmx_particles_set_program(LmxParticles* ps, uint32_t system, uint32_t emitte
 	desc.emit_inputs_count = p->emit_inputs_count;
 	desc.n_emitters = ps->systems[system].n;
 	desc.n_globals = (uint32_t)ps->systems[system].globals.size();
+	desc.sources = (ps->systems[system].mesh_declared ? PARTICLE_SRC_MESH : 0u) | (ps->systems[system].spline_declared ? PARTICLE_SRC_SPLINE : 0u);
 	ParticleProgram prog;
 	std::string err;
-	if (particle_program_decode(desc, prog, err) != PD_OK) return fail(ctx, LMX_ERR_INVALID, "%s", err.c_str());
-	if (prog.has_mesh_or_spline) return fail(ctx, LMX_ERR_UNSUPPORTED, "MESH / SPLINE instructions need the entity's mesh, pose and spline: not run on the device");
+	const ParticleDecodeResult decoded = particle_program_decode(desc, prog, err);
+	if (decoded != PD_OK) return fail(ctx, decoded == PD_UNSUPPORTED ? LMX_ERR_UNSUPPORTED : LMX_ERR_INVALID, "%s", err.c_str());
+	if (prog.stopped) return fail(ctx, LMX_ERR_UNSUPPORTED, "MESH / SPLINE instructions need the entity's mesh, pose and spline: not run on the device");
 	if (!(p->emit_per_second == p->emit_per_second)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "emit_per_second is not a number");
 	LmxParticles::Emitter& em = ps->emitters[e];
 	if (em.is_ribbon())
@@ -447,8 +540,14 @@ int lmx_particles_step(LmxParticles* ps, float dt) {
 	LMX_CHECK_PARTICLES(ps);
 	if (int rc = build(ps)) return rc;
 	if (ps->emitters.empty()) return LMX_OK;
+	std::vector<ParticleSourceDev> sources;
+	const bool quiet = sources_quiet(ps);
+	if (!quiet)
+		if (int rc = resolve_sources(ps, sources)) return rc; // (before any host state moves: a refused step changes nothing)
 	uint32_t set;
 	if (int rc = begin_upload(ps, &set)) return rc;
+	if (!quiet)
+		if (int rc = upload_sources(ps, set, sources)) return rc;
 	std::vector<ParticleEmitJob>&jobs_first = ps->jobs_first_up[set], &jobs_rate = ps->jobs_rate_up[set];
 	std::vector<ParticleRibbonJob>&rjobs_first = ps->rjobs_first_up[set], &rjobs_rate = ps->rjobs_rate_up[set];
 	uint32_t max_first = 0, max_rate = 0, lanes_first = 0, lanes_rate = 0;
@@ -530,6 +629,7 @@ int lmx_particles_fill(LmxParticles* ps) {
 	LMX_CHECK_PARTICLES(ps);
 	if (int rc = build(ps)) return rc;
 	if (ps->emitters.empty()) return LMX_OK;
+	if (int rc = sync_sources(ps)) return rc;
 	LMX_HIP(ctx, launch_particles_fill(ctx->stream, ps->dev(), ps->max_chunks, ps->max_registers));
 	LMX_HIP(ctx, launch_particles_ribbon_fill(ctx->stream, ps->dev(), ps->max_groups, ps->max_registers));
 	return LMX_OK;
@@ -615,6 +715,7 @@ int lmx_particles_emit_ribbons(LmxParticles* ps, uint32_t system, uint32_t emitt
 	if (int rc = find_emitter(ps, system, emitter, &e)) return rc;
 	if (int rc = build(ps)) return rc;
 	if (!ps->emitters[e].is_ribbon()) return LMX_OK; // (emitRibbons clamps to max_ribbons = 0)
+	if (int rc = sync_sources(ps)) return rc;
 	uint32_t set, lanes = 0;
 	if (int rc = begin_upload(ps, &set)) return rc;
 	const LmxParticles::System& sy = ps->systems[system];
@@ -653,6 +754,7 @@ int lmx_particles_apply_transforms(LmxParticles* ps, uint32_t n_systems, const d
 	if (n_systems != ps->systems.size() || (n_systems && !pos_xyz)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "%zu particle systems registered", ps->systems.size());
 	if (int rc = build(ps)) return rc;
 	if (ps->emitters.empty()) return LMX_OK;
+	if (int rc = sync_sources(ps)) return rc;
 	uint32_t set, lanes = 0, max_count = 0;
 	if (int rc = begin_upload(ps, &set)) return rc;
 	std::vector<ParticleEmitJob>& jobs = ps->jobs_first_up[set];
@@ -704,6 +806,63 @@ int lmx_particles_ribbons(LmxParticles* ps, uint32_t system, uint32_t emitter, L
 		out[r] = LmxParticleRibbon{em.ribbons[r].offset, em.ribbons[r].length, em.ribbons[r].emit_index, row * em.outputs * 4u};
 		row += em.ribbons[r].length;
 	}
+	return LMX_OK;
+}
+
+int lmx_particles_add_mesh(LmxParticles* ps, uint32_t n_verts, const float* positions_xyz, const LmxSkin* skin, uint32_t* out_mesh) {
+	LMX_CHECK_PARTICLES(ps);
+	if (!n_verts || !positions_xyz) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "a mesh needs at least one vertex");
+	if (ps->mesh_positions.size() / 3 + (uint64_t)n_verts > (1u << 27)) return fail(ctx, LMX_ERR_CAPACITY, "more than 2^27 mesh vertices"); // (the kernels address both tables with 32-bit byte offsets)
+	LmxParticles::Mesh m;
+	m.vert_at = (uint32_t)(ps->mesh_positions.size() / 3);
+	m.n_verts = n_verts;
+	m.skin_at = skin ? (uint32_t)ps->mesh_skins.size() : PARTICLE_NO_SOURCE;
+	ps->mesh_positions.insert(ps->mesh_positions.end(), positions_xyz, positions_xyz + 3 * (size_t)n_verts);
+	if (skin) ps->mesh_skins.insert(ps->mesh_skins.end(), skin, skin + n_verts);
+	if (out_mesh) *out_mesh = (uint32_t)ps->meshes.size();
+	ps->meshes.push_back(m);
+	ps->meshes_changed = true;
+	return LMX_OK;
+}
+
+int lmx_particles_clear_meshes(LmxParticles* ps) {
+	LMX_CHECK_PARTICLES(ps);
+	ps->meshes.clear();
+	ps->mesh_positions.clear();
+	ps->mesh_skins.clear();
+	for (LmxParticles::System& sy : ps->systems) sy.source.mesh = PARTICLE_NO_SOURCE; // a source that named a mesh has none until it is set again
+	ps->meshes_changed = true;
+	return LMX_OK;
+}
+
+int lmx_particles_set_mesh_source(LmxParticles* ps, uint32_t system, const LmxParticleMeshSource* source) {
+	LMX_CHECK_PARTICLES(ps);
+	if (system >= ps->systems.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "particle system %u: %zu registered", system, ps->systems.size());
+	if (!source) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null mesh source");
+	if (source->flags & ~(uint32_t)LMX_PARTICLE_MESH_HAS_BONES) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "mesh source flags %#x", source->flags);
+	if (source->mesh != PARTICLE_NO_SOURCE) {
+		if (source->mesh >= ps->meshes.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "mesh %u: %zu added", source->mesh, ps->meshes.size());
+		if ((source->flags & LMX_PARTICLE_MESH_HAS_BONES) && ps->meshes[source->mesh].skin_at == PARTICLE_NO_SOURCE)
+			return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "the model has bones and mesh %u carries no skin", source->mesh);
+	}
+	LmxParticles::System& sy = ps->systems[system];
+	sy.source = *source;
+	sy.mesh_declared = true;
+	ps->any_source = true;
+	return LMX_OK;
+}
+
+int lmx_particles_set_spline(LmxParticles* ps, uint32_t system, const float* points_xyz, uint32_t n_points) {
+	LMX_CHECK_PARTICLES(ps);
+	if (system >= ps->systems.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "particle system %u: %zu registered", system, ps->systems.size());
+	if (n_points == 1 || n_points == 2) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "a spline of %u points: the reference reads outside its array", n_points);
+	if (n_points && !points_xyz) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null spline points");
+	if (n_points > (1u << 24)) return fail(ctx, LMX_ERR_CAPACITY, "a spline of more than 2^24 points");
+	LmxParticles::System& sy = ps->systems[system];
+	sy.spline.assign(points_xyz, points_xyz + 3 * (size_t)n_points);
+	sy.spline_declared = true;
+	ps->splines_changed = true;
+	ps->any_source = true;
 	return LMX_OK;
 }
 

@@ -4,9 +4,10 @@
 // The layout is InputMemoryStream::read of the engine (no padding between items): a u8 InstructionType, then per instruction
 // DataStream operands of 8 bytes {u8 type, u8 index, 2 pad, float value}, and for RAND two floats, GRADIENT a u32 count with count keys and
 // count values, EMIT a u32 emitter, CMP a condition and a u16 block size, CMP_ELSE a condition and two u16 block sizes, MESH / SPLINE a
-// trailing u8. The update program starts at byte 0, the emit program at emit_offset, the output program at output_offset.
+// destination, one operand and a trailing u8 (the subindex). The update program starts at byte 0, the emit program at emit_offset, the output program at output_offset.
 #include "lmx_particle_program.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 
@@ -23,6 +24,7 @@ struct Decoder {
 	std::string& error;
 	Section section = SEC_UPDATE;
 	bool in_emit_block = false;
+	bool unsupported = false; // the refusal is of a well-formed MESH / SPLINE the device does not run (PD_UNSUPPORTED)
 	uint32_t group = 0; // whole-chunk conditionals of the update program seen so far
 
 	Decoder(const ParticleProgramDesc& desc, ParticleProgram& o, std::string& e) : d(desc), out(o), error(e) {}
@@ -120,6 +122,40 @@ struct Decoder {
 		return true;
 	}
 
+	// MESH (run :741-774) and SPLINE (run :775-798, processChunk :1189-1219): dst, one operand, a u8 subindex. Without a declared source the
+	// decoding stops here, as it always did, and the caller refuses the program.
+	bool source_op(uint8_t op, uint32_t at, uint32_t& pos, uint32_t limit, bool scalar, ParticleRec& r, uint16_t* wmask) {
+		const bool is_mesh = op == P_MESH;
+		out.has_mesh_or_spline = true;
+		(is_mesh ? out.has_mesh : out.has_spline) = true;
+		if (!(d.sources & (is_mesh ? PARTICLE_SRC_MESH : PARTICLE_SRC_SPLINE))) {
+			out.stopped = true;
+			return true;
+		}
+		if (in_emit_block) return unsupported_form(at, "MESH / SPLINE inside an EMIT block: the reference's early return leaves the outer run in the middle of the block");
+		if (is_mesh && !scalar) return unsupported_form(at, "MESH outside a conditional block or the emit program: the reference asserts");
+		if (!operand(pos, limit, scalar, POS_DST, r.o[0])) return false;
+		if (!operand(pos, limit, scalar, scalar ? POS_SRC : POS_SRC_STREAM, r.o[1])) return false;
+		if (!room(pos, 1, limit)) return bad(pos, "MESH / SPLINE runs past its block");
+		r.b = d.bytes[pos++];
+		if (r.b > 2) return bad(at, "subindex above 2");
+		if (!scalar && r.o[0].type != PS_OUT) return unsupported_form(at, "whole-chunk SPLINE into a channel or a register: the reference asserts an output");
+		if (r.o[0].type == PS_CHANNEL && wmask) *wmask |= (uint16_t)(1u << r.o[0].index);
+		if (is_mesh) {
+			const ParticleOperand& index = r.o[1]; // written when it is negative: it counts as written
+			if (index.type == PS_GLOBAL || index.type == PS_SYSTEM_VALUE) return bad(at, "MESH index is a global or a system value: it cannot take the drawn vertex");
+			if (index.type == PS_LITERAL && index.value < 0.0f) return bad(at, "MESH index is a negative literal: it cannot take the drawn vertex");
+			if (index.type == PS_CHANNEL && wmask) *wmask |= (uint16_t)(1u << index.index);
+			r.a = at; // the byte offset: made an ordinal once every section is decoded
+			++out.mesh_count;
+		}
+		return true;
+	}
+	bool unsupported_form(uint32_t at, const char* what) {
+		unsupported = true;
+		return bad(at, what);
+	}
+
 	// Instructions run per particle by the scalar interpreter (ParticleSystem::run) from `pos` to the END that closes them. With
 	// `exact` the END must be the block's last byte (`limit`). Leaves `pos` behind the END.
 	bool scalar_block(uint32_t& pos, uint32_t limit, bool exact, uint32_t depth, bool skip_pending, uint8_t end_kind, uint32_t* end_rec, uint16_t* wmask, bool* kills) {
@@ -144,8 +180,10 @@ struct Decoder {
 					out.recs.push_back(r);
 					break;
 				case P_MESH: case P_SPLINE:
-					out.has_mesh_or_spline = true;
-					return true;
+					if (!source_op(op, at, pos, limit, true, r, wmask)) return false;
+					if (out.stopped) return true;
+					out.recs.push_back(r);
+					break;
 				case P_RAND:
 					if (!rand_op(pos, limit, true, r, wmask)) return false;
 					out.recs.push_back(r);
@@ -166,7 +204,7 @@ struct Decoder {
 					in_emit_block = true; // (its own run(): a fresh skip stack)
 					const bool ok = scalar_block(pos, limit, false, depth + 1, false, PE_EMIT_END, nullptr, nullptr, nullptr);
 					in_emit_block = false;
-					if (!ok || out.has_mesh_or_spline) return ok;
+					if (!ok || out.stopped) return ok;
 					break;
 				}
 				case P_CMP: case P_CMP_ELSE: {
@@ -182,11 +220,11 @@ struct Decoder {
 					out.recs.push_back(r);
 					uint32_t true_end = 0;
 					if (!scalar_block(pos, pos + ts, true, depth + 1, has_else, has_else ? PE_JUMP : PE_CONTINUE, &true_end, wmask, kills)) return false;
-					if (out.has_mesh_or_spline) return true;
+					if (out.stopped) return true;
 					out.recs[me].a = (uint32_t)out.recs.size();
 					if (has_else) {
 						if (!scalar_block(pos, pos + fs, true, depth + 1, false, PE_CONTINUE, nullptr, wmask, kills)) return false;
-						if (out.has_mesh_or_spline) return true;
+						if (out.stopped) return true;
 						out.recs[true_end].a = (uint32_t)out.recs.size();
 					}
 					break;
@@ -221,8 +259,10 @@ struct Decoder {
 				case P_EMIT: return bad(at, "EMIT outside a conditional block");
 				case P_NOT: return bad(at, "NOT outside a conditional block");
 				case P_MESH: case P_SPLINE:
-					out.has_mesh_or_spline = true;
-					return true;
+					if (!source_op(op, at, pos, limit, false, r, nullptr)) return false;
+					if (out.stopped) return true;
+					out.recs.push_back(r);
+					break;
 				case P_RAND:
 					if (!rand_op(pos, limit, false, r, nullptr)) return false;
 					out.recs.push_back(r);
@@ -260,11 +300,11 @@ struct Decoder {
 					uint16_t wmask = 0;
 					bool kills = false;
 					if (!scalar_block(pos, pos + ts, true, 1, false, PE_RETURN, nullptr, &wmask, &kills)) return false;
-					if (out.has_mesh_or_spline) return true;
+					if (out.stopped) return true;
 					out.recs[me].a = (uint32_t)out.recs.size();
 					if (has_else) {
 						if (!scalar_block(pos, pos + fs, true, 1, false, PE_RETURN, nullptr, &wmask, &kills)) return false;
-						if (out.has_mesh_or_spline) return true;
+						if (out.stopped) return true;
 					}
 					++group;
 					out.recs[me].c = (uint32_t)out.recs.size();
@@ -295,16 +335,25 @@ ParticleDecodeResult particle_program_decode(const ParticleProgramDesc& desc, Pa
 	if (desc.emit_offset >= desc.size || desc.output_offset >= desc.size) return dec.bad(0, "program offset outside the stream"), PD_INVALID;
 	dec.section = SEC_UPDATE;
 	out.update_at = 0;
-	if (!dec.chunk_program(0)) return PD_INVALID;
-	if (out.has_mesh_or_spline) return PD_OK;
+	const auto refused = [&]() { return dec.unsupported ? PD_UNSUPPORTED : PD_INVALID; };
+	if (!dec.chunk_program(0)) return refused();
+	if (out.stopped) return PD_OK;
 	dec.section = SEC_EMIT;
 	out.emit_at = (uint32_t)out.recs.size();
 	uint32_t pos = desc.emit_offset;
-	if (!dec.scalar_block(pos, desc.size, false, 0, false, PE_RETURN, nullptr, nullptr, nullptr)) return PD_INVALID;
-	if (out.has_mesh_or_spline) return PD_OK;
+	if (!dec.scalar_block(pos, desc.size, false, 0, false, PE_RETURN, nullptr, nullptr, nullptr)) return refused();
+	if (out.stopped) return PD_OK;
 	dec.section = SEC_OUTPUT;
 	out.output_at = (uint32_t)out.recs.size();
-	if (!dec.chunk_program(desc.output_offset)) return PD_INVALID;
+	if (!dec.chunk_program(desc.output_offset)) return refused();
+	if (out.stopped) return PD_OK;
+	// MESH ordinals: by byte offset, whatever order the sections lie in (the draw of a MESH does not depend on which one was decoded first)
+	std::vector<uint32_t> at;
+	for (const ParticleRec& r : out.recs)
+		if (r.op == P_MESH) at.push_back(r.a);
+	std::sort(at.begin(), at.end());
+	for (ParticleRec& r : out.recs)
+		if (r.op == P_MESH) r.a = (uint32_t)(std::lower_bound(at.begin(), at.end(), r.a) - at.begin());
 	return PD_OK;
 }
 

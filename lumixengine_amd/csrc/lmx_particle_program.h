@@ -36,10 +36,11 @@ struct ParticleRec {
 	uint8_t op;
 	uint8_t kind;   // END: ParticleEndKind
 	uint16_t wmask; // whole-chunk CMP / CMP_ELSE: the channels its blocks write, when one of them can kill (0 otherwise)
-	uint32_t a;     // CMP / CMP_ELSE: the record behind the true block; END of kind PE_JUMP: the target; GRADIENT: its table; RAND: its ordinal; EMIT: the target emitter
-	uint32_t b;     // whole-chunk CMP / CMP_ELSE: bit 0 = a block holds a KILL; EMIT: its ordinal among the program's EMITs
+	uint32_t a;     // CMP / CMP_ELSE: the record behind the true block; END of kind PE_JUMP: the target; GRADIENT: its table; RAND: its ordinal; EMIT: the target emitter;
+	                // MESH: its ordinal among the program's MESH instructions (the draw's key)
+	uint32_t b;     // whole-chunk CMP / CMP_ELSE: bit 0 = a block holds a KILL; EMIT: its ordinal among the program's EMITs; MESH / SPLINE: subindex (0..2)
 	uint32_t c;     // whole-chunk CMP / CMP_ELSE: the next whole-chunk record
-	ParticleOperand o[4]; // dst, op0, op1, op2 (RAND: o[1].value = from, o[2].value = to; CMP: o[0] = the condition)
+	ParticleOperand o[4]; // dst, op0, op1, op2 (RAND: o[1].value = from, o[2].value = to; CMP: o[0] = the condition; MESH: o[1] = the index, read and written)
 };
 static_assert(sizeof(ParticleRec) == 48, "read by the kernels sixteen bytes at a time");
 
@@ -55,7 +56,11 @@ struct ParticleProgramDesc {
 	uint32_t channels_count, registers_count, outputs_count, emit_inputs_count;
 	uint32_t n_emitters; // of the system: EMIT targets are checked against it
 	uint32_t n_globals;
+	// What the system has declared (lmx_particles_set_mesh_source / lmx_particles_set_spline, a "none" declaration included). Decoding
+	// stops at the first MESH / SPLINE whose source is not declared, with has_mesh_or_spline set: the caller refuses such a program.
+	uint32_t sources;
 };
+constexpr uint32_t PARTICLE_SRC_MESH = 1u, PARTICLE_SRC_SPLINE = 2u;
 
 struct ParticleProgram {
 	std::vector<ParticleRec> recs; // update | emit | output sections back to back
@@ -67,12 +72,15 @@ struct ParticleProgram {
 	uint8_t emit_group[PARTICLE_MAX_EMITS] = {};   // the whole-chunk conditional each sits in, counted from 0: records are drained block by block
 	uint32_t emit_target[PARTICLE_MAX_EMITS] = {}; // ... and the emitter of its system it emits into
 	bool has_emit = false, has_mesh_or_spline = false;
+	bool has_mesh = false, has_spline = false;
+	bool stopped = false;                         // decoding ended at a MESH / SPLINE without a declared source: `recs` is a prefix
+	uint32_t mesh_count = 0;                      // MESH instructions, numbered by byte offset
 	bool has_kill = false;                        // a KILL anywhere in the update program (refused for ribbon emitters)
 };
 
-enum ParticleDecodeResult { PD_OK = 0, PD_INVALID = 1 };
+enum ParticleDecodeResult { PD_OK = 0, PD_INVALID = 1, PD_UNSUPPORTED = 2 /* well formed, but a form of MESH / SPLINE the device does not run */ };
 
-// Decodes and validates. On PD_INVALID `error` says what was wrong; `out` is then unspecified. Never reads outside [bytes, bytes + size).
+// Decodes and validates. On PD_INVALID / PD_UNSUPPORTED `error` says what was wrong; `out` is then unspecified. Never reads outside [bytes, bytes + size).
 ParticleDecodeResult particle_program_decode(const ParticleProgramDesc& desc, ParticleProgram& out, std::string& error);
 
 } // namespace lmx

@@ -62,6 +62,20 @@ struct ParticleSystemDev {
 	uint32_t globals_at, n_globals, pad[2];
 };
 
+// What MESH and SPLINE read for the particles of one system: its entity's mesh 0, pose and spline. Uniform over a block.
+constexpr uint32_t PARTICLE_NO_SOURCE = 0xffffffffu;
+constexpr uint32_t PARTICLE_SOURCE_BONES = 1u; // flags: the model has bones
+struct ParticleSourceDev {
+	uint32_t mesh_at;       // first vertex in mesh_positions (x 3 floats)
+	uint32_t n_verts;       // 0: no model instance, model not ready or no mesh - the run ends at a MESH
+	uint32_t skin_at;       // first LmxSkin in mesh_skins; PARTICLE_NO_SOURCE: the mesh has none
+	uint32_t palette_at;    // first bone of the instance's palette; PARTICLE_NO_SOURCE: no pose
+	uint32_t n_bones;
+	uint32_t flags;
+	uint32_t spline_at;     // first point in spline_points (x 3 floats)
+	uint32_t n_points;      // 0: no spline component; otherwise >= 3
+};
+
 struct ParticleStateDev {   // per emitter
 	uint32_t count, emit_index, overflow, killed;
 };
@@ -100,6 +114,11 @@ struct ParticlesDevice {
 	const ParticleRibbonDev* ribbons;         // the live ribbons of every ribbon emitter, as the host's last call left them
 	const ParticleRibbonCount* ribbon_counts; // per ribbon emitter
 	uint32_t n_ribbon_emitters;
+	const ParticleSourceDev* sources;         // per system
+	const float* mesh_positions;
+	const LmxSkin* mesh_skins;
+	const float4* palette;                    // of the last lmx_skin_run (skin_kernels.hip "Palette layout")
+	const float* spline_points;
 };
 
 size_t particle_chunk_lds_bytes(uint32_t registers, uint32_t shadow_channels);

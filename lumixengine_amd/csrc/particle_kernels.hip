@@ -14,7 +14,9 @@
 // The decoded program (lmx_particle_program.h) is wave-uniform outside conditional blocks: `ip` is a loop counter there and the records
 // come through scalar loads (the program is a kernel argument of its own, const and __restrict__: no store of the kernel can clobber it). The VM's registers are LDS pages of 1024 floats, indexed by lane (chunk-local: DESIGN §4.15 deviation 3).
 // Arithmetic is fp32 under -ffp-contract=off; MULTIPLY_ADD is a multiply and an add, MIX is a + (b - a) * c.
+// MESH and SPLINE read the tables of the lane's system (ParticleSourceDev: its entity's mesh 0, the palette of its pose, its spline).
 #include "lmx_particles.h"
+#include "lmx_skin_eval.h"
 
 namespace lmx {
 
@@ -69,13 +71,24 @@ __device__ __forceinline__ uint32_t p_mix(uint32_t x) {
 	return x;
 }
 // RAND: a counter-based draw keyed by (seed, emitter, step, particle, instruction ordinal) through RandomGenerator::randFloat's formula
-__device__ __forceinline__ float p_rand(uint32_t seed, uint32_t emitter, uint32_t step, uint32_t particle, uint32_t ordinal, float from, float to) {
+__device__ __forceinline__ uint32_t p_draw(uint32_t seed, uint32_t emitter, uint32_t step, uint32_t particle, uint32_t ordinal) {
 	uint32_t r = p_mix(seed ^ 0x9e3779b9u);
 	r = p_mix(r ^ emitter);
 	r = p_mix(r ^ step);
 	r = p_mix(r ^ particle);
-	r = p_mix(r ^ ordinal);
+	return p_mix(r ^ ordinal);
+}
+__device__ __forceinline__ float p_rand(uint32_t seed, uint32_t emitter, uint32_t step, uint32_t particle, uint32_t ordinal, float from, float to) {
+	const uint32_t r = p_draw(seed, emitter, step, particle, ordinal);
 	return from + float((to - from) * (r * 2.328306435996595e-10));
+}
+constexpr uint32_t MESH_DRAW_DOMAIN = 0x80000000u; // MESH ordinals are keyed apart from RAND's: neither numbering moves the other's draws
+
+// u32(x) of a float as x86-64 converts it: through a signed 64-bit conversion, low word kept; NaN and out of range give 0
+__device__ __forceinline__ uint32_t u32_x86(float v) {
+	uint32_t i = 0;
+	if (fabsf(v) < 9223372036854775808.0f) i = (uint32_t)(uint64_t)(int64_t)v;
+	return i;
 }
 
 // What one lane of the VM sees
@@ -94,6 +107,8 @@ struct Lane {
 	uint32_t seed, emitter, step;
 	uint32_t* stage;      // the emitter's staging records (update program with EMIT only)
 	uint32_t n_emit;
+	const ParticlesDevice* dev; // MESH / SPLINE: the source tables, read where such an instruction runs
+	uint32_t system;
 };
 
 __device__ __forceinline__ float lane_read(const Lane& L, const ParticleOperand& o) {
@@ -117,6 +132,45 @@ __device__ __forceinline__ void lane_write(const Lane& L, const ParticleOperand&
 		case PS_OUT: L.outp[o.index] = v; break;
 		default: break;
 	}
+}
+
+// SPLINE (run :785-796, processChunk :1207-1216): the quadratic through the midpoints of segment `u32(t)`, component `sub`. clamp(u32, 0, i32)
+// is the unsigned minimum (core/math.h:520): a negative t of magnitude >= 1 converts to a large u32 and lands in the LAST segment.
+__device__ __forceinline__ float p_spline(const ParticlesDevice& d, const ParticleSourceDev& s, float value, uint32_t sub) {
+	const float t = f_mul(value, float(s.n_points - 2u));
+	const uint32_t last = s.n_points - 3u;
+	uint32_t seg = u32_x86(t);
+	if (!(seg < last)) seg = last;
+	const float rel = f_sub(t, float(seg));
+	const float* q = d.spline_points + 3 * ((size_t)s.spline_at + seg) + sub;
+	const float p1 = q[3];
+	const float p0 = f_mul(f_add(p1, q[0]), 0.5f), p2 = f_mul(f_add(p1, q[6]), 0.5f);
+	const float one_t = f_sub(1.f, rel);
+	const float a = f_add(f_mul(p0, one_t), f_mul(p1, rel)), b = f_add(f_mul(p1, one_t), f_mul(p2, rel)); // lerp of core/math.cpp:190
+	return f_add(f_mul(a, one_t), f_mul(b, rel));
+}
+
+// MESH's value (run :761-771): component `sub` of vertex `idx`, through Model::evalVertexPose where the model has bones. Only row `sub` of the
+// blended matrix is formed, bone by bone in the reference's association ((a0 * w0 + a1 * w1) + a2 * w2) + a3 * w3.
+__device__ __forceinline__ float p_mesh_vertex(const ParticlesDevice& d, const ParticleSourceDev& s, uint32_t idx, uint32_t sub) {
+	const uint32_t vert = 3u * (s.mesh_at + idx); // (32-bit offsets from uniform bases: lmx_particles_add_mesh bounds the tables)
+	if (!(s.flags & PARTICLE_SOURCE_BONES)) return d.mesh_positions[vert + sub];
+	const char* skins = reinterpret_cast<const char*>(d.mesh_skins);
+	const uint32_t skin = (s.skin_at + idx) * (uint32_t)sizeof(LmxSkin);
+	const float4* pal = d.palette + 3 * (size_t)s.palette_at;
+	float m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+	// One bone at a time, not unrolled: with the four bones' sixteen elements in flight at once the chunk kernels leave their 64 VGPRs
+#pragma unroll 1
+	for (uint32_t k = 0; k < 4; ++k) {
+		uint32_t bone = *reinterpret_cast<const uint16_t*>(skins + (skin + (uint32_t)offsetof(LmxSkin, indices) + 2u * k));
+		if (bone >= s.n_bones) bone = 0;
+		const SkinRow e = skin_row(pal, bone, sub);
+		const float w = *reinterpret_cast<const float*>(skins + (skin + 4u * k));
+#pragma unroll
+		for (int j = 0; j < 4; ++j) m[j] = k == 0 ? f_mul(e.e[j], w) : f_add(m[j], f_mul(e.e[j], w));
+	}
+	const float* p = d.mesh_positions;
+	return f_add(f_add(f_add(f_mul(m[0], p[vert]), f_mul(m[1], p[vert + 1u])), f_mul(m[2], p[vert + 2u])), m[3]); // transformPoint, math.cpp:1231-1235
 }
 
 // ParticleSystem::run from record `ip` to the END that returns. True: the particle was killed.
@@ -145,6 +199,26 @@ __device__ __forceinline__ bool run_scalar(Lane L, const ParticleRec* prog, uint
 				if (!(lane_read(L, r.o[0]) != 0.0f)) next = r.a;
 				break;
 			case P_RAND: lane_write(L, r.o[0], p_rand(L.seed, L.emitter, L.step, L.rslot, r.a, r.o[1].value, r.o[2].value)); break;
+			case P_MESH: { // :741-774. Every `return` is the reference's: the run ends with its verdict so far
+				const ParticleSourceDev s = L.dev->sources[L.system];
+				if (!s.n_verts) return killed;
+				float index = lane_read(L, r.o[1]);
+				if (index < 0.0f) {
+					index = float(p_draw(L.seed, L.emitter, L.step, L.rslot, MESH_DRAW_DOMAIN + r.a) % s.n_verts);
+					lane_write(L, r.o[1], index);
+				}
+				if ((s.flags & PARTICLE_SOURCE_BONES) && s.palette_at == PARTICLE_NO_SOURCE) return killed;
+				uint32_t idx = u32_x86(index + 0.5f);
+				if (idx >= s.n_verts) idx = 0; // (the reference reads past the array)
+				lane_write(L, r.o[0], p_mesh_vertex(*L.dev, s, idx, r.b));
+				break;
+			}
+			case P_SPLINE: { // :775-798
+				const ParticleSourceDev s = L.dev->sources[L.system];
+				if (!s.n_points) return killed;
+				lane_write(L, r.o[0], p_spline(*L.dev, s, lane_read(L, r.o[1]), r.b));
+				break;
+			}
 			case P_MULTIPLY_ADD: lane_write(L, r.o[0], f_add(f_mul(lane_read(L, r.o[1]), lane_read(L, r.o[2])), lane_read(L, r.o[3]))); break;
 			case P_MIX: { // lerp of core/math.cpp:190
 				const float a = lane_read(L, r.o[1]), b = lane_read(L, r.o[2]), t = lane_read(L, r.o[3]);
@@ -192,6 +266,7 @@ __device__ __forceinline__ void run_whole(const Lane& L, const ParticleRec& r, c
 		case P_SQRT: v = f_sqrt(lane_read(L, r.o[1])); break;
 		case P_NOISE: v = p_gnoise(lane_read(L, r.o[1])); break;
 		case P_RAND: v = p_rand(L.seed, L.emitter, L.step, L.rslot, r.a, r.o[1].value, r.o[2].value); break;
+		case P_SPLINE: v = p_spline(*L.dev, L.dev->sources[L.system], lane_read(L, r.o[1]), r.b); break; // (a system without a spline never gets here: the caller stops the program)
 		case P_GRADIENT: {
 			const ParticleGradient& g = gradients[r.a];
 			const float arg = lane_read(L, r.o[1]);
@@ -266,6 +341,7 @@ __global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_emit(Particle
 	L.emitting = true;
 	L.seed = d.seed; L.emitter = job.emitter; L.step = d.step;
 	L.stage = nullptr; L.n_emit = 0;
+	L.dev = &d; L.system = em.system;
 	(void)run_scalar(L, prog, em.prog_emit);
 }
 
@@ -286,7 +362,7 @@ __global__ void k_particles_commit(ParticlesDevice d, const ParticleEmitJob* __r
 	d.state[job.emitter] = st;
 }
 
-template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particles_chunk(ParticlesDevice d, const ParticleRec* __restrict__ prog, const ParticleGradient* __restrict__ gradients) {
+template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK, 8) k_particles_chunk(ParticlesDevice d, const ParticleRec* __restrict__ prog, const ParticleGradient* __restrict__ gradients) {
 	LMX_DYNAMIC_LDS(float, s_lds); // [registers][1024] register pages | [shadow channels][1024] | map[1024] | ballots[16 x 2] | kill count
 	const uint32_t e = blockIdx.y;
 	const ParticleStateDev st = d.state[e];
@@ -323,6 +399,7 @@ template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particl
 	L.seed = d.seed; L.emitter = e; L.step = d.step;
 	L.stage = d.stage + em.stage_base;
 	L.n_emit = FILL ? 0u : em.n_emit;
+	L.dev = &d; L.system = em.system;
 	if (active)
 		for (uint32_t j = 0; j < L.n_emit; ++j) L.stage[((size_t)L.slot * L.n_emit + j) * PARTICLE_STAGE_WORDS] = 0u;
 
@@ -331,6 +408,7 @@ template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particl
 		const ParticleRec& r = prog[ip];
 		const uint32_t op = r.op;
 		if (op == P_END) break;
+		if (FILL && op == P_SPLINE && !d.sources[em.system].n_points) break; // processChunk :1196-1198 returns: uniform over the block, nothing behind it runs
 		if (op != P_CMP && op != P_CMP_ELSE) {
 			if (active) run_whole(L, r, gradients);
 			++ip;
@@ -504,6 +582,7 @@ __global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_subemit(Parti
 			L.emitting = true;
 			L.seed = d.seed; L.emitter = job.target; L.step = d.step;
 			L.stage = nullptr; L.n_emit = 0;
+			L.dev = &d; L.system = em.system;
 			(void)run_scalar(L, prog, em.prog_emit);
 		}
 	}
@@ -555,7 +634,7 @@ __global__ void __launch_bounds__(PARTICLE_SCAN_BLOCK) k_particles_slices(Partic
 // ParticleSystem::emitRibbonPoints (:358-409) of every job of a pass. Point i of a call lands in ring slot (offset0 + length0 + i) % ribbon_len,
 // so lane j of a job owns the slot of points j, j + ribbon_len, ... and runs them in order: no two lanes write one slot. (The reference
 // takes the modulus of a u32 sum; the two agree until offset + length passes 2^32, which is where the slots are computed as it does.)
-__global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_ribbon_emit(ParticlesDevice d, const ParticleRibbonJob* __restrict__ jobs, uint32_t n_jobs, uint32_t total_lanes, const ParticleRec* __restrict__ prog) {
+__global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK, 6) k_particles_ribbon_emit(ParticlesDevice d, const ParticleRibbonJob* __restrict__ jobs, uint32_t n_jobs, uint32_t total_lanes, const ParticleRec* __restrict__ prog) {
 	__shared__ float s_regs[PARTICLE_MAX_REGISTERS * PARTICLE_EMIT_BLOCK];
 	const uint32_t g = blockIdx.x * PARTICLE_EMIT_BLOCK + threadIdx.x;
 	if (g >= total_lanes) return;
@@ -583,6 +662,7 @@ __global__ void __launch_bounds__(PARTICLE_EMIT_BLOCK) k_particles_ribbon_emit(P
 	L.emitting = true;
 	L.seed = d.seed; L.emitter = job.emitter; L.step = d.step;
 	L.stage = nullptr; L.n_emit = 0;
+	L.dev = &d; L.system = em.system;
 	float t = job.total_time; // the repeated sum c1 + d + d + ..., restarted for every ribbon
 	uint64_t summed = 0;
 	for (uint64_t i = g - job.first_lane; i < job.count; i += len) {
@@ -644,6 +724,7 @@ template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particl
 	L.emit_index = L.sysv[PSV_EMIT_INDEX];
 	L.emitting = false;
 	L.seed = d.seed; L.emitter = rc.emitter; L.step = d.step;
+	L.dev = &d; L.system = em.system;
 	L.stage = d.stage; L.n_emit = 0; // never used: no program of a ribbon emitter holds an EMIT (a null pointer here crashes ROCm 7.2's clang in SimplifyCFG)
 
 	uint32_t ip = FILL ? em.prog_output : em.prog_update;
@@ -651,6 +732,7 @@ template <bool FILL> __global__ void __launch_bounds__(PARTICLE_BLOCK) k_particl
 		const ParticleRec& r = prog[ip];
 		const uint32_t op = r.op;
 		if (op == P_END) break;
+		if (FILL && op == P_SPLINE && !d.sources[em.system].n_points) break; // processChunk :1196-1198 returns: uniform over the block, nothing behind it runs
 		if (op != P_CMP && op != P_CMP_ELSE) {
 			if (active) run_whole(L, r, gradients);
 			++ip;

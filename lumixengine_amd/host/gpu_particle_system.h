@@ -9,9 +9,11 @@
 // with their options; emitRibbons, killRibbon and applyTransforms forward ParticleSystem's calls of those names, and mirrorRibbons copies
 // the ribbon records (host state of the library: no wait) into Emitter::ribbons and particles_count, so that the ribbon loops of
 // Pipeline's createCommands (pipeline.cpp:2865, :2919) draw from the device slice unchanged - the slice is packed per ribbon, which is
-// the layout those loops assume. Autodestroy, MESH / SPLINE programs and the sort-key pairs stay with the engine: add() returns false for
-// a system it cannot take and the engine keeps updating that one itself (a system refused at its programs keeps its index, with empty
-// programs).
+// the layout those loops assume. MESH / SPLINE programs are taken when add() is given what they read of the system's entity - its Model
+// (mesh 0 and its skin, uploaded once per model), the skin instance the pose bridge gave the entity and its Spline; updateSources()
+// re-declares them for an entity whose pose instance or spline changed. Autodestroy and the sort-key pairs stay with the engine: add()
+// returns false for a system it cannot take and the engine keeps updating that one itself (a system refused at its programs keeps its
+// index, with empty programs).
 //
 // `System` is ParticleSystem inside the engine (-DLMX_WITH_LUMIX_HEADERS); a standalone build passes any type with getResource(),
 // m_globals, m_world and m_entity (tests/cpp/lumix_compat_particles.h).
@@ -47,6 +49,50 @@ struct GpuParticleSystems {
 
 	// Registers `system` (its resource must be ready) with `capacity` particles per emitter. False: the system stays with the engine.
 	template <typename System> bool add(System& system, u32 capacity, u32* out_index = nullptr) {
+		return addDeclared(system, capacity, out_index, [](u32) { return true; });
+	}
+
+	// ... with what MESH and SPLINE read of the system's entity, from the engine's objects: `model` = RenderModule::getModelInstanceModel(entity)
+	// (null: no model instance), `skin_instance` = the instance of lmx_skin_set_instances the pose bridge gave the entity (0xffffffff: no
+	// pose), `spline` = &CoreModule::getSpline(entity) where the entity has the component (null: none). A system whose programs hold MESH or
+	// SPLINE is taken only through this overload. False also for a spline of one or two points (the reference reads outside its array).
+	template <typename System, typename Model, typename Spline> bool add(System& system, u32 capacity, u32* out_index, const Model* model, u32 skin_instance, const Spline* spline) {
+		return addDeclared(system, capacity, out_index, [&](u32 index) { return updateSources(index, model, skin_instance, spline); });
+	}
+
+	// Per frame, for a system whose entity got another pose instance, model or spline: the tables follow in stream order, no new layout and
+	// no reset (a new POSE of the same instance needs no call: the palette is read where lmx_skin_run leaves it).
+	template <typename Model, typename Spline> bool updateSources(u32 index, const Model* model, u32 skin_instance, const Spline* spline) {
+		LmxParticleMeshSource src = {0xffffffffu, skin_instance, 0};
+		if (model && model->isReady() && model->getMeshCount() > 0) {
+			const auto& mesh = model->getMesh(0);
+			const bool bones = model->getBones().size() > 0;
+			static_assert(sizeof(mesh.vertices[0]) == 3 * sizeof(float) && sizeof(mesh.skin[0]) == sizeof(LmxSkin), "Mesh::vertices / Mesh::skin are read as they lie");
+			if (bones && mesh.skin.size() != mesh.vertices.size()) return false;
+			u32 id = 0xffffffffu;
+			for (const ModelMesh& m : m_meshes)
+				if (m.model == (const void*)model) id = m.mesh;
+			if (id == 0xffffffffu) { // once per model, whatever number of systems sit on it
+				if (mesh.vertices.size() == 0) return false;
+				const LmxSkin* skin = mesh.skin.size() == mesh.vertices.size() ? (const LmxSkin*)&mesh.skin[0] : nullptr;
+				if (lmx_particles_add_mesh(m_ps, (u32)mesh.vertices.size(), (const float*)&mesh.vertices[0], skin, &id) != LMX_OK) return false;
+				m_meshes.push_back(ModelMesh{(const void*)model, id});
+			}
+			src.mesh = id;
+			src.flags = bones ? (u32)LMX_PARTICLE_MESH_HAS_BONES : 0u;
+		}
+		if (lmx_particles_set_mesh_source(m_ps, index, &src) != LMX_OK) return false;
+		const u32 n_points = spline ? (u32)spline->points.size() : 0u;
+		if (n_points == 1 || n_points == 2) return false;
+		return lmx_particles_set_spline(m_ps, index, n_points ? (const float*)&spline->points[0] : nullptr, n_points) == LMX_OK;
+	}
+
+private:
+	struct ModelMesh { const void* model; u32 mesh; };
+	std::vector<ModelMesh> m_meshes;
+
+	// `declare(index)` runs behind lmx_particles_add_system and before the programs are set: a declaration is what lets a program hold MESH / SPLINE
+	template <typename System, typename Declare> bool addDeclared(System& system, u32 capacity, u32* out_index, Declare declare) {
 		auto* res = system.getResource();
 		if (!res || !res->isReady()) return false;
 		auto& emitters = res->getEmitters();
@@ -55,7 +101,7 @@ struct GpuParticleSystems {
 		u32 index = 0;
 		if (lmx_particles_add_system(m_ps, (u32)emitters.size(), (u32)system.m_globals.size(), &index) != LMX_OK) return false;
 		m_first.push_back((u32)m_emitters.size());
-		bool ok = true;
+		bool ok = declare(index);
 		u32 k = 0;
 		for (const auto& e : emitters) {
 			LmxParticleProgram p;
@@ -93,6 +139,7 @@ struct GpuParticleSystems {
 		return ok;
 	}
 
+public:
 	// ParticleSystem::m_globals and World::getPosition(entity) of a registered system, before update()
 	template <typename System> bool sync(u32 index, System& system) {
 		const DVec3 pos = system.m_world.getPosition(EntityRef{system.m_entity.index});
