@@ -302,6 +302,41 @@ typedef struct LmxBlendInstr {
 #define LMX_TIME_ONE_SECOND (1u << 15)       /* Time::ONE_SECOND, animation/animation.h:41 */
 #define LMX_ANIM_NONE 0xffffffffu
 
+/* Animator controllers (anim::Controller). A controller's node tree may nest pose nodes LMX_CONTROLLER_MAX_POSE_DEPTH deep (a root
+ * alone has depth 1) and a value tree may need LMX_CONTROLLER_MAX_VALUE_DEPTH operands at once (a chain of math nodes that deep). */
+#define LMX_CONTROLLER_NONE 0xffffffffu
+#define LMX_CONTROLLER_MAX_POSE_DEPTH 8
+#define LMX_CONTROLLER_MAX_VALUE_DEPTH 8
+#define LMX_ANIMATOR_USE_ROOT_MOTION 1u      /* Animator::USE_ROOT_MOTION, animation_module.cpp:46 */
+#define LMX_VALUE_NUMBER 0u                  /* anim::Value::Type, controller.h:17-21 */
+#define LMX_VALUE_BOOL 1u
+#define LMX_VALUE_VEC3 2u
+
+/* anim::Value (controller.h:16-37): an input of an Animator. A BOOL is its first byte, zero or not. sizeof == 16. */
+typedef struct LmxAnimatorValue {
+	uint32_t type;                           /* LMX_VALUE_* */
+	union {
+		float f;
+		uint8_t b;
+		float v3[3];
+	};
+} LmxAnimatorValue;
+
+/* What lmx_anim_controller_check reports of a compiled controller resource. */
+typedef struct LmxControllerInfo {
+	uint32_t version;                        /* ControllerVersion of the header */
+	uint32_t n_inputs;                       /* m_inputs */
+	uint32_t n_slots;                        /* m_animation_slots_count */
+	uint32_t n_entries;                      /* m_animation_entries */
+	uint32_t n_nodes;                        /* pose nodes */
+	uint32_t n_ik;                           /* IK nodes */
+	uint32_t state_bytes;                    /* upper bound of RuntimeContext::data after any update */
+	uint32_t max_instrs;                     /* upper bound of the blend instructions one update emits */
+	uint32_t enter_bytes;                    /* RuntimeContext::data as Controller::createRuntime leaves it */
+	uint32_t pose_depth, value_depth;        /* the nesting the tree uses of the two caps */
+	uint32_t _pad;
+} LmxControllerInfo;
+
 /* One ray of lmx_rays_cast: Ray {origin, dir} (core/geometry.h) with what castRay(ray, ignored) carries besides. sizeof == 48. */
 typedef struct LmxRay {
 	double origin[3];

@@ -81,7 +81,9 @@ enum {
 	LMX_K_ANIM_UPDATE = 8,
 	LMX_K_CULL_PATCH = 9, /* the copy + k_apply_patches launch that ships queued add / remove / set records */
 	LMX_K_POSE_SLICES = 10, /* lmx_poses_run: slice offsets + the listed instances' dual quaternions */
-	LMX_K_COUNT = 11
+	LMX_K_ANIMATORS_UPDATE = 11, /* lmx_animators_update: Controller::update of every Animator (k_animators_update) */
+	LMX_K_ANIMATORS_PACK = 12,   /* ... its instruction counts scanned and the records packed; the blend kernel behind them is LMX_K_ANIM_UPDATE */
+	LMX_K_COUNT = 13
 };
 LMX_API int lmx_profile_enable(LmxContext* ctx, int enable);
 LMX_API int lmx_profile_reset(LmxContext* ctx);
@@ -479,6 +481,56 @@ LMX_API int lmx_anim_decode_blend_stack(const uint8_t* bytes, uint64_t n_bytes, 
 LMX_API int lmx_anim_read_times(LmxContext* ctx, uint32_t* time, uint32_t n_instances);
 /* The relative pose of an instance after lmx_anim_update (before lmx_skin_run turns it into the absolute one). */
 LMX_API int lmx_anim_read_pose(LmxContext* ctx, uint32_t instance, float* out_pos, float* out_rot, uint32_t cap_bones);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Animator controllers: the first half of AnimationModuleImpl::updateAnimator (animation_module.cpp:602-636) - Controller::update, the
+ * walk over the controller's node tree (animation/nodes.cpp) that advances an Animator's runtime data, leaves the frame's blend stack
+ * and computes root_motion - for every Animator at once, on the device. The blend stack never leaves device memory: the same call runs
+ * evalBlendStack (the kernel of lmx_anim_eval_blend_instrs) on it, so its output is the relative pose lmx_skin_run consumes.
+ *
+ * Deviations, all where the reference is undefined: a float or double converted to u32 goes through a 64-bit integer and keeps the low
+ * 32 bits (0 for NaN and beyond +-2^63), a float to i32 outside its range or NaN gives INT32_MIN (child 0 after SELECT's clamp) - what the
+ * reference's x86-64 build does; AND / OR operands must be BOOL; a BOOL is its first byte, zero or not; a zero blend length is accepted
+ * and yields the reference's NaN root motion (0 / 0) with weight 0.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* Parses and validates a compiled controller resource (the bytes Controller::load receives) without a context or a device: what
+ * lmx_anim_controller_add would accept. `out_info`, `out_enter_image` (RuntimeContext::data as Controller::createRuntime leaves it,
+ * capacity_bytes of room) and `out_error` (a message for LMX_ERR_INVALID) may be null. No read outside [bytes, bytes + n_bytes). */
+LMX_API int lmx_anim_controller_check(const void* bytes, uint64_t n_bytes, LmxControllerInfo* out_info, void* out_enter_image, uint32_t capacity_bytes, char* out_error,
+	uint32_t error_capacity);
+/* Flattens a compiled controller into a device-resident program. LMX_ERR_INVALID: truncated, unknown or editor-only node type, a value
+ * tree whose static types break a toFloat / toI32 / toBool / toVec3 assert, an INPUT, slot or triangle index out of range, a SELECT or
+ * BLEND without children, IK bones_count outside [1, LMX_IK_MAX_BONES], nesting beyond LMX_CONTROLLER_MAX_*_DEPTH. */
+LMX_API int lmx_anim_controller_add(LmxContext* ctx, const void* bytes, uint64_t n_bytes, uint32_t* out_controller);
+/* Controller::m_inputs[i].type (LMX_VALUE_*) of a controller: what Controller::createRuntime gives RuntimeContext::inputs before any setInput. */
+LMX_API int lmx_anim_controller_input_types(LmxContext* ctx, uint32_t controller, uint32_t* out_types, uint32_t capacity, uint32_t* out_count);
+/* RuntimeContext::animations of one animation set: lmx_anim_add ids or LMX_ANIM_NONE, n_slots == m_animation_slots_count. A slot that an
+ * ANIMATION or BLEND1D node names cannot be empty (the reference dereferences null there); BLEND2D takes its early return. */
+LMX_API int lmx_anim_controller_set_slots(LmxContext* ctx, uint32_t controller, uint32_t set, const uint32_t* slot_animation, uint32_t n_slots);
+/* Animation::RootMotion::translations (x3) / rotations (x4), frame_count + 1 entries each; null = the reference's empty array. */
+LMX_API int lmx_anim_set_root_motion(LmxContext* ctx, uint32_t animation, const float* translations, const float* rotations);
+/* One Animator per skin instance (LMX_CONTROLLER_NONE: none, the instance keeps its model's relative pose). flags: LMX_ANIMATOR_*;
+ * entity: the world entity USE_ROOT_MOTION moves; bone_hashes: the bone name hashes of every instance's model, instances back to back like the pose
+ * arrays (null with n_bone_hashes 0: no IK leaf is found; instances of one model carry the same hashes, the first one's are read). Resolves every IK leaf per (controller, model) and applies the chain rules of
+ * lmx_anim_eval_blend_instrs; every Animator starts from its controller's enter image with zero inputs and identity root motion. */
+LMX_API int lmx_animators_set(LmxContext* ctx, uint32_t n_instances, const uint32_t* controller, const uint32_t* set, const uint32_t* flags, const int32_t* entity,
+	const uint64_t* bone_hashes, uint32_t n_bone_hashes);
+/* RuntimeContext::inputs of Animators [first_animator, first_animator + n): their controllers' inputs back to back. A type that differs
+ * from the controller's is refused; the _device variant reads device memory on the stream and keeps the controller's types. */
+LMX_API int lmx_animators_set_inputs(LmxContext* ctx, uint32_t first_animator, uint32_t n, const LmxAnimatorValue* values);
+LMX_API int lmx_animators_set_inputs_device(LmxContext* ctx, uint32_t first_animator, uint32_t n, const void* d_values);
+/* Controller::update + evalBlendStack for every Animator. time_delta: finite, >= 0 (Time::fromSeconds asserts), below 2^32 ticks. */
+LMX_API int lmx_animators_update(LmxContext* ctx, float time_delta);
+/* RuntimeContext::root_motion of every Animator after the last update (28 bytes each), and the device pointers to it, to first_instr
+ * (n + 1 words) and to the LmxBlendInstr records of the last update; valid until the next lmx_animators_set / blend-stack call. */
+LMX_API int lmx_animators_read_root_motion(LmxContext* ctx, LmxLocalRigidTransform* out, uint32_t n_animators);
+LMX_API int lmx_animators_device_outputs(LmxContext* ctx, void** d_root_motion, void** d_first_instr, void** d_instrs);
+/* animation_module.cpp:630-635 for the Animators with USE_ROOT_MOTION: tr.pos += tr.rot.rotate(rm.pos), tr.rot = rm.rot * tr.rot on the
+ * entity's world transform, staged as World::setTransform; lmx_world_propagate then carries subtrees, spheres and moved marks. */
+LMX_API int lmx_animators_apply_root_motion(LmxContext* ctx);
+/* Read-outs: an Animator's runtime-data bytes (SwitchNode's two padding bytes read as zero), and first_instr / the records of the last update. */
+LMX_API int lmx_animators_read_state(LmxContext* ctx, uint32_t animator, void* out, uint32_t capacity_bytes, uint32_t* out_bytes);
+LMX_API int lmx_animators_read_instrs(LmxContext* ctx, uint32_t* out_first_instr, uint32_t n_animators, LmxBlendInstr* out_instrs, uint32_t capacity, uint32_t* out_count);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Sort keys: PipelineImpl::createSortKeys (renderer/pipeline.cpp:3789-3968), the consumer of the visible list (SURVEY.md

@@ -30,7 +30,7 @@ SKIN_OPT_INSTANCES_PER_BLOCK = 0
 SKIN_INSTANCES_PER_BLOCK_DEFAULT = 2  # what a fresh context uses (lmx_context.h: SkinState::multi)
 (K_CULL_CLASSIFY, K_CULL_SPHERES, K_XFORM_LEVEL, K_SPHERE_REFRESH, K_POSE_PALETTE, K_SKIN_VERTICES, K_CULL_DYNAMIC) = range(7)
 KERNEL_NAMES = ["cull_classify", "cull_spheres", "xform_level", "sphere_refresh", "pose_palette", "skin_vertices", "cull_dynamic", "sort_keys", "anim_update", "cull_patch",
-                "pose_slices"]
+                "pose_slices", "animators_update", "animators_pack"]
 K_CULL_PATCH = 9
 K_POSE_SLICES = 10
 
@@ -51,6 +51,12 @@ BLEND_INSTR = np.dtype([("op", "<u4"), ("animation", "<u4"), ("weight", "<f4"), 
 BLEND_SAMPLE_OP, BLEND_IK_OP, BONE_NONE, IK_MAX_BONES, ANIM_NONE = 1, 2, 0xFFFFFFFF, 32, 0xFFFFFFFF  # LMX_BLEND_*, LMX_BONE_NONE, LMX_IK_MAX_BONES, LMX_ANIM_NONE
 ANIM_ROTATION_TRACK = np.dtype([("min", "<f4", 3), ("to_range", "<f4", 3), ("offset_bits", "<u2"), ("bone_index", "<u2"), ("bitsizes", "u1", 3), ("skipped_channel", "u1")],
                                align=True)
+ANIMATOR_VALUE = np.dtype([("type", "<u4"), ("v", "<u4", 3)])  # LmxAnimatorValue: the union as three words (a NUMBER's bits, a BOOL's byte, a VEC3)
+CONTROLLER_INFO = np.dtype([(k, "<u4") for k in ("version", "n_inputs", "n_slots", "n_entries", "n_nodes", "n_ik", "state_bytes", "max_instrs", "enter_bytes",
+                                                    "pose_depth", "value_depth", "_pad")])
+CONTROLLER_NONE = 0xFFFFFFFF
+ANIMATOR_USE_ROOT_MOTION = 1
+VALUE_NUMBER, VALUE_BOOL, VALUE_VEC3 = 0, 1, 2
 
 
 class LmxAnimation(C.Structure):
@@ -264,6 +270,20 @@ SYMBOLS = {
     "lmx_anim_decode_blend_stack": (_ci, [_vp, C.c_uint64, _vp, _u32, _vp, _u32, C.c_float, _vp, _u32, _vp]),
     "lmx_anim_read_times": (_ci, [_vp, _vp, _u32]),
     "lmx_anim_read_pose": (_ci, [_vp, _u32, _vp, _vp, _u32]),
+    "lmx_anim_controller_check": (_ci, [_vp, C.c_uint64, _vp, _vp, _u32, _vp, _u32]),
+    "lmx_anim_controller_add": (_ci, [_vp, _vp, C.c_uint64, C.POINTER(_u32)]),
+    "lmx_anim_controller_input_types": (_ci, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_anim_controller_set_slots": (_ci, [_vp, _u32, _u32, _vp, _u32]),
+    "lmx_anim_set_root_motion": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_animators_set": (_ci, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32]),
+    "lmx_animators_set_inputs": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_animators_set_inputs_device": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_animators_update": (_ci, [_vp, _f32]),
+    "lmx_animators_read_root_motion": (_ci, [_vp, _vp, _u32]),
+    "lmx_animators_device_outputs": (_ci, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "lmx_animators_apply_root_motion": (_ci, [_vp]),
+    "lmx_animators_read_state": (_ci, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "lmx_animators_read_instrs": (_ci, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "lmx_keys_set_models": (_ci, [_vp, _vp, _u32, _vp, _u32]),
     "lmx_keys_set_instances": (_ci, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "lmx_keys_set_decals": (_ci, [_vp, _u32, _vp, _vp, _vp, _vp]),
@@ -1581,6 +1601,100 @@ class RayCaster:
 
 
 SKIN_FUSED, SKIN_EXACT, SKIN_DQS = 0, 1, 2
+
+
+class Animators:
+    """Animator controllers on the device (lmx_anim_controller_* / lmx_animators_*): one Animator per instance of `skinning`."""
+
+    def __init__(self, skinning):
+        self.ctx, self.lib, self.sk = skinning.ctx, skinning.lib, skinning
+        self.n = 0
+
+    @staticmethod
+    def checkController(raw: bytes):
+        """lmx_anim_controller_check (host only): (info record, enter image bytes). Raises LumixError(LMX_ERR_INVALID) with the parser's message."""
+        lib = load_library()
+        buf = np.frombuffer(bytes(raw), np.uint8)
+        info = np.zeros(1, CONTROLLER_INFO)
+        err = C.create_string_buffer(256)
+        rc = lib.lmx_anim_controller_check(_ptr(buf) if len(buf) else None, len(buf), _ptr(info), None, 0, err, 256)
+        if rc != 0:
+            raise LumixError(rc, err.value.decode())
+        image = np.zeros(max(int(info["enter_bytes"][0]), 1), np.uint8)
+        rc = lib.lmx_anim_controller_check(_ptr(buf), len(buf), None, _ptr(image), len(image), err, 256)
+        if rc != 0:
+            raise LumixError(rc, err.value.decode())
+        return info[0], image[: int(info["enter_bytes"][0])].tobytes()
+
+    def addController(self, raw: bytes) -> int:
+        buf = np.frombuffer(bytes(raw), np.uint8)
+        out = _u32()
+        self.ctx.check(self.lib.lmx_anim_controller_add(self.ctx.h, _ptr(buf) if len(buf) else None, len(buf), C.byref(out)))
+        return int(out.value)
+
+    def inputTypes(self, controller: int) -> np.ndarray:
+        n = _u32()
+        self.ctx.check(self.lib.lmx_anim_controller_input_types(self.ctx.h, controller, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint32)
+        self.ctx.check(self.lib.lmx_anim_controller_input_types(self.ctx.h, controller, _ptr(out), len(out), C.byref(n)))
+        return out[: n.value]
+
+    def setSlots(self, controller: int, anim_set: int, slot_animation):
+        a = np.ascontiguousarray(slot_animation, np.uint32)
+        self.ctx.check(self.lib.lmx_anim_controller_set_slots(self.ctx.h, controller, anim_set, _ptr(a) if len(a) else None, len(a)))
+
+    def setRootMotion(self, animation: int, translations=None, rotations=None):
+        t = None if translations is None else np.ascontiguousarray(translations, np.float32)
+        r = None if rotations is None else np.ascontiguousarray(rotations, np.float32)
+        self.ctx.check(self.lib.lmx_anim_set_root_motion(self.ctx.h, animation, _ptr(t), _ptr(r)))
+
+    def setAnimators(self, controller, anim_set, flags, entity, bone_hashes=None):
+        c = np.ascontiguousarray(controller, np.uint32)
+        s = np.ascontiguousarray(anim_set, np.uint32)
+        f = np.ascontiguousarray(flags, np.uint32)
+        e = np.ascontiguousarray(entity, np.int32)
+        h = None if bone_hashes is None else np.ascontiguousarray(bone_hashes, np.uint64)
+        self.ctx.check(self.lib.lmx_animators_set(self.ctx.h, len(c), _ptr(c), _ptr(s), _ptr(f), _ptr(e), _ptr(h), 0 if h is None else len(h)))
+        self.n = len(c)
+
+    def setInputs(self, first: int, n: int, values):
+        v = np.ascontiguousarray(values, ANIMATOR_VALUE)
+        self.ctx.check(self.lib.lmx_animators_set_inputs(self.ctx.h, first, n, _ptr(v) if len(v) else None))
+
+    def setInputsDevice(self, first: int, n: int, device_ptr: int):
+        self.ctx.check(self.lib.lmx_animators_set_inputs_device(self.ctx.h, first, n, C.c_void_p(device_ptr)))
+
+    def update(self, time_delta: float):
+        self.ctx.check(self.lib.lmx_animators_update(self.ctx.h, float(time_delta)))
+
+    def readRootMotion(self) -> np.ndarray:
+        out = np.zeros(max(self.n, 1), LOCAL_RIGID)
+        self.ctx.check(self.lib.lmx_animators_read_root_motion(self.ctx.h, _ptr(out), self.n))
+        return out[: self.n]
+
+    def deviceOutputs(self):
+        a, b, c = _vp(), _vp(), _vp()
+        self.ctx.check(self.lib.lmx_animators_device_outputs(self.ctx.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def applyRootMotion(self):
+        self.ctx.check(self.lib.lmx_animators_apply_root_motion(self.ctx.h))
+
+    def readState(self, animator: int) -> bytes:
+        n = _u32()
+        self.ctx.check(self.lib.lmx_animators_read_state(self.ctx.h, animator, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 4), np.uint8)
+        self.ctx.check(self.lib.lmx_animators_read_state(self.ctx.h, animator, _ptr(out), len(out), C.byref(n)))
+        return out[: n.value].tobytes()
+
+    def readInstrs(self):
+        """(first_instr, BLEND_INSTR records) of the last update"""
+        first = np.zeros(self.n + 1, np.uint32)
+        n = _u32()
+        self.ctx.check(self.lib.lmx_animators_read_instrs(self.ctx.h, _ptr(first), self.n, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), BLEND_INSTR)
+        self.ctx.check(self.lib.lmx_animators_read_instrs(self.ctx.h, _ptr(first), self.n, _ptr(out), len(out), C.byref(n)))
+        return first, out[: n.value]
 
 
 class Skinning:

@@ -7,7 +7,7 @@
 
 using namespace lmx;
 
-namespace {
+namespace lmx {
 
 int anim_upload_tables(LmxContext* ctx) {
 	AnimState& an = ctx->anim;
@@ -29,7 +29,7 @@ int anim_upload_tables(LmxContext* ctx) {
 	return LMX_OK;
 }
 
-} // namespace
+} // namespace lmx
 
 extern "C" {
 

@@ -599,6 +599,41 @@ struct AnimState {
 	std::vector<LmxBlendSample> samples_scratch; // a call without IK runs k_anim_blend_stack on its SAMPLE fields
 };
 
+// animator controllers (lmx_capi_animators.hip): controller programs, their slot tables, one Animator per skin instance
+struct ControllerHost {
+	ControllerProgram prog;
+	std::unordered_map<uint32_t, std::vector<uint32_t>> sets; // RuntimeContext::animations per animation set, as lmx_anim_add ids
+};
+struct AnimatorsState {
+	std::vector<ControllerHost> controllers;
+	// Animation::RootMotion::translations / rotations per animation (lmx_anim_set_root_motion), LMX_ANIM_NONE: the empty array
+	std::vector<uint32_t> rm_t_of, rm_r_of;
+	std::vector<float> rm_t, rm_r;
+	bool clips_dirty = true;
+	size_t clips_uploaded = 0;
+	DevBuf<CtlClip> d_clips;
+	DevBuf<float> d_rm_t, d_rm_r;
+	// what lmx_animators_set built
+	bool is_set = false;
+	bool any_ik = false; // a controller in use has an IK node: the frame runs k_anim_blend_instrs, otherwise k_anim_blend_stack
+	uint32_t n = 0, n_active = 0, n_rm = 0, flip = 0, total_slots = 0, total_inputs = 0;
+	std::vector<CtlAnimator> animators;
+	std::vector<uint32_t> input_types; // per Value record of the inputs buffer
+	std::unordered_map<uint64_t, uint32_t> slots_at; // (controller, set) -> its place in d_slots
+	DevBuf<CtlHeader> d_headers;
+	DevBuf<CtlNode> d_nodes;
+	DevBuf<CtlOp> d_ops;
+	DevBuf<uint32_t> d_exprs, d_aux, d_slots, d_ik_leaf, d_order, d_inputs, d_input_types, d_state[2], d_state_len, d_counts, d_rm_animator;
+	DevBuf<CtlAnimator> d_animators;
+	DevBuf<float> d_root_motion;
+	DevBuf<LmxBlendInstr> d_slots_out;
+	DevBuf<int32_t> d_rm_entity;
+	DevBuf<LmxTransform> d_rm_tr;
+	DevBuf<uint8_t> d_scan_temp;
+	std::vector<uint32_t> inputs_scratch;
+	std::vector<int32_t> rm_entity; // entities moved by root motion (the Animators with USE_ROOT_MOTION)
+};
+
 struct ProfSlot { hipEvent_t a, b; int kernel; };
 
 
@@ -624,6 +659,7 @@ struct LmxContext {
 	lmx::ClustersState clusters;
 	lmx::RaysState rays;
 	lmx::AnimState anim;
+	lmx::AnimatorsState animators;
 };
 
 namespace lmx {
@@ -635,6 +671,7 @@ int keys_before_layout_change(LmxContext* ctx); // lmx_capi_keys.hip: the slot-o
 int keys_before_tombstones(LmxContext* ctx, const PatchId* d_patches, uint32_t n); // ... for the slots of these id patches (device-visible records; enqueued BEFORE the patch kernel)
 int keys_upload_instances(LmxContext* ctx); // ... the host mirror of the per-entity records goes up if it changed (lmx_keys_run, the draw pass)
 void prof_drain(LmxContext* ctx);
+int anim_upload_tables(LmxContext* ctx);  // lmx_capi_anim.hip: make the device copy of the animation tables current
 int rays_scene_reserve(LmxContext* ctx);  // lmx_capi_rays_scene.hip: the scene stages' buffers for the current reserve and tables (may wait for the stream when they grow)
 int rays_scene_pass(LmxContext* ctx, const RaysDevice& d, const LmxRay* rays, const LmxRayImHit* im_hits); // ... enqueues them behind the entity stage `d`; rays: the caller's
 int cull_flush(LmxContext* ctx);          // lmx_capi_cull.hip: make the device copy of the culling sets current

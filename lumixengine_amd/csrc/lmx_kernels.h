@@ -6,6 +6,7 @@
 
 #include "lmx_math.h"
 #include "lmx_types.h"
+#include "lmx_controller_program.h"
 
 // Dynamic LDS of a launch. (tests/hostsim compiles these sources for the CPU and supplies its own definition: there the block is
 // a buffer of the simulated device, not an `extern __shared__` array.)
@@ -232,6 +233,40 @@ hipError_t launch_anim_blend_stack(hipStream_t s, const SkinInstance* inst, uint
 hipError_t launch_anim_blend_instrs(hipStream_t s, const SkinInstance* inst, uint32_t n_inst, const AnimDevice* anims, const AnimTables& t, uint32_t n_anims,
 	const LmxBlendInstr* instrs, const uint32_t* first_instr, const int16_t* parents, const float* model_rel_pos, const float4* model_rel_rot, float* pose_pos,
 	float4* pose_rot);
+
+// ---- animator controllers (animator_kernels.hip): Controller::update of every Animator, the VM of lmx_controller_program.h ----
+struct CtlHeader { uint32_t nodes_off, ops_off, exprs_off, aux_off, root, n_inputs, state_words, max_instrs; }; // one controller in the concatenated program tables
+struct CtlAnimator {       // one Animator = one skin instance that has a controller
+	uint32_t controller;   // LMX_CONTROLLER_NONE: the lane order does not list it
+	uint32_t slots_off;    // RuntimeContext::animations of its (controller, set)
+	uint32_t state_base;   // its column of the runtime-data words: word k at state[state_base + k * state_stride]
+	uint32_t state_stride; // the Animators of its controller (they are neighbours in the lane order, so a wave reads a word of 64 of them at once)
+	uint32_t input_base;   // in 16-byte Value records
+	uint32_t instr_base;   // its max_instrs records of the instruction slots
+	uint32_t ik_off;       // the resolved leaf bones of its (controller, model)
+	uint32_t flags;
+};
+struct AnimatorTables {
+	const CtlHeader* headers;
+	const CtlNode* nodes;
+	const CtlOp* ops;
+	const uint32_t *exprs, *aux, *slots, *ik_leaf;
+	const CtlClip* clips;
+	const float *rm_t, *rm_r;
+};
+// lane p runs Animator order[p]: state_in -> state_out (+ state_len words), root_motion (7 floats each, read for the stale value and written),
+// slots_out[instr_base ..] and counts
+hipError_t launch_animators_update(hipStream_t s, const AnimatorTables& t, const CtlAnimator* animators, const uint32_t* order, uint32_t n_active, const uint32_t* inputs,
+	const uint32_t* state_in, uint32_t* state_out, uint32_t* state_len, float* root_motion, LmxBlendInstr* slots_out, uint32_t* counts, uint32_t time_delta);
+// the slots' records into the first_instr form of k_anim_blend_instrs (first = exclusive scan of counts); `samples` (optional): their SAMPLE
+// fields in the 16-byte form of k_anim_blend_stack as well, for a call in which no record can be an IK
+hipError_t launch_animators_pack(hipStream_t s, const CtlAnimator* animators, uint32_t n, const uint32_t* first, const uint32_t* counts, const LmxBlendInstr* slots_out,
+	LmxBlendInstr* packed, LmxBlendSample* samples);
+// RuntimeContext::inputs from device memory: the payloads of `values`, typed as the controllers declare them
+hipError_t launch_animators_set_inputs(hipStream_t s, const uint32_t* values, const uint32_t* types, uint32_t* inputs, uint32_t n_records);
+// animation_module.cpp:630-635 for the listed Animators: world transforms of `entity` advanced by root_motion into `out` (LmxTransform records)
+hipError_t launch_animators_root_motion(hipStream_t s, const WorldDevice& w, const int32_t* slot_of_entity, const uint32_t* animator, const int32_t* entity, uint32_t n,
+	const float* root_motion, void* out);
 
 // ---- createSortKeys (keys_kernels.hip) ----
 // Counter words. {pairs, recs} and {poses, dirty} are two 64-bit cells on their own 128-byte lines: k_keys_mesh reserves a tile's four
