@@ -17,6 +17,7 @@
 //                      map_capacity is not written.
 #include "lmx_kernels.h"
 #include "lmx_entity_tr.h"
+#include "lmx_wave.h"
 
 namespace lmx {
 
@@ -24,16 +25,6 @@ namespace {
 
 constexpr uint32_t CLUSTER_WAVES = CLUSTER_BLOCK / 64;
 constexpr uint32_t PLANES_X = 0, PLANES_Y = 65, PLANES_Z = 130;
-
-__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) {
-	const uint32_t s = a + b;
-	return s < a ? 0xffffffffu : s;
-}
-
-__device__ __forceinline__ uint32_t list_length(const ClustersDevice& d) {
-	const uint32_t n = *d.list_count;
-	return n < d.list_cap ? n : d.list_cap;
-}
 
 // planeDist, core/geometry.cpp:826-828
 __device__ __forceinline__ float plane_dist(float4 pl, float x, float y, float z) { return ((pl.x * x + pl.y * y) + pl.z * z) + pl.w; }
@@ -143,8 +134,7 @@ template <bool FILL> __device__ __forceinline__ uint32_t gather(const uint2* ite
 			const bool hit = valid && in_ranges(s_r[sub * 64 + lane], cx1, cy1, cz1);
 			const unsigned long long mask = __ballot(hit);
 			if (FILL) {
-				const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-				const uint32_t to = at + count + rank; // (< offset + total <= map_capacity: the count step saw the same ranges)
+				const uint32_t to = at + count + rank_in(mask); // (< offset + total <= map_capacity: the count step saw the same ranges)
 				if (hit && to < map_capacity) map[to] = (int32_t)(base + sub * 64 + lane);
 			}
 			count += (uint32_t)__popcll(mask);
@@ -190,11 +180,9 @@ __global__ __launch_bounds__(CLUSTER_SCAN_BLOCK) void k_cluster_offsets(Clusters
 	const uint32_t begin = tid * per < d.n_clusters ? tid * per : d.n_clusters, end = begin + per < d.n_clusters ? begin + per : d.n_clusters;
 	uint32_t sum = 0;
 	for (uint32_t c = begin; c < end; ++c) sum = sat_add(sum, d.totals[c]);
-	uint32_t v = sum; // inclusive over the wave, the waves' sums through LDS
-	for (uint32_t off = 1; off < 64; off <<= 1) {
-		const uint32_t up = __shfl_up(v, off);
-		if (lane >= off) v = sat_add(up, v);
-	}
+	// lmx_wave.h's block_scan<true> written out WITHOUT its trailing barrier (s_wave is not used again): with the barrier this one-block
+	// kernel took 15.26-15.27 us against 14.96-15.03 us (tools/cluster_time.py under a kernel trace, profiles/wave/README.md)
+	const uint32_t v = wave_inclusive(sum, lane, SatAdd());
 	if (lane == 63) s_wave[wave] = v;
 	__syncthreads();
 	uint32_t before = 0, all = 0;
@@ -212,7 +200,7 @@ __global__ __launch_bounds__(CLUSTER_SCAN_BLOCK) void k_cluster_offsets(Clusters
 		offset = sat_add(offset, d.totals[c]);
 	}
 	if (tid == 0) {
-		const uint32_t n_listed = *d.list_count < d.list_cap ? *d.list_count : d.list_cap;
+		const uint32_t n_listed = list_length(d);
 		d.state[CLUSTERS_LIGHTS] = n_listed;
 		d.state[CLUSTERS_ENV] = d.n_env;
 		d.state[CLUSTERS_REFL] = d.n_refl;

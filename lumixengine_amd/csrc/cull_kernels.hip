@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "lmx_kernels.h"
+#include "lmx_wave.h" // lane_id(), mbcnt64()
 #include <type_traits>
 
 #include <hip/hip_ext.h>
@@ -29,10 +30,6 @@ namespace lmx {
 
 namespace {
 
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t mbcnt64(uint64_t mask) {
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // a 16-byte access the compiler may only assume 4-byte aligned
 __device__ __forceinline__ float readlane_f(float v, int lane) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), lane)); }
 

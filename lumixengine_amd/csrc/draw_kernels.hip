@@ -13,6 +13,7 @@
 // block through LDS, the blocks through one small launch), no thread per batch.
 #include "lmx_kernels.h"
 #include "lmx_entity_tr.h"
+#include "lmx_wave.h"
 
 namespace lmx {
 
@@ -48,23 +49,11 @@ __device__ __forceinline__ bool head_of(uint32_t fl, uint32_t state_before) {
 }
 
 // Inclusive scan of the block's functions in thread order; *total = the block's composition. s_wave: one word per wave.
+struct FnCompose {
+	__device__ __forceinline__ uint32_t operator()(uint32_t f, uint32_t g) const { return fn_compose(f, g); }
+};
 __device__ __forceinline__ uint32_t block_scan_fn(uint32_t f, uint32_t* s_wave, uint32_t* total) {
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, n_waves = blockDim.x >> 6;
-	for (uint32_t off = 1; off < 64; off <<= 1) {
-		const uint32_t up = __shfl_up(f, off);
-		if (lane >= off) f = fn_compose(up, f);
-	}
-	if (lane == 63) s_wave[wave] = f;
-	__syncthreads();
-	uint32_t pre = FN_IDENTITY, all = FN_IDENTITY;
-	for (uint32_t w = 0; w < n_waves; ++w) {
-		const uint32_t fw = s_wave[w];
-		if (w < wave) pre = fn_compose(pre, fw);
-		all = fn_compose(all, fw);
-	}
-	__syncthreads();
-	*total = all;
-	return fn_compose(pre, f);
+	return block_scan<false>(f, blockDim.x >> 6, FN_IDENTITY, s_wave, total, FnCompose());
 }
 
 __device__ __forceinline__ uint64_t key_mask(const DrawViewDevice& v, uint64_t key) { // instance_key_mask, :2824-2825

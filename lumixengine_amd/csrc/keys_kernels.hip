@@ -14,28 +14,13 @@
 // no single-purpose launch in the chain: TWO launches for key ranges up to 1024 (k_keys_mesh, k_keys_scatter), four beyond (round 4: 8).
 // Integer work is bit-exact by construction; the two fp64 -> fp32 distances use the reference's operation order.
 #include "lmx_kernels.h"
+#include "lmx_wave.h"
 
 #include <algorithm>
 
 namespace lmx {
 
 namespace {
-
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t rank_in(uint64_t mask) {
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// wave-aggregated append: every lane with `want` gets a distinct index of a list whose length lives at *counter
-__device__ __forceinline__ uint32_t wave_append(bool want, uint32_t* counter) {
-	const uint64_t mask = __ballot(want);
-	if (mask == 0) return 0;
-	uint32_t base = 0;
-	const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-	if (lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(mask));
-	base = __shfl(base, (int)leader);
-	return base + rank_in(mask);
-}
 
 // histogram increment with one atomic per distinct key of the wave (a scene of one model puts every lane on one counter)
 __device__ __forceinline__ void wave_histogram(bool want, uint32_t key, uint32_t* hist) {
@@ -93,12 +78,7 @@ struct ShardWalk {
 #pragma unroll
 		for (int h = 0; h < 2; ++h) {
 			u[h] = unit(cnt[h]);
-			uint32_t incl = u[h];
-#pragma unroll
-			for (int o = 1; o < 64; o <<= 1) {
-				const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-				if (lane >= (uint32_t)o) incl += up;
-			}
+			const uint32_t incl = wave_inclusive_sum(u[h], lane);
 			first[h] = before + incl - u[h];
 			before += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 		}
@@ -359,12 +339,7 @@ __global__ __launch_bounds__(KEYS_BLOCK, LMX_KEYS_MIN_WAVES) void k_keys_mesh(Ke
 			push_pose = true;
 		}
 		// ---- block-wide exclusive prefix of (pairs, recs) and ranks of the two flags; one atomic per pair of lists
-		uint32_t incl = n_pairs | (n_recs << 16); // <= 2 * span per lane, <= 64 * that per wave: 16 bits each
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-			if (lane >= (uint32_t)o) incl += up;
-		}
+		const uint32_t incl = wave_inclusive_sum(n_pairs | (n_recs << 16), lane); // <= 2 * span per lane, <= 64 * that per wave: 16 bits each
 		const uint64_t pose_mask = __ballot(push_pose), dirty_mask = __ballot(queue_dirty);
 		if (lane == 63) { s_wave[wave][0] = incl; s_wave[wave][1] = (uint32_t)__popcll(pose_mask); s_wave[wave][2] = (uint32_t)__popcll(dirty_mask); }
 		__syncthreads();
@@ -572,12 +547,7 @@ __global__ __launch_bounds__(256) void k_keys_reduce_copies(KeysDevice d) {
 		const uint32_t c = c0 + lane;
 		const size_t at = (size_t)c * n + k;
 		const uint32_t v = c < d.n_copies ? d.group_count[at] : 0;
-		uint32_t incl = v;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-			if (lane >= (uint32_t)o) incl += up;
-		}
+		const uint32_t incl = wave_inclusive_sum(v, lane);
 		if (c < d.n_copies) {
 			d.group_base[at] = carry + incl - v;
 			d.group_count[at] = 0;
@@ -663,12 +633,7 @@ __global__ __launch_bounds__(1024) void k_keys_offsets(KeysDevice d) {
 		const uint32_t k = base + tid;
 		const uint32_t c = k < n ? d.group_total[k] : 0;
 		non_empty += c != 0;
-		uint32_t incl = c; // inclusive scan inside the wave
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-			if (lane >= (uint32_t)o) incl += up;
-		}
+		const uint32_t incl = wave_inclusive_sum(c, lane);
 		if (lane == 63) s_wave[wave] = incl;
 		__syncthreads();
 		uint32_t before = s_carry;
@@ -719,12 +684,7 @@ template <bool OWN_OFFSETS> __global__ __launch_bounds__(256) void k_keys_scatte
 			if (threadIdx.x < (uint32_t)KEYS_COUNTERS) d.counters_next[threadIdx.x] = 0;
 			for (uint32_t k = threadIdx.x; k < stride; k += 256u) d.total_pad_next[(size_t)k * KEYS_PAD_WORDS] = 0;
 		}
-		uint32_t incl = sum;
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1) {
-			const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-			if (lane >= (uint32_t)o) incl += up;
-		}
+		const uint32_t incl = wave_inclusive_sum(sum, lane);
 		if (lane == 63) s_wave_sum[wave] = incl;
 		__syncthreads();
 		uint32_t run = incl - sum;

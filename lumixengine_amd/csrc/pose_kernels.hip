@@ -14,6 +14,7 @@
 //                   which costs issue slots of a kernel that waits for memory.
 // Sums saturate at 2^32 - 1: a slice that would start or end there lies past any buffer (its size is checked against 32-bit offsets).
 #include "lmx_kernels.h"
+#include "lmx_wave.h"
 
 namespace lmx {
 
@@ -21,16 +22,7 @@ namespace {
 
 constexpr uint32_t POSE_NONE = 0xffffffffu;
 
-__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) {
-	const uint32_t s = a + b;
-	return s < a ? 0xffffffffu : s;
-}
-
-// the list's length as the kernels see it, and block b's part of it: whole tiles of POSE_BLOCK entries
-__device__ __forceinline__ uint32_t list_length(const PosesDevice& d) {
-	const uint32_t n = *d.list_count;
-	return n < d.list_cap ? n : d.list_cap;
-}
+// block b's part of the list (list_length(d) entries): whole tiles of POSE_BLOCK entries
 __device__ __forceinline__ uint32_t part_length(uint32_t n) {
 	const uint32_t per = (n + POSE_GRID - 1) / POSE_GRID;
 	return (per + POSE_BLOCK - 1) / POSE_BLOCK * POSE_BLOCK;
@@ -38,24 +30,7 @@ __device__ __forceinline__ uint32_t part_length(uint32_t n) {
 
 // Exclusive saturating prefix of v in thread order; *total = the block's sum. s_wave: one word per wave.
 __device__ __forceinline__ uint32_t block_scan_sum(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	for (uint32_t off = 1; off < 64; off <<= 1) {
-		const uint32_t up = __shfl_up(v, off);
-		if (lane >= off) v = sat_add(up, v);
-	}
-	if (lane == 63) s_wave[wave] = v;
-	uint32_t before = __shfl_up(v, 1u);
-	if (lane == 0) before = 0;
-	__syncthreads();
-	uint32_t pre = 0, all = 0;
-	for (uint32_t w = 0; w < POSE_BLOCK / 64; ++w) {
-		const uint32_t sw = s_wave[w];
-		if (w < wave) pre = sat_add(pre, sw);
-		all = sat_add(all, sw);
-	}
-	__syncthreads();
-	*total = all;
-	return sat_add(pre, before);
+	return block_scan<true>(v, POSE_BLOCK / 64, 0u, s_wave, total, SatAdd());
 }
 
 // Step 1. entries[i] = {entity, first bone in the pose arrays, n_bones, first bone of the model's inverse bind}; y = POSE_NONE: no skin instance.

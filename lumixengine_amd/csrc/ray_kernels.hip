@@ -31,6 +31,7 @@
 #include "lmx_im.h"
 #include "lmx_ray_math.h"
 #include "lmx_skin_eval.h"
+#include "lmx_wave.h"
 
 namespace lmx {
 
@@ -170,12 +171,15 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_ray_broad(RaysDevice d) {
 					pass = ray_sphere(o, dir, radius) && ray_aabb(o, dir, mn, mx);
 				}
 			}
+			// The append is written out, with lane 0 as the leader (every lane is here): lmx_wave.h's wave_append picks its leader from the
+			// ballot, which this loop pays once per ray - the kernel's average over tools/ray_time.py's batches was 90.7-90.8 ms with it
+			// against 90.1-90.3 ms (k_imray_broad below: 23.2 against 21.1-21.2 ms; k_pgray_broad: 99.4-99.7 against 98.7-98.9 us).
 			const unsigned long long mask = __ballot(pass);
 			if (mask == 0) continue; // (wave-uniform)
 			unsigned long long base = 0; // (64 bits: rays x entities can pass 2^32, and the count is the size a larger reserve needs)
 			if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long*>(d.state + RAYS_COUNTER), (unsigned long long)__popcll(mask));
 			base = __shfl(base, 0);
-			const unsigned long long slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+			const unsigned long long slot = base + rank_in(mask);
 			if (pass && slot < d.max_cand) {
 				RayCandidate c;
 				c.ray = ray0 + r; c.entity = e;
@@ -373,12 +377,12 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_imray_broad(ImRaysDevice q) {
 					o = rotate(conjugated(rot), V3{rel.x * inv_scale, rel.y * inv_scale, rel.z * inv_scale});
 				}
 			}
-			const unsigned long long mask = __ballot(pass);
+			const unsigned long long mask = __ballot(pass); // (written out, lane 0 leads: see k_ray_broad)
 			if (mask == 0) continue; // (wave-uniform)
 			unsigned long long base = 0;
 			if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long*>(d.state + RAYS_COUNTER), (unsigned long long)__popcll(mask));
 			base = __shfl(base, 0);
-			const unsigned long long at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+			const unsigned long long at = base + rank_in(mask);
 			if (pass && at < d.max_cand) {
 				RayCandidate c;
 				c.ray = ray0 + r; c.entity = slot;

@@ -22,6 +22,7 @@
 #include "lmx_kernels.h"
 #include "lmx_entity_tr.h"
 #include "lmx_ray_math.h"
+#include "lmx_wave.h"
 #include "lmx_terrain_height.h" // both Terrain::getHeight, shared with grass_kernels.hip
 
 namespace lmx {
@@ -97,12 +98,12 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_pgray_broad(SceneRaysDevice q) {
 				float tmin;
 				pass = contains || ray_aabb_tmin(ro, rd, mn, mx, &tmin);
 			}
-			const unsigned long long mask = __ballot(pass);
+			const unsigned long long mask = __ballot(pass); // (written out, lane 0 leads: see k_ray_broad, ray_kernels.hip)
 			if (mask == 0) continue; // (wave-uniform)
 			unsigned long long base = 0;
 			if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long*>(d.state + RAYS_COUNTER), (unsigned long long)__popcll(mask));
 			base = __shfl(base, 0);
-			const unsigned long long at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+			const unsigned long long at = base + rank_in(mask);
 			if (pass && at < d.max_cand) {
 				RayCandidate c;
 				c.ray = ray0 + r; c.entity = g;

@@ -9,6 +9,7 @@
 // level from its parent's already-final world transform (fp64 position, fp32 rotation/scale, no FMA), so sibling
 // lanes read the same or adjacent parent slots. A fused pass refreshes the culling spheres of bound entities.
 #include "lmx_kernels.h"
+#include "lmx_wave.h"
 
 namespace lmx {
 
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(256, LMX_XFORM_MIN_WAVES) void k_xform_subtree(Worl
 	// address per 64 nodes - 15.6 k of them for 10^6 moved nodes, ~180 us at the ~90 per microsecond one address retires (measured: 203 us).
 	// Inside the block's range a wave's entries of one step are consecutive (ballot + mbcnt ranks): a step writes one run of <= 64
 	// 56-byte transforms and one of ids, not 64 scattered ones (a thread numbering its own slots: 65 us for 10^6 moved nodes, 23 untracked).
-	const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), wave = tid >> 6;
+	const uint32_t lane = lane_id(), wave = tid >> 6;
 	uint32_t wave_at = 0; // wave-uniform: the wave's next free entry
 	if (a.count != nullptr) {
 		uint32_t wave_total = 0;
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(256, LMX_XFORM_MIN_WAVES) void k_xform_subtree(Worl
 			if (mark != 0) w.dirty[s] = 0;
 			const bool collect = (mark & XF_MOVED) != 0 && a.count != nullptr;
 			const uint64_t mask = __ballot(collect);
-			const uint32_t at = wave_at + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+			const uint32_t at = wave_at + rank_in(mask);
 			wave_at += (uint32_t)__popcll(mask);
 			const uint32_t dyn = live && a.bound_dyn_of_slot != nullptr ? a.bound_dyn_of_slot[s] : 0xffffffffu;
 			if (dyn == 0xffffffffu && !collect) continue;
@@ -293,16 +294,9 @@ __global__ __launch_bounds__(256) void k_xform_collect_moved(WorldDevice w, cons
 	int32_t* __restrict__ out_entity, TransformAoS* __restrict__ out_tr, uint32_t* __restrict__ count) {
 	const uint32_t s = blockIdx.x * 256u + threadIdx.x;
 	const bool moved = s < n && (w.dirty[s] & XF_MOVED) != 0;
-	const uint64_t mask = __ballot(moved);
 	if (s < n && w.dirty[s] != 0) w.dirty[s] = 0;
-	if (mask == 0) return;
-	const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-	uint32_t base = 0;
-	if (lane == 0) base = atomicAdd(count, (uint32_t)__popcll(mask));
-	base = __builtin_amdgcn_readfirstlane(base);
-	if (!moved) return;
-	const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-	if (at >= cap) return;
+	const uint32_t at = wave_append(moved, count);
+	if (!moved || at >= cap) return;
 	const float4 r = w.wrot[s];
 	TransformAoS t;
 	t.pos[0] = w.wpx[s]; t.pos[1] = w.wpy[s]; t.pos[2] = w.wpz[s];

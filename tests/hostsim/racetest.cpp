@@ -3,11 +3,15 @@
 //   racy_global  two blocks add to one global word with plain loads and stores       -> must be reported
 //   clean        the same exchange behind __syncthreads(), the global word by atomicAdd, lanes of ONE wave exchanging through LDS behind
 //                the wave barrier                                                      -> must be quiet
+//   scan_twice   two block_scan calls of csrc/lmx_wave.h back to back over ONE s_wave (the header's reuse contract: the trailing
+//                barrier is what keeps a fast wave's next write off the words a slow wave still reads) -> must be quiet
 // argv[1] selects the kernel; the caller greps ThreadSanitizer's report.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
+
+#include "lmx_wave.h"
 
 namespace {
 
@@ -36,6 +40,15 @@ __global__ void clean(uint32_t* out) {
 	if (lane == 0) atomicAdd(out, 1u);
 }
 
+__global__ void scan_twice(uint32_t* out) {
+	__shared__ uint32_t s_wave[4];
+	uint32_t total;
+	const uint32_t first = lmx::block_scan<true>(threadIdx.x, 4u, 0u, s_wave, &total, lmx::Sum());
+	const uint32_t second = lmx::block_scan<false>(first, 4u, 0u, s_wave, &total, lmx::SatAdd());
+	out[1 + threadIdx.x] = second;
+	if (threadIdx.x == 0) atomicAdd(out, total);
+}
+
 } // namespace
 
 int main(int argc, char** argv) {
@@ -45,6 +58,7 @@ int main(int argc, char** argv) {
 	const char* which = argc > 1 ? argv[1] : "clean";
 	if (!strcmp(which, "racy_lds")) hipLaunchKernelGGL(racy_lds, dim3(1), dim3(128), 0, 0, d);
 	else if (!strcmp(which, "racy_global")) hipLaunchKernelGGL(racy_global, dim3(2), dim3(64), 0, 0, d);
+	else if (!strcmp(which, "scan_twice")) hipLaunchKernelGGL(scan_twice, dim3(1), dim3(256), 0, 0, d);
 	else hipLaunchKernelGGL(clean, dim3(4), dim3(128), 0, 0, d);
 	uint32_t h = 0;
 	(void)hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost);

@@ -19,14 +19,15 @@ SLOW = "full_size or 100m or config2_10m or add_stream or slab_all or async_comp
 
 
 def test_simulated_device_semantics():
-    """The simulator itself: ballots / ranks / readlane under divergence, early-exit loops, shuffles, DPP, LDS behind both barriers."""
+    """The simulator itself: ballots / ranks / readlane under divergence, early-exit loops, shuffles, DPP, LDS behind both barriers -
+    and on it the kernels' wave / block vocabulary (csrc/lmx_wave.h: scans and appends) against a sequential fold on the host."""
     out_dir = os.path.join(ROOT, "tests", "_build")
     os.makedirs(out_dir, exist_ok=True)
     exe = os.path.join(out_dir, "hostsim_selftest")
     hs = os.path.join(ROOT, "tests", "hostsim")
     for opt in ("-O2", "-O0"):  # convergence groups are found by code address: the layout of both must work
-        subprocess.run([CLANG, "-std=c++17", opt, "-ffp-contract=off", "-I" + os.path.join(hs, "include"), "-Wno-unknown-attributes", "-x", "c++",
-                        os.path.join(hs, "selftest.cpp"), os.path.join(hs, "hostsim_runtime.cpp"), "-o", exe, "-pthread"], check=True, capture_output=True)
+        subprocess.run([CLANG, "-std=c++17", opt, "-ffp-contract=off", "-I" + os.path.join(hs, "include"), "-I" + os.path.join(ROOT, "lumixengine_amd", "csrc"),
+                        "-Wno-unknown-attributes", "-x", "c++", os.path.join(hs, "selftest.cpp"), os.path.join(hs, "hostsim_runtime.cpp"), "-o", exe, "-pthread"], check=True, capture_output=True)
         r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and "selftest: ok" in r.stdout, opt + "\n" + r.stdout + r.stderr
 
@@ -98,16 +99,17 @@ def test_race_detector_reports_races_and_only_races(tmp_path):
     """The kernel-level race detector (ThreadSanitizer build of the simulated device + HOSTSIM_RACE=1: every wave a fiber, no ordering but
     the hardware's - launch, __syncthreads(), completion; blocks spread over two host threads): an LDS exchange between two waves without
     a barrier and a plain read-modify-write of one global word by two blocks must be reported, the same exchanges behind the barriers /
-    through an atomic must not."""
+    through an atomic must not - and neither must two block scans of csrc/lmx_wave.h back to back over one s_wave."""
     hs = os.path.join(ROOT, "tests", "hostsim")
     exe = str(tmp_path / "racetest")
-    common = [CLANG, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-I" + os.path.join(hs, "include"), "-Wno-unknown-attributes", "-x", "c++", "-c"]
+    common = [CLANG, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-I" + os.path.join(hs, "include"), "-I" + os.path.join(ROOT, "lumixengine_amd", "csrc"),
+              "-Wno-unknown-attributes", "-x", "c++", "-c"]
     subprocess.run(common + ["-DHOSTSIM_WITH_TSAN=1", os.path.join(hs, "hostsim_runtime.cpp"), "-o", str(tmp_path / "rt.o")], check=True, capture_output=True)
     subprocess.run(common + ["-fsanitize=thread", "-mllvm", "-tsan-instrument-func-entry-exit=0", os.path.join(hs, "racetest.cpp"), "-o", str(tmp_path / "k.o")],
                    check=True, capture_output=True)
     subprocess.run([CLANG, "-fsanitize=thread", str(tmp_path / "k.o"), str(tmp_path / "rt.o"), "-o", exe, "-pthread"], check=True, capture_output=True)
     env = dict(os.environ, HOSTSIM_RACE="1", TSAN_OPTIONS="halt_on_error=0 report_signal_unsafe=0 exitcode=0")
-    for kernel, racy in (("racy_lds", True), ("racy_global", True), ("clean", False)):
+    for kernel, racy in (("racy_lds", True), ("racy_global", True), ("clean", False), ("scan_twice", False)):
         r = subprocess.run([exe, kernel], env=env, capture_output=True, text=True, timeout=120)
         assert f"{kernel} done" in r.stdout, r.stdout + r.stderr
         assert ("ThreadSanitizer: data race" in r.stderr) == racy, kernel + "\n" + r.stderr[-3000:]
