@@ -23,7 +23,8 @@ struct GrassTexture {
 };
 
 struct GrassModel {
-	bool isReady() const { return true; }
+	bool ready = true;
+	bool isReady() const { return ready; }
 };
 
 struct Terrain {
@@ -40,8 +41,9 @@ struct Terrain {
 	std::vector<GrassType> m_grass_types;
 };
 
-struct GrassWorld {
-	DVec3 getPosition(EntityRef) const { return DVec3{0, 0, 0}; }
+struct GrassWorld { // World::getPosition: by entity index, the origin for an entity the test gave no position
+	std::vector<DVec3> positions;
+	DVec3 getPosition(EntityRef e) const { return e.index >= 0 && (size_t)e.index < positions.size() ? positions[e.index] : DVec3{0, 0, 0}; }
 };
 
 } // namespace Lumix
