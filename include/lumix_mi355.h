@@ -318,6 +318,41 @@ LMX_API int lmx_world_build_with_world(LmxContext* ctx, uint32_t n, const int32_
  * (LMX_ERR_INVALID_ARGUMENT, the reference logs "Hierarchy can not contain a cycle."). Editing operation: rebuilds the
  * slot order on the host; culling bindings survive. */
 LMX_API int lmx_world_set_parent(LmxContext* ctx, int32_t new_parent, int32_t child);
+/* World::destroyEntity / createEntity / setParent (engine/world.cpp:521-561, 489-519, 619-701) for a batch, applied as that sequence
+ * of World calls: every destroy, then every create, then the re-parentings in list order. The slot order is derived again on the
+ * device and the transforms move between two sets of arrays in HBM: per call the bus carries the batch, one word per level and one
+ * word per root. Every consumer that reads the world (sort keys, draws, rays, clusters, root motion) sees the new order at its next
+ * launch, with no re-bind.
+ *   Entity indices  are the engine's; the World's free list stays with the engine.
+ *   Create beyond n create_entity[i] >= n grows the index range to max + 1; indices in between that were never created are dead.
+ *   Dead entities   keep their index. A dead entity is never in the moved list, never moves a culling sphere, and is refused by the
+ *                   staging calls (lmx_world_set_transforms, lmx_world_set_world_transforms, lmx_animators_apply_root_motion:
+ *                   LMX_ERR_INVALID_ARGUMENT; lmx_world_set_transforms_device cannot check). What lmx_world_read_transforms /
+ *                   lmx_world_read_local_transforms return for it is not specified.
+ *   Destroy         kills the entity and all its descendants, as destroyEntity does; listing a descendant as well is allowed. A
+ *                   culling binding or bone attachment of a destroyed entity (an attachment also with its parent entity) is
+ *                   dropped - for good: it does not come back when the index is created again, in the same call or later (bind
+ *                   the new entity with lmx_world_bind_culling) -; all others survive the call, unlike lmx_world_set_parent.
+ *   Create          makes a root with the given world transform (all three parts, as World::deserialize writes them). An index
+ *                   destroyed earlier in the same call may be created again; a created entity may be named as new_parent or child
+ *                   in the same call.
+ *   Re-parent       is World::setParent: the child keeps its world transform, its stored local becomes
+ *                   Transform::computeLocal(parent world, child world); new_parent < 0 detaches. Every other entity's stored local
+ *                   is carried over bit for bit.
+ *   Refusals        before anything is launched the host checks range, liveness, duplicates in create_entity and cycles against the
+ *                   list order, with its mirror of `parent` in O(batch x depth). A refused call (LMX_ERR_INVALID_ARGUMENT) leaves
+ *                   the world bit for bit as it was; no kernel sees an index that was not checked. A call that fails later (a HIP
+ *                   error) takes the batch back out of the host's mirror; `edits` counts neither.
+ *   Pending writes  the reference propagates every write before the next call, so if anything was staged since the last
+ *                   lmx_world_propagate (lmx_world_set_*, also the _device form, lmx_world_update_bone_attachments,
+ *                   lmx_animators_apply_root_motion, a first build from locals) lmx_world_edit propagates first. That
+ *                   propagation's moved list stays readable.
+ * lmx_world_info: n = the index range, n_live = live entities, n_levels, fused = whether the next propagation takes the one-launch
+ * path (the same answer a fresh build of the same hierarchy gives), edits = successful lmx_world_edit calls since the last lmx_world_build*. */
+LMX_API int lmx_world_edit(LmxContext* ctx, uint32_t n_destroy, const int32_t* destroy_entity, uint32_t n_create, const int32_t* create_entity,
+	const LmxTransform* create_transform, uint32_t n_reparent, const int32_t* new_parent, const int32_t* child);
+typedef struct LmxWorldInfo { uint32_t n, n_live, n_levels, fused, edits, reserved[3]; } LmxWorldInfo;
+LMX_API int lmx_world_info(LmxContext* ctx, LmxWorldInfo* out);
 /* World::getLocalTransform (world.cpp:756-766) for every entity: Hierarchy::local_transform, or the world transform of
  * entities without a parent. */
 LMX_API int lmx_world_read_local_transforms(LmxContext* ctx, LmxTransform* out, uint32_t n);

@@ -227,6 +227,8 @@ SYMBOLS = {
     "lmx_world_build": (_ci, [_vp, _u32, _vp, _vp]),
     "lmx_world_build_with_world": (_ci, [_vp, _u32, _vp, _vp, _vp]),
     "lmx_world_set_parent": (_ci, [_vp, _i32, _i32]),
+    "lmx_world_edit": (_ci, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "lmx_world_info": (_ci, [_vp, _vp]),
     "lmx_world_read_local_transforms": (_ci, [_vp, _vp, _u32]),
     "lmx_transform_compose": (_ci, [_vp, _vp, _vp]),
     "lmx_transform_compute_local": (_ci, [_vp, _vp, _vp]),
@@ -819,6 +821,9 @@ class VisibleExchange:
         return self.readMany(slot, rank, 0)
 
 
+WORLD_INFO = np.dtype([("n", "<u4"), ("n_live", "<u4"), ("n_levels", "<u4"), ("fused", "<u4"), ("edits", "<u4"), ("reserved", "<u4", 3)])  # LmxWorldInfo
+
+
 class World:
     """Batch form of World's transform hierarchy (src/engine/world.cpp:255-282)."""
 
@@ -869,6 +874,26 @@ class World:
     def setParent(self, new_parent: int, child: int):
         """World::setParent (world.cpp:619-701); new_parent < 0 detaches."""
         self.ctx.check(self.lib.lmx_world_set_parent(self.ctx.h, int(new_parent), int(child)))
+
+    def edit(self, destroy=(), create=(), create_transforms=None, reparent=()):
+        """World::destroyEntity / createEntity / setParent for a batch (lmx_world_edit): every destroy, then every create (roots with
+        `create_transforms` as world transforms), then reparent = [(new_parent, child), ...] in list order; new_parent < 0 detaches.
+        The slot order is derived again on the device; a refused batch (LumixError) leaves the world as it was."""
+        destroy = np.ascontiguousarray(destroy, np.int32).reshape(-1)
+        create = np.ascontiguousarray(create, np.int32).reshape(-1)
+        tr = np.zeros(0, TRANSFORM) if create_transforms is None else np.ascontiguousarray(create_transforms, TRANSFORM).reshape(-1)
+        assert len(tr) == len(create)
+        rp = np.ascontiguousarray(reparent, np.int32).reshape(-1, 2)
+        new_parent, child = np.ascontiguousarray(rp[:, 0]), np.ascontiguousarray(rp[:, 1])
+        self.ctx.check(self.lib.lmx_world_edit(self.ctx.h, len(destroy), _ptr(destroy) if len(destroy) else None, len(create), _ptr(create) if len(create) else None,
+                                               _ptr(tr) if len(tr) else None, len(child), _ptr(new_parent) if len(child) else None, _ptr(child) if len(child) else None))
+        self.n = self.info()["n"]
+
+    def info(self) -> dict:
+        """{"n": index range, "n_live", "n_levels", "fused": the next propagate() takes the one-launch path, "edits": successful edit() calls}"""
+        out = np.zeros(1, WORLD_INFO)
+        self.ctx.check(self.lib.lmx_world_info(self.ctx.h, _ptr(out)))
+        return {k: int(out[k][0]) for k in ("n", "n_live", "n_levels", "fused", "edits")}
 
     def setBoneAttachments(self, entity, parent_entity, skin_instance, bone_index, relative):
         """RenderModuleImpl::m_bone_attachments: entity follows bone `bone_index` of `skin_instance`, posed on `parent_entity`."""

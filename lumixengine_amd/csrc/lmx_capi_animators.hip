@@ -392,6 +392,10 @@ int lmx_animators_apply_root_motion(LmxContext* ctx) {
 	if (!as.n_rm) return LMX_OK;
 	for (int32_t e : as.rm_entity) // (lmx_animators_set may have run before the world was built)
 		if ((uint32_t)e >= w.n) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "root-motion entity %d out of range", e);
+	if (w.n_live != w.n)
+		for (int32_t e : as.rm_entity)
+			if (!w.mirror.alive(e)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "root-motion entity %d was destroyed", e);
+	w.pending = true; // staged like lmx_world_set_world_transforms: lmx_world_edit propagates first
 	LMX_HIP(ctx, launch_animators_root_motion(ctx->stream, w.dev(), w.d_slot_of_entity.p, as.d_rm_animator.p, as.d_rm_entity.p, as.n_rm, as.d_root_motion.p, as.d_rm_tr.p));
 	// World::setTransform (animation_module.cpp:634): the path of lmx_world_set_world_transforms, fed from device memory
 	LMX_HIP(ctx, launch_xform_scatter(ctx->stream, w.dev(), w.d_slot_of_entity.p, as.d_rm_entity.p, as.d_rm_tr.p, as.n_rm, XF_STAGE_SET_WORLD));

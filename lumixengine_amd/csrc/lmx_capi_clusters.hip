@@ -48,7 +48,7 @@ int clusters_pass(LmxContext* ctx, const LmxClusterView* cv, const int32_t* d_li
 	LmxClusterPlanes planes;
 	if (lmx_clusters_planes(&cv->frustum, cv->viewport_w, cv->viewport_h, &planes) != LMX_OK)
 		return fail(ctx, LMX_ERR_CAPACITY, "viewport %u x %u: more than %d x %d clusters", cv->viewport_w, cv->viewport_h, LMX_CLUSTER_MAX_XY, LMX_CLUSTER_MAX_XY);
-	if (ds.use_world && ctx->world.slot_of_entity.empty()) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
+	if (ds.use_world && !ctx->world.n) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
 	list_cap = std::min<size_t>(list_cap, 1u << 30);
 	if (cl.d_ranges.cap < std::max<size_t>(list_cap, 1)) {
 		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a pass of the previous view may still read the old ranges)
@@ -60,7 +60,7 @@ int clusters_pass(LmxContext* ctx, const LmxClusterView* cv, const int32_t* d_li
 	if (ds.use_world) {
 		WorldState& w = ctx->world;
 		d.wpx = w.pos[3].p; d.wpy = w.pos[4].p; d.wpz = w.pos[5].p; d.wrot = w.rot[1].p; d.wsx = w.scl[3].p; d.wsy = w.scl[4].p; d.wsz = w.scl[5].p;
-		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = (uint32_t)w.slot_of_entity.size();
+		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = w.n;
 	} else {
 		if (!ds.d_tr.p) LMX_HIP(ctx, ds.d_tr.reserve(1)); // (a non-null pointer selects the uploaded array; n_tr == 0 reads zeros)
 		d.tr = ds.d_tr.p; d.n_tr = ds.n_tr;

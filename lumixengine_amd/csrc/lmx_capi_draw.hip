@@ -34,7 +34,7 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 	if (!n_batches) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "n_batches must be at least 1");
 	if ((uint64_t)n * 96 + 16 > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "%u pairs: the instance buffer's offsets are 32 bits", n);
 	if ((uint64_t)n_group_values * 48 + 16 > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "%u instanced renderables: the group buffer's offsets are 32 bits", n_group_values);
-	if (ds.use_world && ctx->world.slot_of_entity.empty()) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
+	if (ds.use_world && !ctx->world.n) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
 	if (int rc = keys_upload_instances(ctx)) return rc; // as lmx_keys_run
 	// ModelInstance::lod of the sorted set's entities lives in the slot-ordered mirror: hand it to the entity-indexed records the encode
 	// reads (what lmx_keys_read_state does; the mirror stays valid)
@@ -81,7 +81,7 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 	if (ds.use_world) {
 		WorldState& w = ctx->world;
 		d.wpx = w.pos[3].p; d.wpy = w.pos[4].p; d.wpz = w.pos[5].p; d.wrot = w.rot[1].p; d.wsx = w.scl[3].p; d.wsy = w.scl[4].p; d.wsz = w.scl[5].p;
-		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = (uint32_t)w.slot_of_entity.size();
+		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = w.n;
 	} else {
 		if (!ds.d_tr.p) LMX_HIP(ctx, ds.d_tr.reserve(1)); // (a non-null pointer selects the uploaded array; n_tr == 0 reads zeros)
 		d.tr = ds.d_tr.p; d.n_tr = ds.n_tr;

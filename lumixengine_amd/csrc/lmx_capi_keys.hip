@@ -259,7 +259,7 @@ int lmx_keys_run(LmxContext* ctx, uint32_t view, uint32_t frustum, const LmxKeys
 	if (!ks.have_instances && !ks.have_decals && !ks.have_curves) return fail(ctx, LMX_ERR_NOT_BUILT, "no instance / decal tables uploaded");
 	const WorldState& w = ctx->world;
 	if (ks.use_world) {
-		if (w.slot_of_entity.size() < ks.n_entities) return fail(ctx, LMX_ERR_NOT_BUILT, "world hierarchy covers %zu entities, instance tables %u", w.slot_of_entity.size(), ks.n_entities);
+		if (w.n < ks.n_entities) return fail(ctx, LMX_ERR_NOT_BUILT, "world hierarchy covers %u entities, instance tables %u", w.n, ks.n_entities);
 	} else if (ks.have_instances && ks.n_positions < ks.n_entities) {
 		return fail(ctx, LMX_ERR_NOT_BUILT, "positions cover %u entities, instance tables %u", ks.n_positions, ks.n_entities);
 	}

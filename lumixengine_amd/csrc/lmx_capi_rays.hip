@@ -82,7 +82,7 @@ int rays_pass(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 	if (!rs.have_instances) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_set_instances has not been called");
 	if (!rs.reserved) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_reserve has not been called");
 	if (n > rs.max_rays) return fail(ctx, LMX_ERR_CAPACITY, "%u rays: %u reserved", n, rs.max_rays);
-	if (ds.use_world && ctx->world.slot_of_entity.empty()) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
+	if (ds.use_world && !ctx->world.n) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
 	if (int rc = rays_upload_meshes(ctx)) return rc;
 	RaysDevice d;
 	memset(&d, 0, sizeof(d));
@@ -91,7 +91,7 @@ int rays_pass(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 	if (ds.use_world) {
 		WorldState& w = ctx->world;
 		d.wpx = w.pos[3].p; d.wpy = w.pos[4].p; d.wpz = w.pos[5].p; d.wrot = w.rot[1].p; d.wsx = w.scl[3].p; d.wsy = w.scl[4].p; d.wsz = w.scl[5].p;
-		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = (uint32_t)w.slot_of_entity.size();
+		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = w.n;
 	} else {
 		if (!ds.d_tr.p) LMX_HIP(ctx, ds.d_tr.reserve(1)); // (a non-null pointer selects the uploaded array; n_tr == 0 reads zeros)
 		d.tr = ds.d_tr.p; d.n_tr = ds.n_tr;

@@ -45,7 +45,11 @@ int world_rebuild(LmxContext* ctx, uint32_t n, const int32_t* parent, const LmxT
 	if (entity_of_slot.size() != n) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "hierarchy contains a cycle (%zu of %u entities reachable)", entity_of_slot.size(), n);
 	w.entity_of_slot.swap(entity_of_slot);
 	w.level_start.swap(level_start);
-	w.parent.assign(parent, parent + n);
+	w.mirror.reset(parent, n);
+	w.edit_dev_valid = false;
+	w.host_slots_stale = false;
+	w.n_live = n;
+	w.pending = !world_all && n; // a first build from locals: the first propagation derives every world transform
 	w.slot_of_entity.assign(n, -1);
 	for (uint32_t s = 0; s < n; ++s) w.slot_of_entity[w.entity_of_slot[s]] = (int32_t)s;
 	w.parent_slot.assign(n, -1);
@@ -136,6 +140,18 @@ int world_rebuild(LmxContext* ctx, uint32_t n, const int32_t* parent, const LmxT
 	return LMX_OK;
 }
 
+// slot_of_entity on the host. An edit derives the order on the device and leaves the host's copy stale; the calls that state slots
+// from the host (a new culling binding, new attachments) fetch it again here: 4 bytes per entity, once per edit at the most.
+int world_host_slots(LmxContext* ctx) {
+	WorldState& w = ctx->world;
+	if (!w.host_slots_stale) return LMX_OK;
+	w.slot_of_entity.resize(w.n);
+	LMX_HIP(ctx, read_back(w.slot_of_entity.data(), w.d_slot_of_entity.p, w.n, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	w.host_slots_stale = false;
+	return LMX_OK;
+}
+
 // AoS Transform[n] by entity of either the world values or the stored locals
 int world_download(LmxContext* ctx, bool locals, LmxTransform* out) {
 	WorldState& w = ctx->world;
@@ -176,6 +192,7 @@ int lmx_world_build(LmxContext* ctx, uint32_t n, const int32_t* parent, const Lm
 	WorldState& w = ctx->world;
 	w.bound_entity.clear();
 	w.bound_radius.clear();
+	w.edits = 0;
 	return world_rebuild(ctx, n, parent, transforms, nullptr);
 }
 
@@ -185,6 +202,7 @@ int lmx_world_build_with_world(LmxContext* ctx, uint32_t n, const int32_t* paren
 	WorldState& w = ctx->world;
 	w.bound_entity.clear();
 	w.bound_radius.clear();
+	w.edits = 0;
 	std::vector<LmxTransform> tr(local_transforms, local_transforms + n);
 	for (uint32_t e = 0; e < n; ++e)
 		if (parent[e] < 0) tr[e] = world_transforms[e];
@@ -199,18 +217,28 @@ int lmx_world_set_parent(LmxContext* ctx, int32_t new_parent, int32_t child) {
 	WorldState& w = ctx->world;
 	if (!w.built) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_world_build has not been called");
 	if (child < 0 || (uint32_t)child >= w.n || new_parent >= (int32_t)w.n) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity out of range");
-	for (int32_t a = new_parent; a >= 0; a = w.parent[a]) { // "Hierarchy can not contain a cycle." (world.cpp:621-626)
+	if (w.n_live != w.n && (!w.mirror.alive(child) || (new_parent >= 0 && !w.mirror.alive(new_parent)))) // (indices that lmx_world_edit left dead)
+		return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity %d or %d was destroyed", child, new_parent);
+	for (int32_t a = new_parent; a >= 0; a = w.mirror.parent[a]) { // "Hierarchy can not contain a cycle." (world.cpp:621-626)
 		if (a == child) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity %d is an ancestor of %d: hierarchy can not contain a cycle", child, new_parent);
 	}
 	std::vector<LmxTransform> world(w.n), tr(w.n);
 	if (int rc = world_download(ctx, false, world.data())) return rc;
 	if (int rc = world_download(ctx, true, tr.data())) return rc;
-	std::vector<int32_t> parent = w.parent;
+	std::vector<int32_t> parent; // (as a fresh build states it: entities that lmx_world_edit destroyed are roots)
+	std::vector<uint8_t> alive;
+	w.mirror.resolve(&parent, &alive);
+	const uint32_t n_live = w.n_live;
+	const bool pending = w.pending; // (what was staged stays staged: the world values travel, the next propagation composes with them)
 	parent[child] = new_parent < 0 ? -1 : new_parent;
 	for (uint32_t e = 0; e < w.n; ++e)
 		if (parent[e] < 0) tr[e] = world[e];
 	if (new_parent >= 0) store_xform(compute_local(load_xform(world[new_parent]), load_xform(world[child])), &tr[child]);
-	return world_rebuild(ctx, w.n, parent.data(), tr.data(), world.data());
+	if (int rc = world_rebuild(ctx, w.n, parent.data(), tr.data(), world.data())) return rc;
+	for (uint32_t e = 0; e < w.n; ++e) w.mirror.born[e] = alive[e];
+	w.n_live = n_live;
+	w.pending = pending;
+	return LMX_OK;
 }
 
 int lmx_world_read_local_transforms(LmxContext* ctx, LmxTransform* out, uint32_t n) { // World::getLocalTransform, world.cpp:756-766
@@ -222,7 +250,7 @@ int lmx_world_read_local_transforms(LmxContext* ctx, LmxTransform* out, uint32_t
 	if (int rc = world_download(ctx, true, out)) return rc;
 	if (int rc = world_download(ctx, false, world.data())) return rc;
 	for (uint32_t e = 0; e < w.n; ++e)
-		if (w.parent[e] < 0) out[e] = world[e]; // entities without a parent: their transform (world.cpp:759)
+		if (w.mirror.parent[e] < 0) out[e] = world[e]; // entities without a parent: their transform (world.cpp:759)
 	return LMX_OK;
 }
 
@@ -246,6 +274,10 @@ static int world_stage(LmxContext* ctx, uint32_t n, const int32_t* entity, const
 	if (!entity || !transforms) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null input array");
 	for (uint32_t i = 0; i < n; ++i)
 		if (entity[i] < 0 || (uint32_t)entity[i] >= w.n) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity[%u] = %d out of range", i, entity[i]);
+	if (w.n_live != w.n) // lmx_world_edit left dead indices in the range: they take no writes
+		for (uint32_t i = 0; i < n; ++i)
+			if (!w.mirror.alive(entity[i])) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity[%u] = %d was destroyed", i, entity[i]);
+	w.pending = true;
 	// The scatter kernel runs one thread per record: two records of ONE entity in a batch would race (SoA components of the two mixed).
 	// The reference applies writes one by one - the last one wins - so only the last record of an entity is staged.
 	std::vector<int32_t> ent_dedup;
@@ -302,6 +334,7 @@ int lmx_world_set_transforms_device(LmxContext* ctx, uint32_t n, const void* d_e
 	if (!w.built) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_world_build has not been called");
 	if (!n) return LMX_OK;
 	if (!d_entity || !d_transforms) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null device pointer");
+	w.pending = true;
 	LMX_HIP(ctx, launch_xform_scatter(ctx->stream, w.dev(), w.d_slot_of_entity.p, (const int32_t*)d_entity, d_transforms, n, XF_STAGE_SET_LOCAL));
 	return LMX_OK;
 }
@@ -313,12 +346,14 @@ int lmx_world_bind_culling(LmxContext* ctx, uint32_t n, const int32_t* entity, c
 	if (n && (!entity || !model_radius)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null input array");
 	for (uint32_t i = 0; i < n; ++i) {
 		if (entity[i] < 0 || (uint32_t)entity[i] >= w.n) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity[%u] = %d out of range", i, entity[i]);
+		if (w.n_live != w.n && !w.mirror.alive(entity[i])) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity[%u] = %d was destroyed", i, entity[i]);
 		if (!lmx_cull_is_added(ctx, entity[i])) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity %d is not in the culling system", entity[i]);
 	}
 	// bound entities move every frame: they live in the culling system's dynamic (unsorted) set from now on; entities of the
 	// previous binding that are not bound again keep their last refreshed sphere and rejoin the sorted set at its next compaction
 	if (int rc = cull_dyn_sync_mirror(ctx)) return rc;
-	for (int32_t e : w.bound_entity) cull_unbind(ctx, e);
+	for (int32_t e : w.bound_entity)
+		if (e >= 0) cull_unbind(ctx, e); // (< 0: a binding that lmx_world_edit dropped with its entity)
 	for (uint32_t i = 0; i < n; ++i) {
 		if (!cull_make_dynamic(ctx, entity[i])) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity %d is not in the culling system", entity[i]);
 	}
@@ -335,8 +370,19 @@ static int world_upload_binding(LmxContext* ctx) {
 	if (w.bound_generation == cs.dyn_generation) return LMX_OK;
 	const size_t n = w.bound_entity.size();
 	std::vector<uint32_t> slot(n), dyn(n);
+	if (int rc = world_host_slots(ctx)) return rc;
 	for (size_t i = 0; i < n; ++i) {
 		const int32_t e = w.bound_entity[i];
+		// a binding dropped by lmx_world_edit (its entry is -1 from then on, also when the index is created again), or - while an edit's
+		// own propagation runs - one of an entity the batch kills, whatever becomes of its index afterwards: the engine may have taken
+		// it out of the culling system already. The edit voids those entries of the host's list when it is through (edit_skipped).
+		const bool killed = e >= 0 && w.edit_in_flight && w.edit_kills(e);
+		if (killed) w.edit_skipped.push_back((uint32_t)i);
+		if (e < 0 || killed) {
+			slot[i] = 0xffffffffu;
+			dyn[i] = 0;
+			continue;
+		}
 		if ((size_t)e >= cs.ent_to_dyn.size() || cs.ent_to_dyn[e] < 0)
 			return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "bound entity %d was removed from the culling system; call lmx_world_bind_culling again", e);
 		slot[i] = (uint32_t)w.slot_of_entity[e];
@@ -353,6 +399,7 @@ static int world_upload_binding(LmxContext* ctx) {
 		std::vector<uint32_t> dyn_of_slot(std::max<size_t>(w.n, 1), 0xffffffffu);
 		std::vector<float> radius_of_slot(std::max<size_t>(w.n, 1), 0.f);
 		for (size_t i = 0; i < n; ++i) {
+			if (slot[i] == 0xffffffffu) continue;
 			dyn_of_slot[slot[i]] = dyn[i];
 			radius_of_slot[slot[i]] = w.bound_radius[i];
 		}
@@ -408,6 +455,7 @@ int lmx_world_propagate(LmxContext* ctx) {
 		}
 	}
 	if (bound) cs.dyn_mirror_stale = true; // the device copy of the bound entities is now newer than the host mirror
+	w.pending = false;
 	return LMX_OK;
 }
 
@@ -420,10 +468,13 @@ int lmx_world_set_bone_attachments(LmxContext* ctx, uint32_t n, const int32_t* e
 	if (n && (!entity || !parent_entity || !skin_instance || !bone_index || !relative)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null input array");
 	std::vector<BoneAttachDevice> att(n);
 	std::vector<uint8_t> attached(w.n, 0);
+	if (int rc = world_host_slots(ctx)) return rc;
 	for (uint32_t i = 0; i < n; ++i) {
 		if (entity[i] < 0 || (uint32_t)entity[i] >= w.n || parent_entity[i] < 0 || (uint32_t)parent_entity[i] >= w.n)
 			return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "attachment %u: entity %d / parent %d out of range", i, entity[i], parent_entity[i]);
-		if (w.parent[entity[i]] >= 0) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "attachment %u: entity %d has a hierarchy parent; attached entities are moved with World::setTransform as roots", i, entity[i]);
+		if (w.n_live != w.n && (!w.mirror.alive(entity[i]) || !w.mirror.alive(parent_entity[i])))
+			return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "attachment %u: entity %d / parent %d was destroyed", i, entity[i], parent_entity[i]);
+		if (w.mirror.parent[entity[i]] >= 0) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "attachment %u: entity %d has a hierarchy parent; attached entities are moved with World::setTransform as roots", i, entity[i]);
 		if (attached[entity[i]]) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "entity %d is attached twice", entity[i]);
 		attached[entity[i]] = 1;
 		if (skin_instance[i] >= sk.inst.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "attachment %u: unknown skin instance %u", i, skin_instance[i]);
@@ -456,6 +507,7 @@ int lmx_world_update_bone_attachments(LmxContext* ctx) {
 	if (!w.n_attach) return LMX_OK;
 	if (w.attach_skin_instances != sk.inst.size()) return fail(ctx, LMX_ERR_NOT_BUILT, "the skin instance table changed; call lmx_world_set_bone_attachments again");
 	if (!sk.pose_is_absolute) return fail(ctx, LMX_ERR_NOT_BUILT, "bone attachments read the absolute pose (ASSERT(pose->is_absolute), render_module.cpp:424): run lmx_skin_run with pose write-back first");
+	w.pending = true;
 	LMX_HIP(ctx, launch_bone_attach(ctx->stream, w.dev(), w.d_attach.p, w.n_attach, sk.d_inst.p, sk.d_pose_pos.p, sk.d_pose_rot.p));
 	return LMX_OK;
 }

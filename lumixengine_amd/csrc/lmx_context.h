@@ -19,6 +19,7 @@
 #include "lumix_mi355.h"
 #include "lmx_kernels.h"
 #include "lmx_cull_layout.h"
+#include "lmx_world_edit_host.h"
 
 namespace lmx {
 
@@ -286,8 +287,39 @@ struct CullState : CullSet {
 struct WorldState {
 	uint32_t n = 0;
 	bool built = false;
-	std::vector<int32_t> parent; // by entity, -1 for roots
+	WorldEditMirror mirror; // parent by entity (-1 for roots) and the liveness stamps (lmx_world_edit_host.h)
+	// the slot order as the last BUILD left it. lmx_world_edit derives the order on the device: it keeps the vectors' sizes at n and
+	// marks the contents stale; world_host_slots() (lmx_capi_world.hip) fetches slot_of_entity again for the few host-side readers.
 	std::vector<int32_t> slot_of_entity, entity_of_slot, parent_slot;
+	bool host_slots_stale = false;
+	// lmx_world_edit propagates what was staged with the mirror still in its before-the-batch state. A re-upload of the binding tables
+	// in there leaves the entries of the entities the batch kills void (edit_doomed: its destroy list, sorted) and says which
+	// (edit_skipped, indices into bound_entity): the edit voids the host's list from it.
+	bool edit_in_flight = false;
+	std::vector<int32_t> edit_doomed;
+	std::vector<uint32_t> edit_skipped;
+	bool edit_kills(int32_t e) const { // e (alive) or one of its ancestors is in the destroy list
+		for (int32_t a = e; a >= 0; a = mirror.parent[a])
+			if (std::binary_search(edit_doomed.begin(), edit_doomed.end(), a)) return true;
+		return false;
+	}
+	bool pending = false;   // something was staged since the last propagation (lmx_world_edit propagates first)
+	uint32_t n_live = 0, edits = 0;
+	// lmx_world_edit: the hierarchy by entity on the device, the second set of every per-slot array (flipped with the first by an edit), scratch
+	bool edit_dev_valid = false; // d_parent / d_alive state the mirror (uploaded by the first edit after a build)
+	DevBuf<int32_t> d_parent;
+	DevBuf<uint8_t> d_alive, d_edit_mark, d_edit_kill;
+	DevBuf<double> alt_pos[6];
+	DevBuf<float4> alt_rot[2];
+	DevBuf<float> alt_scl[6];
+	DevBuf<int32_t> alt_parent_slot, alt_slot_of_entity, alt_entity_of_slot;
+	DevBuf<uint32_t> alt_bound_dyn_of_slot;
+	DevBuf<float> alt_bound_radius_of_slot;
+	DevBuf<uint32_t> d_edit_key, d_edit_key_alt, d_edit_val, d_edit_val_alt, d_edit_first, d_edit_count, d_edit_root, d_edit_cnt, d_edit_off, d_edit_word, d_edit_level_start,
+		d_edit_sizes, d_edit_run_root, d_edit_dropped;
+	DevBuf<int32_t> d_edit_destroy, d_edit_create, d_edit_child, d_edit_new_parent;
+	DevBuf<LmxTransform> d_edit_tr;
+	DevBuf<uint8_t> d_edit_temp; // hipcub's temporary storage
 	std::vector<uint32_t> level_start; // size levels + 1
 	DevBuf<double> pos[6];             // lpx lpy lpz wpx wpy wpz
 	DevBuf<float4> rot[2];             // lrot wrot

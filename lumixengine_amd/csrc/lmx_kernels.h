@@ -203,6 +203,45 @@ struct BoneAttachDevice { uint32_t slot, parent_slot, skin_instance, bone; float
 hipError_t launch_bone_attach(hipStream_t s, const WorldDevice& w, const BoneAttachDevice* att, uint32_t n, const SkinInstance* inst,
 	const float* pose_pos, const float4* pose_rot);
 
+// ---- world edits (world_edit_kernels.hip): destroy / create / re-parent a batch, then the slot order again from `parent` ----
+struct WorldEditDevice {
+	int32_t* parent; // by entity, -1: root (dead entities are childless roots)
+	uint8_t* alive;  // by entity
+	uint8_t* mark;   // by entity, zero on entry: the destroy list's entities
+	uint8_t* kill;   // by entity, zero on entry: dies in this call
+};
+struct WorldEditOrder {
+	const uint32_t* sorted; // entities sorted by (parent + 1, entity): the roots, then every parent's children
+	const uint32_t* first;  // [n + 1] by parent + 1: where that group begins in `sorted`
+	const uint32_t* count;  // [n + 1] its size
+	int32_t* entity_of_slot;
+	int32_t* slot_of_entity;
+	int32_t* parent_slot;
+	uint32_t* root_of_slot;
+};
+constexpr uint32_t WORLD_EDIT_SMALL_LEVEL = 256; // a level of at most this many slots expands in one block (lmx_wave.h's block_scan)
+hipError_t launch_edit_kill(hipStream_t s, const WorldEditDevice& d, const int32_t* destroy, uint32_t n_destroy, uint32_t n_old);
+hipError_t launch_edit_link(hipStream_t s, const WorldEditDevice& d, const int32_t* create, uint32_t n_create, const int32_t* child, const int32_t* new_parent, uint32_t n_reparent);
+hipError_t launch_edit_keys(hipStream_t s, const WorldEditDevice& d, uint32_t n, uint32_t* key, uint32_t* value, uint32_t* n_live /* += live entities */);
+hipError_t launch_edit_child_ranges(hipStream_t s, const uint32_t* sorted_key, uint32_t n, uint32_t* first /* [n + 1] */, uint32_t* count /* [n + 1], zero on entry */);
+hipError_t launch_edit_roots(hipStream_t s, const WorldEditOrder& o, uint32_t n_roots);
+// level [level_first, level_first + m) -> its children behind it; the small form writes the next level's size to *total
+hipError_t launch_edit_level_small(hipStream_t s, const WorldEditOrder& o, uint32_t level_first, uint32_t m, uint32_t* total);
+hipError_t launch_edit_level_count(hipStream_t s, const WorldEditOrder& o, uint32_t level_first, uint32_t m, uint32_t* cnt /* [m + 1], the last one 0 */);
+hipError_t launch_edit_level_scatter(hipStream_t s, const WorldEditOrder& o, uint32_t level_first, uint32_t m, const uint32_t* cnt, const uint32_t* off);
+hipError_t launch_edit_permute(hipStream_t s, const WorldDevice& from, const WorldDevice& to, const int32_t* entity_of_slot, const int32_t* old_slot_of_entity, const uint8_t* kill /* by entity: died in this call */,
+	uint32_t n_old, uint32_t n, const uint32_t* dyn_from, const float* radius_from, uint32_t* dyn_to /* nullptr: no per-slot culling tables */, float* radius_to);
+hipError_t launch_edit_create(hipStream_t s, const WorldDevice& w, const int32_t* slot_of_entity, const int32_t* create, const void* transforms, uint32_t n);
+hipError_t launch_edit_locals(hipStream_t s, const WorldDevice& w, const int32_t* slot_of_entity, const int32_t* child, const int32_t* new_parent, uint32_t n);
+hipError_t launch_edit_remap(hipStream_t s, const int32_t* old_entity_of_slot, const int32_t* slot_of_entity, const uint8_t* kill, uint32_t* bound_slot, uint32_t n_bound,
+	BoneAttachDevice* attach, uint32_t n_attach);
+// dropped[0 .. *count) = the entries of the binding list whose entity dies in this call (any order); *count zero on entry
+hipError_t launch_edit_dropped(hipStream_t s, const int32_t* old_entity_of_slot, const uint8_t* kill, const uint32_t* bound_slot, uint32_t n_bound, uint32_t* dropped,
+	uint32_t* count);
+hipError_t launch_edit_root_sizes(hipStream_t s, const uint32_t* root_of_slot, const uint32_t* level_start, uint32_t n_levels, uint32_t n_roots, uint32_t* size);
+hipError_t launch_edit_run_table(hipStream_t s, const uint32_t* root_of_slot, const uint32_t* level_start, uint32_t n_levels, const uint32_t* run_root, uint32_t n_rows,
+	uint32_t* table);
+
 // ---- animation sampling (anim_kernels.hip) ----
 struct AnimDevice { // one Animation resource: offsets into the concatenated tables of AnimTables
 	float fps;

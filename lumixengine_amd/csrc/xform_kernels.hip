@@ -341,6 +341,7 @@ __global__ __launch_bounds__(256) void k_sphere_refresh(WorldDevice w, const uin
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= n) return;
 	const uint32_t s = bound_slot[i];
+	if (s == 0xffffffffu) return; // the bound entity was destroyed (lmx_world_edit)
 	const uint32_t d = bound_dyn[i];
 	dyn_px[d] = w.wpx[s];
 	dyn_py[d] = w.wpy[s];
@@ -387,6 +388,7 @@ __global__ __launch_bounds__(256) void k_bone_attach(WorldDevice w, const BoneAt
 	if (i >= n) return;
 	const BoneAttachDevice a = att[i];
 	const uint32_t ps = a.parent_slot, s = a.slot;
+	if (s == 0xffffffffu) return; // the attached entity or its parent was destroyed (lmx_world_edit)
 	Xform parent;
 	parent.pos = DV3{w.wpx[ps], w.wpy[ps], w.wpz[ps]};
 	const float4 pr = w.wrot[ps];

@@ -36,6 +36,7 @@
 #include "gpu_culling_system.h"
 #include "pose_bridge.h"
 #include "world_sync.h"
+#include "world_edit_queue.h"
 
 namespace Lumix {
 
@@ -66,13 +67,14 @@ struct Mi355Module final : IModule {
 			logError("mi355: ", lmx_last_error(nullptr)); // the module then idles
 			m_ctx = nullptr;
 		}
-		// structural changes invalidate the mirror (entity slots, hierarchy); setParent has no delegate: callers use markDirty()
-		m_world.entityCreated().bind<&Mi355Module::onEntityChanged>(this);
-		m_world.entityDestroyed().bind<&Mi355Module::onEntityChanged>(this);
+		// structural changes are queued and reach the mirror as one batch per update() (WorldSync::edit); World::setParent has no
+		// delegate: callers re-parent through setParent() below, or call markDirty() after the World's own
+		m_world.entityCreated().bind<&Mi355Module::onEntityCreated>(this);
+		m_world.entityDestroyed().bind<&Mi355Module::onEntityDestroyed>(this);
 	}
 	~Mi355Module() override {
-		m_world.entityCreated().unbind<&Mi355Module::onEntityChanged>(this);
-		m_world.entityDestroyed().unbind<&Mi355Module::onEntityChanged>(this);
+		m_world.entityCreated().unbind<&Mi355Module::onEntityCreated>(this);
+		m_world.entityDestroyed().unbind<&Mi355Module::onEntityDestroyed>(this);
 		unbindTransformed();
 		m_sync.reset();
 		m_poses.reset();
@@ -96,7 +98,13 @@ struct Mi355Module final : IModule {
 	// staged writes: game code (or a script binding) calls these instead of World::setTransform / setLocalTransform
 	void setTransform(EntityRef e, const Transform& t) { if (m_sync) m_sync->setTransform(e, t); }
 	void setLocalTransform(EntityRef e, const Transform& t) { if (m_sync) m_sync->setLocalTransform(e, t); }
-	// after World::setParent (the World has no delegate for it), or whenever the mirror must be re-read
+	// World::setParent through the module: the World re-parents (and refuses a cycle, world.cpp:621-626) as always, the mirror follows
+	// with the frame's batch instead of a rebuild
+	void setParent(EntityPtr new_parent, EntityRef child) {
+		m_world.setParent(new_parent, child);
+		if (queueing()) m_queue.reparented(child);
+	}
+	// after a World::setParent that did not go through setParent() above, or whenever the mirror must be re-read
 	void markDirty() { m_dirty = true; }
 	LmxContext* context() { return m_ctx; }
 	// RenderModuleImpl::onModelInstanceMoved on the device for these entities (culling sphere = world position, model_radius *
@@ -116,6 +124,8 @@ struct Mi355Module final : IModule {
 	void update(float) override {
 		if (!m_ctx) return;
 		if (m_dirty) rebuild();
+		else if (!m_queue.empty()) applyEvents();
+		m_queue.clear();
 		if (!m_sync) return;
 		// 1. every transformEntity DFS of the frame + onModelInstanceMoved for bound entities, on the device
 		if (!m_sync->propagate()) fail("propagate", m_sync->lastError());
@@ -145,7 +155,24 @@ struct Mi355Module final : IModule {
 	}
 
 private:
-	void onEntityChanged(EntityRef) { m_dirty = true; }
+	// What the World did to its entity set since the last update() (world_edit_queue.h). A full rebuild that is due anyway takes it all.
+	bool queueing() {
+		if (!m_dirty && m_sync) return true;
+		m_dirty = true;
+		return false;
+	}
+	void onEntityCreated(EntityRef e) { if (queueing()) m_queue.created(e); }
+	void onEntityDestroyed(EntityRef e) { if (queueing()) m_queue.destroyed(e); }
+
+	// The frame's batch through WorldSync::edit; a batch the mirror refuses falls back to the full rebuild. The RenderModule bindings are
+	// then derived again as rebuild() derives them (components come and go with their entities), without re-mirroring the World.
+	void applyEvents() {
+		if (!m_queue.apply(*m_sync, m_world)) {
+			rebuild(); // (says why if that fails as well)
+			return;
+		}
+		bindRenderModule();
+	}
 
 	// A World::setTransform* by other engine code (editor gizmo, physics, scripts): the World has already run its own DFS and fired the
 	// delegates. The device mirror takes the WRITTEN entity's new world transform as a staged world-space write; the descendants the
@@ -217,6 +244,13 @@ private:
 			return;
 		}
 		bindTransformed();
+		bindRenderModule();
+	}
+
+	// The RenderModule's side of the mirror: culling bindings of the valid model instances, skeletons / meshes / skinned instances, bone
+	// attachments. After a rebuild, and after a batch of structural edits (components come and go with their entities).
+	void bindRenderModule() {
+		m_bound_ok = false;
 		if (!m_render_module) {
 			m_bound_ok = true; // nothing to bind
 			return;
@@ -322,6 +356,7 @@ private:
 	std::vector<int32_t> m_moved_entities;
 	std::vector<Transform> m_moved_transforms;
 	std::vector<ComponentType> m_transformed_types;
+	WorldEditQueue m_queue;
 	std::vector<u32> m_engine_write_stamp; // per entity: the frame in which the World announced a direct write to it
 	u32 m_frame_stamp = 1;
 	struct EntityList {

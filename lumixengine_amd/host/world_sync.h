@@ -97,22 +97,57 @@ struct WorldSync {
 	// entities). The reference applies writes one by one, in call order: for two writes to ONE entity in a frame the last one wins
 	// (push() keeps only it, whichever of the two entry points each used).
 	bool propagate() {
-		m_set_entities.clear();
-		m_set_values.clear();
-		m_set_world_entities.clear();
-		m_set_world_values.clear();
-		for (const Staged& st : m_staged) {
-			(st.world_space ? m_set_world_entities : m_set_entities).push_back(st.entity);
-			(st.world_space ? m_set_world_values : m_set_values).push_back(st.value);
-			m_staged_at[st.entity] = -1;
-		}
-		m_staged.clear();
 		Lock guard(m_ctx);
-		bool ok = true;
-		if (!m_set_entities.empty()) ok = check(lmx_world_set_transforms(m_ctx, (u32)m_set_entities.size(), m_set_entities.data(), m_set_values.data())) && ok;
-		if (!m_set_world_entities.empty())
-			ok = check(lmx_world_set_world_transforms(m_ctx, (u32)m_set_world_entities.size(), m_set_world_entities.data(), m_set_world_values.data())) && ok;
+		const bool ok = flush();
 		return check(lmx_world_propagate(m_ctx)) && ok;
+	}
+
+	// World::destroyEntity / World::createEntity / World::setParent of a frame as ONE batch (lmx_world_edit), applied as that sequence of
+	// World calls: every destroy (each takes its subtree along, as destroyEntity does), then every create - a root with the given world
+	// transform; an index destroyed in the same call may come back - then the re-parentings in list order (an invalid new parent
+	// detaches). The mirror is NOT rebuilt: the device derives the slot order again, and culling bindings and bone attachments of the
+	// surviving entities stay. Writes staged so far reach the device first and are propagated by the edit, as the reference applies
+	// every write before the next call; readMoved() still returns what that propagation moved. A refused batch (a dead entity, a
+	// duplicate create, a cycle; lastError() says which entry) leaves the mirror as it was.
+	bool edit(const EntityRef* destroyed, u32 n_destroyed, const EntityRef* created, const Transform* created_transforms, u32 n_created, const EntityPtr* new_parents,
+		const EntityRef* children, u32 n_reparented) {
+		m_tmp_entities.resize((size_t)n_destroyed + n_created + 2 * (size_t)n_reparented);
+		int32_t* d = m_tmp_entities.data();
+		int32_t* c = d + n_destroyed;
+		int32_t* p = c + n_created;
+		int32_t* k = p + n_reparented;
+		for (u32 i = 0; i < n_destroyed; ++i) d[i] = destroyed[i].index;
+		for (u32 i = 0; i < n_created; ++i) c[i] = created[i].index;
+		for (u32 i = 0; i < n_reparented; ++i) {
+			p[i] = new_parents[i].isValid() ? new_parents[i].index : -1;
+			k[i] = children[i].index;
+		}
+		// A write staged to an index that the batch creates is meant for the entity that lives there now (the World's free list hands a
+		// destroyed index straight back: createEntity, then setScale / setTransform on it in the same frame). The mirror still holds that
+		// index as dead and would refuse the write, so it waits until the entity exists: it stays staged for the next propagate(),
+		// also when the batch is refused (the caller then rebuilds, and build() keeps it).
+		std::vector<Staged> held;
+		if (n_created && !m_staged.empty()) {
+			std::vector<Staged> now;
+			for (u32 i = 0; i < n_created; ++i)
+				if (c[i] >= 0 && (u32)c[i] < m_n && m_staged_at[c[i]] >= 0) m_staged_at[c[i]] = -2;
+			for (const Staged& st : m_staged) (m_staged_at[st.entity] == -2 ? held : now).push_back(st);
+			for (const Staged& st : held) m_staged_at[st.entity] = -1;
+			m_staged.swap(now); // (flush() takes them all and clears their marks)
+		}
+		Lock guard(m_ctx);
+		bool ok = flush();
+		ok = check(lmx_world_edit(m_ctx, n_destroyed, d, n_created, c, reinterpret_cast<const LmxTransform*>(created_transforms), n_reparented, p, k)) && ok;
+		LmxWorldInfo info;
+		if (check(lmx_world_info(m_ctx, &info)) && info.n != m_n) { // the index range grew
+			m_n = info.n;
+			m_staged_at.resize(m_n, -1);
+		}
+		for (const Staged& st : held) {
+			m_staged_at[st.entity] = (int32_t)m_staged.size();
+			m_staged.push_back(st);
+		}
+		return ok;
 	}
 
 	// The frame's hand-back: the entities World::transformEntity would have visited since the last call (every propagate() in
@@ -181,6 +216,30 @@ private:
 			m_staged[at].world_space = world_space;
 			m_staged[at].value = v;
 		}
+	}
+	// the staged writes to the device, under the caller's lock; nothing is propagated here
+	bool flush() {
+		m_set_entities.clear();
+		m_set_values.clear();
+		m_set_world_entities.clear();
+		m_set_world_values.clear();
+		for (const Staged& st : m_staged) {
+			(st.world_space ? m_set_world_entities : m_set_entities).push_back(st.entity);
+			(st.world_space ? m_set_world_values : m_set_values).push_back(st.value);
+			m_staged_at[st.entity] = -1;
+		}
+		m_staged.clear();
+		const bool ok = stage(lmx_world_set_transforms, m_set_entities, m_set_values);
+		return stage(lmx_world_set_world_transforms, m_set_world_entities, m_set_world_values) && ok;
+	}
+	// The C ABI refuses a batch of writes as a whole, before it stages any of it (one entity out of range, or dead in the mirror). The
+	// frame's other writes are in nobody else's hands: they still go, one by one, and the call reports the refusal.
+	bool stage(int (*set)(LmxContext*, uint32_t, const int32_t*, const LmxTransform*), const std::vector<int32_t>& entities, const std::vector<LmxTransform>& values) {
+		if (entities.empty() || check(set(m_ctx, (u32)entities.size(), entities.data(), values.data()))) return true;
+		const std::string why = m_error;
+		for (size_t i = 0; i < entities.size(); ++i) set(m_ctx, 1, &entities[i], &values[i]);
+		m_error = why;
+		return false;
 	}
 	bool check(int rc) {
 		if (rc == LMX_OK) return true;
