@@ -1,13 +1,16 @@
 """numpy restatement of PipelineImpl::fillClusters (renderer/pipeline.cpp:3327-3684) in np.float32 + the seeded scene the cluster tests share.
 
-Written from the reference's description of the algorithm, line by line cited, with none of its text: the cluster planes (:3464-3495, powf
-taken from libm through ctypes - numpy's power is another function), the light records (:3387-3410), the probe records and their sort
-(:3500-3538; deviations of DESIGN.md 4.11: enabled probes only, ties in module order), range() (:3540-3561) with its early returns, the
-three count passes (:3628-3638), the prefix (:3640-3645) and the three fill passes (:3649-3662). Every product and sum is rounded to
+A transcription with none of the reference's text: the cluster planes (:3464-3495, powf taken from libm through ctypes - numpy's power is
+another function), the light records (:3387-3410), the probe records and their sort (:3500-3538; deviations of DESIGN.md 4.11: enabled
+probes only, ties in module order), range() (:3540-3561) with its early returns, the three count passes (:3628-3638), the prefix
+(:3640-3645) and the three fill passes (:3649-3662). It is held to the reference's own code by tests/test_cluster_oracle_vs_ref.py, which
+compiles those statements out of the reference tree and compares planes, range(), records, `clusters` and `map` bit for bit, and by the
+recorded fixture tests/golden/clusters_small.npz where the tree is absent. Every product and sum is rounded to
 float32 on its own (numpy never fuses), in the reference's operation order."""
 import ctypes
 import ctypes.util
 import functools
+import os
 
 import numpy as np
 
@@ -167,14 +170,26 @@ def axis_range(dist, r, size: int):
         return (-1, -1)
 
 
+def axis_ranges(dist, r, size: int):
+    """axis_range for every row of dist[n, size + 1] at once -> [n, 2]. The same comparisons, so a NaN fails each of them: the first plane
+    i + 1 with `dist > r` false gives lo = i, the first plane behind it with `dist < -r` true gives hi, else hi = size."""
+    dist, r = np.asarray(dist, f32)[:, : size + 1], np.asarray(r, f32).reshape(-1, 1)
+    with np.errstate(all="ignore"):
+        reached = ~(dist[:, 1:] > r)
+        behind = dist < -r
+    lo = np.argmax(reached, axis=1)
+    ends = behind & (np.arange(size + 1)[None, :] > lo[:, None])
+    hi = np.where(ends.any(axis=1), np.argmax(ends, axis=1), size)
+    none = behind[:, 0] | ~reached.any(axis=1)
+    return np.where(none[:, None], -1, np.stack([lo, hi], axis=1)).astype(np.int32)
+
+
 def ranges(size, xp, yp, zp, pos, radius):
     """[n, 3, 2]: (xrange, yrange, zrange) of every sphere (:3570-3572)."""
     pos = np.asarray(pos, f32).reshape(-1, 3)
     out = np.zeros((len(pos), 3, 2), np.int32)
     for axis, pl in enumerate((xp, yp, zp)):
-        d = plane_dists(pl[: size[axis] + 1], pos)
-        for i in range(len(pos)):
-            out[i, axis] = axis_range(d[i], radius[i], size[axis])
+        out[:, axis] = axis_ranges(plane_dists(pl[: size[axis] + 1], pos), radius, size[axis])
     return out
 
 
@@ -189,9 +204,13 @@ def fill(size, light_ranges, env_ranges, refl_ranges):
     """-> (clusters, map): three count passes, the exclusive prefix over clusters in index order, three fill passes in sequence."""
     n = size[0] * size[1] * size[2]
     clusters = np.zeros(n, api.CLUSTER)
-    groups = (("lights_count", light_ranges), ("env_probes_count", env_ranges), ("refl_probes_count", refl_ranges))
+    groups = []
+    for field, rgs in (("lights_count", light_ranges), ("env_probes_count", env_ranges), ("refl_probes_count", refl_ranges)):
+        rgs = np.asarray(rgs, np.int64).reshape(-1, 3, 2)
+        some = np.flatnonzero((rgs[:, :, 1] > rgs[:, :, 0]).all(axis=1))  # (an empty range on one axis: the triple loop visits nothing)
+        groups.append((field, [(int(i), rgs[i]) for i in some]))
     for field, rgs in groups:
-        for rg in rgs:
+        for _, rg in rgs:
             clusters[field][_cluster_ids(size, rg)] += 1
     total = clusters["lights_count"].astype(np.int64) + clusters["env_probes_count"] + clusters["refl_probes_count"]
     offset = np.concatenate([[0], np.cumsum(total)])
@@ -199,7 +218,7 @@ def fill(size, light_ranges, env_ranges, refl_ranges):
     cmap = np.zeros(int(offset[-1]), np.int32)
     cursor = offset[:-1].copy()
     for _, rgs in groups:
-        for i, rg in enumerate(rgs):
+        for i, rg in rgs:
             ids = _cluster_ids(size, rg)
             cmap[cursor[ids]] = i
             cursor[ids] += 1
@@ -278,3 +297,138 @@ def scene(seed=5, n_entities=N_ENTITIES):
     for a in (tr, lights, atlas, env, refl, env_entities, refl_entities):
         a.setflags(write=False)
     return {"transforms": tr, "lights": lights, "atlas": atlas, "env": env, "env_entities": env_entities, "refl": refl, "refl_entities": refl_entities}
+
+
+# ---- cases the device tests and the pin share -------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def hand_made():
+    """-> (view, names, transforms, light table, radius by name): sixteen lights by name; the last entity lies past every table. Shared by
+    tests/test_gpu_clusters.py and tests/test_cluster_oracle_vs_ref.py, which runs the same spheres through the reference's range()."""
+    v = view(128, 64)
+    size, xp, yp, zp = planes(v["frustum"][0], 128, 64)
+    assert size == (2, 1, 16)
+    names = ["inside", "straddles_x", "left", "right", "above", "below", "before_near", "beyond_far", "dist_eq_r", "dist_gt_r", "dist_eq_minus_r", "dist_lt_minus_r",
+             "nan", "radius_0", "everything", "past_tables"]
+    rel = {"inside": (0.3, 0.0, -1.0), "straddles_x": (0.0, 0.0, -1.0), "left": (-10.0, 0.0, -1.0), "right": (10.0, 0.0, -1.0), "above": (0.0, 10.0, -1.0),
+           "below": (0.0, -10.0, -1.0), "before_near": (0.0, 0.0, -0.01), "beyond_far": (0.0, 0.0, -20000.0), "nan": (np.nan, 0.0, -1.0), "radius_0": (-0.3, 0.0, -1.0),
+           "everything": (0.0, 0.0, -50.0)}
+    radius = {"inside": 0.01, "straddles_x": 0.05, "left": 0.1, "right": 0.1, "above": 0.1, "below": 0.1, "before_near": 0.01, "beyond_far": 1.0, "nan": 1.0, "radius_0": 0.0,
+              "everything": 1.0e5}
+    # a sphere whose distance to z plane 3 EQUALS its radius (`dist > r` is false: the plane's near cluster is in) and one a bit smaller;
+    # one whose distance to z plane 4 equals MINUS its radius (`dist < -r` is false: the range goes on) and one a bit smaller
+    on_axis = np.array([[0.0, 0.0, -1.0]], np.float32)
+    dz = plane_dists(zp, on_axis)[0]
+    assert dz[3] > 0 > dz[4]
+    for k in ("dist_eq_r", "dist_gt_r", "dist_eq_minus_r", "dist_lt_minus_r"):
+        rel[k] = (0.0, 0.0, -1.0)
+    radius["dist_eq_r"], radius["dist_gt_r"] = dz[3], np.nextafter(dz[3], np.float32(0))
+    radius["dist_eq_minus_r"], radius["dist_lt_minus_r"] = -dz[4], np.nextafter(-dz[4], np.float32(0))
+    n = len(names)
+    tr = np.zeros(n - 1, api.TRANSFORM)  # the last entity lies past every table
+    lights = np.zeros(n - 1, api.POINT_LIGHT)
+    for i, k in enumerate(names[:-1]):
+        tr["pos"][i] = np.asarray(CAM_POS) + np.array(rel[k], np.float64)
+        lights["range"][i] = radius[k]
+    tr["rot"], tr["scale"] = (0, 0, 0, 1), 1
+    lights["color"], lights["intensity"] = (1, 0.5, 0.25), 3
+    tr.setflags(write=False)
+    lights.setflags(write=False)
+    return v, names, tr, lights, radius
+
+
+N_SEEDED = 3000
+
+
+def edge_indices(n):
+    """List indices on the edges of the kernels' decomposition: waves (64), the gather's light tile and the record step's blocks
+    (CLUSTER_BLOCK), the list's ends."""
+    edges = {0, n - 1}
+    for step in (64, api.CLUSTER_BLOCK):
+        for k in range(step, n, step):
+            edges |= {k - 1, k}
+    edges |= {api.CLUSTER_BLOCK + 1, (n // api.CLUSTER_BLOCK) * api.CLUSTER_BLOCK - 2}
+    return sorted(e for e in edges if 0 <= e < n)
+
+
+@functools.lru_cache(maxsize=None)
+def seeded_case():
+    """-> (view, listed, probes, want): N_SEEDED lights of scene() on 1920 x 1080 with scene-wide and tiny lights alternating on edge_indices,
+    the scene's own probes, and the oracle's result for them. Never modified by a test."""
+    sc = scene()
+    rng = np.random.default_rng(77)
+    listed = rng.permutation(N_ENTITIES).astype(np.int32)
+    # scene-wide lights (they land in every cluster: a lost or doubled entry shows in all of them) and tiny ones on the edges, alternating
+    wide = [e for e in np.flatnonzero(sc["lights"]["range"] == np.float32(2.0e4))]
+    tiny = [e for e in np.flatnonzero((sc["lights"]["range"] < 0.5) & (sc["lights"]["range"] > 0))]
+    edges = edge_indices(N_SEEDED)
+    assert len(wide) >= 8 and len(tiny) >= len(edges)
+    placed = set(wide) | set(tiny[: len(edges)])
+    listed = np.array([e for e in listed if e not in placed], np.int32)[:N_SEEDED]
+    assert len(listed) == N_SEEDED
+    for k, at in enumerate(edges):
+        listed[at] = wide[(k // 2) % len(wide)] if k % 2 == 0 else tiny[k]
+    v = view(1920, 1080)
+    probes = {k: sc[k] for k in ("env", "env_entities", "refl", "refl_entities")}
+    want = fill_clusters(v, listed, sc["transforms"], sc["lights"], sc["atlas"], **probes)
+    return v, listed, probes, want
+
+
+def _probe_extents(rng, n, wide):
+    """[n, 3] in OUTPUT order: strictly ascending, pairwise distinct fp32 volume products of boxes of side 100 .. 400 (radius >= 173);
+    the ones at the output indices `wide` are needles of the same volume and a radius of 3e4 - in every cluster of any view here."""
+    side = (100.0 + 300.0 * np.arange(n) / max(n, 1)).astype(np.float64)
+    ext = np.stack([side * 1.25, side, side / 1.25], axis=1)
+    for k in wide:
+        if 0 <= k < n:
+            ext[k] = (3.0e4, np.sqrt(side[k] ** 3 / 3.0e4), np.sqrt(side[k] ** 3 / 3.0e4))
+    ext = ext.astype(f32)
+    assert (np.diff(ext[:, 0] * ext[:, 1] * ext[:, 2]) > 0).all()
+    return ext
+
+
+def probe_tables(n_env, n_refl, seed=9, scene_seed=5, n_entities=N_ENTITIES, disabled=0, wide=(), far=0.1):
+    """Probe tables for scene(scene_seed, n_entities) with n_env / n_refl ENABLED probes of pairwise distinct volume products, in a
+    shuffled module order, and `disabled` disabled ones of each kind mixed in (with volumes that would sort them between the others).
+    All but the fraction `far` sit on entities within (+-60, +-60, -50 .. -200) of CAM_POS, so that every one of them holds the point (0, 0, -100) and
+    some cluster holds them all; the others sit beyond z = -1000. `wide`: output indices (ascending volume) of scene-wide probes."""
+    rng = np.random.default_rng(seed)
+    rel = scene(scene_seed, n_entities)["transforms"]["pos"] - np.asarray(CAM_POS)
+    near = np.flatnonzero((np.abs(rel[:, 0]) < 60) & (np.abs(rel[:, 1]) < 60) & (rel[:, 2] < -50) & (rel[:, 2] > -200))
+    away = np.flatnonzero(rel[:, 2] < -1000)
+    assert len(near) and len(away)
+    out = {}
+    for kind, n, dtype, field in (("env", n_env, api.ENV_PROBE, "outer_range"), ("refl", n_refl, api.REFL_PROBE, "half_extents")):
+        total = n + disabled
+        t = np.zeros(total, dtype)
+        order = rng.permutation(total)  # module index of output position k (the disabled ones take the last positions of `order`)
+        t[field][order[:n]] = _probe_extents(rng, n, wide)
+        t["flags"][order[:n]] = api.PROBE_ENABLED | (1 if kind == "env" else 0)
+        t[field][order[n:]] = rng.uniform(100, 400, (disabled, 3))
+        t["flags"][order[n:]] = 1 if kind == "env" else 0
+        if kind == "env":
+            t["inner_range"] = t["outer_range"] * f32(0.5)
+            t["sh_coefs"] = rng.normal(size=(total, 9, 3))
+        else:
+            t["texture_id"] = rng.integers(0, 64, total)
+        out[kind] = t
+        out[kind + "_entities"] = np.where(rng.random(total) >= far, rng.choice(near, total), rng.choice(away, total)).astype(np.int32)
+    return out
+
+
+GOLDEN_SMALL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clusters_small.npz")
+
+
+@functools.lru_cache(maxsize=None)
+def golden_small():
+    """tests/golden/clusters_small.npz (tests/golden/make_golden_clusters.py: the REFERENCE's output, recorded) ->
+    (scene tables, listed entities, probe tables, [(view, planes and fill_clusters-shaped dict of the reference's results), ...])"""
+    z = np.load(GOLDEN_SMALL)
+    assert str(z["kind"]) == "reference"
+    sc = scene(int(z["seed"]))
+    probes = {k: z["probes_" + k] for k in ("env", "env_entities", "refl", "refl_entities")}
+    views = []
+    for i, v in enumerate(z["views"]):
+        want = {k: z[f"v{i}_{k}"] for k in ("xplanes", "yplanes", "zplanes", "lights", "env_probes", "refl_probes", "clusters", "map")}
+        want["size"] = tuple(int(x) for x in z[f"v{i}_size"])
+        views.append((v.reshape(1), want))
+    return sc, z["listed"], probes, views

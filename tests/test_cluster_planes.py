@@ -1,6 +1,8 @@
-"""lmx_clusters_planes (lumixengine_amd/csrc/lmx_cluster_planes.cpp) against tests/cluster_oracle.py, bit for bit (no GPU needed). The two are
-independent transcriptions of renderer/pipeline.cpp:3464-3495 - the reference's own fillClusters cannot be built outside the engine - and
-both take powf from libm: one differing last bit in a z plane would move lights across cluster borders."""
+"""lmx_clusters_planes (lumixengine_amd/csrc/lmx_cluster_planes.cpp) against tests/cluster_oracle.py, bit for bit (no GPU needed). Both are
+transcriptions of renderer/pipeline.cpp:3464-3495 by one reading of core/math.cpp and core/geometry.cpp; what holds that reading to the
+reference is tests/test_cluster_oracle_vs_ref.py, which compiles the reference's own plane block and compares both with it, and - where
+the reference tree is absent - the recorded fixture tests/golden/clusters_small.npz below. Both take powf from libm: one differing last
+bit in a z plane would move lights across cluster borders."""
 import os
 
 import numpy as np
@@ -53,3 +55,24 @@ def test_more_than_64_clusters_on_an_axis_is_a_capacity_error(api, w, h):
     with pytest.raises(api.LumixError) as e:
         api.clusters_planes(api.viewport_frustum(pos=CAM), w, h)
     assert e.value.code == 5  # LMX_ERR_CAPACITY
+
+
+# ---- the recorded reference (tests/golden/make_golden_clusters.py) ----------------------------------------------------------------
+def test_oracle_and_planes_reproduce_the_recorded_reference(api):
+    """tests/golden/clusters_small.npz holds what the reference's own fillClusters statements gave for two small views: the oracle's
+    whole pass and the library's planes equal it byte for byte. Reads nothing of the reference tree."""
+    sc, listed, probes, views = CO.golden_small()
+    assert [want["size"] for _, want in views] == [(2, 1, 16), (4, 3, 16)] and len(listed) > 200 and len(probes["env"]) == len(probes["refl"]) == 12
+    for view, want in views:
+        w, h = int(view["viewport_w"][0]), int(view["viewport_h"][0])
+        got = CO.fill_clusters(view, listed, sc["transforms"], sc["lights"], None, **probes)
+        assert got["size"] == want["size"]
+        for k in ("lights", "env_probes", "refl_probes", "clusters", "map"):
+            assert len(want[k]) and got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes(), (w, h, k)
+        cl = want["clusters"]
+        assert cl["lights_count"].max() > 1 and cl["env_probes_count"].min() >= 1 and cl["refl_probes_count"].max() > 1 and len(want["map"]) > 500
+        size, xp, yp, zp = CO.planes(view["frustum"][0], w, h)
+        lib = api.clusters_planes(view["frustum"][0], w, h)[0]
+        for name, oracle in (("xplanes", xp), ("yplanes", yp), ("zplanes", zp)):
+            assert oracle.view(np.uint32).tolist() == want[name].view(np.uint32).tolist(), (w, h, name)
+            assert lib[name][: len(oracle)].view(np.uint32).tolist() == want[name].view(np.uint32).tolist(), (w, h, name)
