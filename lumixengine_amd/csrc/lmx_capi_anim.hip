@@ -318,9 +318,7 @@ int lmx_anim_read_times(LmxContext* ctx, uint32_t* time, uint32_t n_instances) {
 	LMX_CHECK_CTX(ctx);
 	AnimState& an = ctx->anim;
 	if (n_instances != an.n_animables || (n_instances && !time)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "expected %u animables", an.n_animables);
-	LMX_HIP(ctx, read_back(time, an.d_time_of.p, n_instances, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, time, (const uint32_t*)an.d_time_of.p, n_instances);
 }
 
 int lmx_anim_read_pose(LmxContext* ctx, uint32_t instance, float* out_pos, float* out_rot, uint32_t cap_bones) {
@@ -331,9 +329,7 @@ int lmx_anim_read_pose(LmxContext* ctx, uint32_t instance, float* out_pos, float
 	if (cap_bones < in.n_bones) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bones", in.n_bones);
 	if (sk.pose_is_absolute || !sk.poses_uploaded || sk.borrowed_pos) return fail(ctx, LMX_ERR_NOT_BUILT, "the pose buffers do not hold a relative pose (call after lmx_anim_update, before lmx_skin_run)");
 	LMX_HIP(ctx, read_back(out_pos, sk.d_pose_pos.p + (size_t)in.bone_offset * 3, (size_t)in.n_bones * 3, ctx->stream));
-	LMX_HIP(ctx, read_back((float4*)out_rot, sk.d_pose_rot.p + in.bone_offset, in.n_bones, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, (float4*)out_rot, (const float4*)sk.d_pose_rot.p + in.bone_offset, in.n_bones);
 }
 
 } // extern "C"

@@ -368,9 +368,7 @@ int lmx_animators_read_root_motion(LmxContext* ctx, LmxLocalRigidTransform* out,
 	AnimatorsState& as = ctx->animators;
 	if (!as.is_set) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_animators_set has not been called");
 	if (n_animators != as.n || (n_animators && !out)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "expected %u Animators", as.n);
-	LMX_HIP(ctx, read_back((float*)out, as.d_root_motion.p, 7 * (size_t)n_animators, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, (float*)out, (const float*)as.d_root_motion.p, 7 * (size_t)n_animators);
 }
 
 int lmx_animators_device_outputs(LmxContext* ctx, void** d_root_motion, void** d_first_instr, void** d_instrs) {
@@ -411,8 +409,7 @@ int lmx_animators_read_state(LmxContext* ctx, uint32_t animator, void* out, uint
 	*out_bytes = 0;
 	if (a.controller == LMX_CONTROLLER_NONE) return LMX_OK;
 	uint32_t len = 0;
-	LMX_HIP(ctx, read_back(&len, as.d_state_len.p + animator, 1, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = read_now(ctx, &len, (const uint32_t*)as.d_state_len.p + animator, 1)) return rc;
 	*out_bytes = 4 * len;
 	if (!out) return LMX_OK;
 	if (capacity_bytes < 4 * len) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bytes", 4 * len);
@@ -427,15 +424,11 @@ int lmx_animators_read_instrs(LmxContext* ctx, uint32_t* out_first_instr, uint32
 	AnimatorsState& as = ctx->animators;
 	if (!as.is_set) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_animators_set has not been called");
 	if (n_animators != as.n || !out_first_instr || !out_count) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "expected %u Animators and non-null outputs", as.n);
-	LMX_HIP(ctx, read_back(out_first_instr, ctx->anim.d_first_sample.p, (size_t)as.n + 1, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = read_now(ctx, out_first_instr, (const uint32_t*)ctx->anim.d_first_sample.p, (size_t)as.n + 1)) return rc;
 	const uint32_t total = out_first_instr[as.n];
 	*out_count = total;
 	if (!out_instrs) return LMX_OK;
-	if (capacity < total) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u instructions", total);
-	LMX_HIP(ctx, read_back(out_instrs, ctx->anim.d_instrs.p, total, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, out_instrs, capacity, (const LmxBlendInstr*)ctx->anim.d_instrs.p, total, total, "instructions");
 }
 
 } // extern "C"

@@ -44,27 +44,18 @@ int clusters_ready(LmxContext* ctx) {
 // The pass over `list_cap` entries at most of `d_list`, its length on the device.
 int clusters_pass(LmxContext* ctx, const LmxClusterView* cv, const int32_t* d_list, const uint32_t* d_count, size_t list_cap) {
 	ClustersState& cl = ctx->clusters;
-	DrawState& ds = ctx->draw;
 	LmxClusterPlanes planes;
 	if (lmx_clusters_planes(&cv->frustum, cv->viewport_w, cv->viewport_h, &planes) != LMX_OK)
 		return fail(ctx, LMX_ERR_CAPACITY, "viewport %u x %u: more than %d x %d clusters", cv->viewport_w, cv->viewport_h, LMX_CLUSTER_MAX_XY, LMX_CLUSTER_MAX_XY);
-	if (ds.use_world && !ctx->world.n) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
+	ClustersDevice d;
+	memset(&d, 0, sizeof(d));
+	if (int rc = bind_entity_transforms(ctx, d)) return rc;
 	list_cap = std::min<size_t>(list_cap, 1u << 30);
 	if (cl.d_ranges.cap < std::max<size_t>(list_cap, 1)) {
 		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a pass of the previous view may still read the old ranges)
 		LMX_HIP(ctx, cl.d_ranges.reserve(std::max<size_t>(list_cap, 1)));
 	}
-	ClustersDevice d;
-	memset(&d, 0, sizeof(d));
 	d.list = d_list; d.list_count = d_count; d.list_cap = (uint32_t)list_cap;
-	if (ds.use_world) {
-		WorldState& w = ctx->world;
-		d.wpx = w.pos[3].p; d.wpy = w.pos[4].p; d.wpz = w.pos[5].p; d.wrot = w.rot[1].p; d.wsx = w.scl[3].p; d.wsy = w.scl[4].p; d.wsz = w.scl[5].p;
-		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = w.n;
-	} else {
-		if (!ds.d_tr.p) LMX_HIP(ctx, ds.d_tr.reserve(1)); // (a non-null pointer selects the uploaded array; n_tr == 0 reads zeros)
-		d.tr = ds.d_tr.p; d.n_tr = ds.n_tr;
-	}
 	d.light_tab = cl.d_light_tab.p; d.n_light_tab = cl.n_light_tab;
 	if (cl.have_atlas) { d.atlas = cl.d_atlas.p; d.n_atlas = cl.n_atlas; }
 	d.env_entity = cl.d_env_entity.p; d.env_radius = cl.d_env_radius.p; d.env_tmpl = cl.d_env_tmpl.p; d.n_env = cl.n_env;
@@ -88,17 +79,7 @@ int clusters_pass(LmxContext* ctx, const LmxClusterView* cv, const int32_t* d_li
 
 int host_counts(LmxContext* ctx, uint32_t c[5]) {
 	if (!ctx->clusters.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_clusters_run has not run");
-	LMX_HIP(ctx, read_back(c, ctx->clusters.d_state.p, 5, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
-}
-
-// `used` elements are what the run left, `room` what the buffer holds with its guard
-template <typename T> int read_out(LmxContext* ctx, T* out, uint32_t cap, const T* src, size_t used, size_t room, const char* what) {
-	if (cap < used) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu %s", used, what);
-	LMX_HIP(ctx, read_back(out, src, std::min<size_t>(cap, room), ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, c, ctx->clusters.d_state.p, 5);
 }
 
 } // namespace
@@ -109,9 +90,7 @@ int lmx_clusters_set_lights(LmxContext* ctx, uint32_t n_entities, const LmxPoint
 	LMX_CHECK_CTX(ctx);
 	if (n_entities && !lights) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null light table");
 	ClustersState& cl = ctx->clusters;
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(cl.d_light_tab, lights, n_entities, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, cl.d_light_tab, lights, n_entities)) return rc;
 	cl.n_light_tab = n_entities;
 	cl.have_lights = true;
 	return LMX_OK;
@@ -123,9 +102,7 @@ int lmx_clusters_set_atlas(LmxContext* ctx, uint32_t n_entities, const uint32_t*
 	cl.have_atlas = false;
 	cl.n_atlas = 0;
 	if (!atlas_idx) return LMX_OK;
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(cl.d_atlas, atlas_idx, n_entities, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, cl.d_atlas, atlas_idx, n_entities)) return rc;
 	cl.n_atlas = n_entities;
 	cl.have_atlas = true;
 	return LMX_OK;
@@ -189,9 +166,9 @@ int lmx_clusters_reserve(LmxContext* ctx, uint32_t max_lights, uint32_t map_capa
 	LMX_HIP(ctx, cl.d_env_out.reserve(LMX_CLUSTER_MAX_PROBES));
 	LMX_HIP(ctx, cl.d_refl_out.reserve(LMX_CLUSTER_MAX_PROBES));
 	LMX_HIP(ctx, cl.d_state.reserve(CLUSTERS_STATE_WORDS));
-	LMX_HIP(ctx, hipMemsetAsync(cl.d_lights.p + (size_t)max_lights * 4, 0xA5, CLUSTERS_GUARD_BYTES, ctx->stream));
-	LMX_HIP(ctx, hipMemsetAsync(cl.d_light_entities.p + max_lights, 0xA5, CLUSTERS_GUARD_BYTES, ctx->stream));
-	LMX_HIP(ctx, hipMemsetAsync(cl.d_map.p + map_capacity, 0xA5, CLUSTERS_GUARD_BYTES, ctx->stream));
+	LMX_HIP(ctx, fill_guard(cl.d_lights.p + (size_t)max_lights * 4, GUARD_RECORDS * 4, ctx->stream));
+	LMX_HIP(ctx, fill_guard(cl.d_light_entities.p + max_lights, GUARD_WORDS, ctx->stream));
+	LMX_HIP(ctx, fill_guard(cl.d_map.p + map_capacity, GUARD_WORDS, ctx->stream));
 	LMX_HIP(ctx, hipMemsetAsync(cl.d_state.p, 0, CLUSTERS_STATE_WORDS * sizeof(uint32_t), ctx->stream));
 	cl.max_lights = max_lights;
 	cl.map_capacity = map_capacity;
@@ -222,11 +199,7 @@ int lmx_clusters_run_list(LmxContext* ctx, const LmxClusterView* cv, const int32
 	if (n > (1u << 30)) return fail(ctx, LMX_ERR_CAPACITY, "%u listed lights: at most 2^30", n);
 	if (int rc = clusters_ready(ctx)) return rc;
 	ClustersState& cl = ctx->clusters;
-	cl.list_n = n;
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(cl.d_list, entities, n, ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(cl.d_state.p + CLUSTERS_LIST_N, &cl.list_n, 1, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_list(ctx, cl.d_list, entities, n, cl.d_state.p + CLUSTERS_LIST_N, cl.list_n)) return rc;
 	return clusters_pass(ctx, cv, cl.d_list.p, cl.d_state.p + CLUSTERS_LIST_N, n);
 }
 

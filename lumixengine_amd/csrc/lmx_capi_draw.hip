@@ -34,7 +34,9 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 	if (!n_batches) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "n_batches must be at least 1");
 	if ((uint64_t)n * 96 + 16 > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "%u pairs: the instance buffer's offsets are 32 bits", n);
 	if ((uint64_t)n_group_values * 48 + 16 > 0xffffffffull) return fail(ctx, LMX_ERR_CAPACITY, "%u instanced renderables: the group buffer's offsets are 32 bits", n_group_values);
-	if (ds.use_world && !ctx->world.n) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
+	DrawDevice d;
+	memset(&d, 0, sizeof(d));
+	if (int rc = bind_entity_transforms(ctx, d)) return rc;
 	if (int rc = keys_upload_instances(ctx)) return rc; // as lmx_keys_run
 	// ModelInstance::lod of the sorted set's entities lives in the slot-ordered mirror: hand it to the entity-indexed records the encode
 	// reads (what lmx_keys_read_state does; the mirror stays valid)
@@ -62,8 +64,6 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 	v.nx = view->frustum.xs[LMX_PLANE_NEAR]; v.ny = view->frustum.ys[LMX_PLANE_NEAR]; v.nz = view->frustum.zs[LMX_PLANE_NEAR]; v.nd = view->frustum.ds[LMX_PLANE_NEAR];
 	for (uint32_t b = 0; b < 256; ++b) if (view->bucket_depth_sorted[b]) v.depth_sorted[b >> 5] |= 1u << (b & 31u);
 
-	DrawDevice d;
-	memset(&d, 0, sizeof(d));
 	d.keys = d_keys; d.values = d_values; d.n = n;
 	d.step = std::max<uint32_t>((uint32_t)(((uint64_t)n + n_batches - 1) / n_batches), 1u); // :2794
 	if (n_groups) {
@@ -78,14 +78,6 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 	}
 	d.mesh_lod = ds.d_mesh_lod.p; d.n_meshes = ds.n_meshes;
 	d.material_index = ds.d_material_index.p; d.n_mesh_materials = ds.n_material_index;
-	if (ds.use_world) {
-		WorldState& w = ctx->world;
-		d.wpx = w.pos[3].p; d.wpy = w.pos[4].p; d.wpz = w.pos[5].p; d.wrot = w.rot[1].p; d.wsx = w.scl[3].p; d.wsy = w.scl[4].p; d.wsz = w.scl[5].p;
-		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = w.n;
-	} else {
-		if (!ds.d_tr.p) LMX_HIP(ctx, ds.d_tr.reserve(1)); // (a non-null pointer selects the uploaded array; n_tr == 0 reads zeros)
-		d.tr = ds.d_tr.p; d.n_tr = ds.n_tr;
-	}
 	d.prev = ds.d_prev.p; d.n_prev = ds.n_prev;
 	d.bones_handle = ds.d_bones_handle.p; d.bones_offset = ds.d_bones_offset.p; d.n_bones = ds.n_bones;
 	if (ds.have_decals) { d.decals = ds.d_decals.p; d.n_decals = ds.n_decals; }
@@ -115,11 +107,8 @@ int draw_pass(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batches, cons
 }
 
 int host_counts(LmxContext* ctx, uint32_t c[4]) {
-	DrawState& ds = ctx->draw;
-	if (!ds.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_run has not run");
-	LMX_HIP(ctx, read_back(c, ds.d_counts.p, 4, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	if (!ctx->draw.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_run has not run");
+	return read_now(ctx, c, ctx->draw.d_counts.p, 4);
 }
 
 } // namespace
@@ -129,9 +118,7 @@ extern "C" {
 int lmx_draw_set_meshes(LmxContext* ctx, const float* mesh_lod, uint32_t n_meshes) {
 	LMX_CHECK_CTX(ctx);
 	if (n_meshes && !mesh_lod) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null mesh table");
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_mesh_lod, mesh_lod, n_meshes, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, ctx->draw.d_mesh_lod, mesh_lod, n_meshes)) return rc;
 	ctx->draw.n_meshes = n_meshes;
 	return LMX_OK;
 }
@@ -139,9 +126,7 @@ int lmx_draw_set_meshes(LmxContext* ctx, const float* mesh_lod, uint32_t n_meshe
 int lmx_draw_set_material_indices(LmxContext* ctx, const uint32_t* material_index, uint32_t n_mesh_materials) {
 	LMX_CHECK_CTX(ctx);
 	if (n_mesh_materials && !material_index) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null material-index table");
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_material_index, material_index, n_mesh_materials, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, ctx->draw.d_material_index, material_index, n_mesh_materials)) return rc;
 	ctx->draw.n_material_index = n_mesh_materials;
 	return LMX_OK;
 }
@@ -149,9 +134,7 @@ int lmx_draw_set_material_indices(LmxContext* ctx, const uint32_t* material_inde
 int lmx_draw_set_transforms(LmxContext* ctx, const LmxTransform* transforms, uint32_t n_entities) {
 	LMX_CHECK_CTX(ctx);
 	if (n_entities && !transforms) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null transforms");
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_tr, transforms, n_entities, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, ctx->draw.d_tr, transforms, n_entities)) return rc;
 	ctx->draw.n_tr = n_entities;
 	return LMX_OK;
 }
@@ -165,9 +148,7 @@ int lmx_draw_bind_world(LmxContext* ctx, int enable) {
 int lmx_draw_set_prev_transforms(LmxContext* ctx, const LmxTransform* transforms, uint32_t n_entities) {
 	LMX_CHECK_CTX(ctx);
 	if (n_entities && !transforms) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null transforms");
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_prev, transforms, n_entities, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, ctx->draw.d_prev, transforms, n_entities)) return rc;
 	ctx->draw.n_prev = n_entities;
 	return LMX_OK;
 }
@@ -177,8 +158,6 @@ int lmx_draw_set_bones(LmxContext* ctx, const uint32_t* handle, const uint32_t* 
 	if (n_entities && (!handle || !offset)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null bones table");
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_bones_handle, handle, n_entities, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	LMX_HIP(ctx, upload_on_stream(ctx->draw.d_bones_offset, offset, n_entities, ctx->stream));
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->draw.n_bones = n_entities;
@@ -201,9 +180,7 @@ int lmx_draw_set_decals(LmxContext* ctx, uint32_t n_entities, const float* half_
 			memcpy(r[e].uv_scale, uv_scale + 2 * (size_t)e, 8);
 			r[e].material_index = material_index[e];
 		}
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, upload_on_stream(ds.d_decals, r.data(), n_entities, ctx->stream));
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (int rc = upload_settled(ctx, ds.d_decals, r.data(), n_entities)) return rc;
 		ds.n_decals = n_entities;
 		ds.have_decals = true;
 	}
@@ -216,9 +193,7 @@ int lmx_draw_set_decals(LmxContext* ctx, uint32_t n_entities, const float* half_
 			memcpy(r[e].bezier, curve_bezier + 4 * (size_t)e, 16);
 			r[e].material_index = curve_material_index[e];
 		}
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, upload_on_stream(ds.d_curves, r.data(), n_entities, ctx->stream));
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (int rc = upload_settled(ctx, ds.d_curves, r.data(), n_entities)) return rc;
 		ds.n_curves = n_entities;
 		ds.have_curves = true;
 	}
@@ -251,18 +226,12 @@ int lmx_draw_run_pairs(LmxContext* ctx, const LmxDrawView* view, uint32_t n_batc
 	DrawState& ds = ctx->draw;
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	LMX_HIP(ctx, upload_on_stream(ds.d_keys, keys, n, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	LMX_HIP(ctx, upload_on_stream(ds.d_values, values, n, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	if (n_groups) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		LMX_HIP(ctx, upload_on_stream(ds.d_group_offset, group_offsets, (size_t)n_groups + 1, ctx->stream));
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		LMX_HIP(ctx, upload_on_stream(ds.d_group_values, group_values, n_group_values, ctx->stream));
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	}
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return draw_pass(ctx, view, n_batches, ds.d_keys.p, ds.d_values.p, n, ds.d_group_offset.p, ds.d_group_values.p, n_groups, n_group_values);
 }
 
@@ -279,20 +248,14 @@ int lmx_draw_read_runs(LmxContext* ctx, LmxDrawRun* runs, uint32_t cap) {
 	LMX_CHECK_CTX(ctx);
 	uint32_t c[4];
 	if (int rc = host_counts(ctx, c)) return rc;
-	if (cap < c[0]) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u runs", c[0]);
-	LMX_HIP(ctx, read_back(runs, ctx->draw.d_runs.p, c[0], ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, runs, cap, (const LmxDrawRun*)ctx->draw.d_runs.p, c[0], c[0], "runs");
 }
 
 int lmx_draw_read_instance_data(LmxContext* ctx, void* out, size_t cap_bytes) {
 	LMX_CHECK_CTX(ctx);
 	uint32_t c[4];
 	if (int rc = host_counts(ctx, c)) return rc;
-	if (cap_bytes < c[1]) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bytes", c[1]);
-	LMX_HIP(ctx, read_back((uint8_t*)out, ctx->draw.d_instance_data.p, c[1], ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, (uint8_t*)out, cap_bytes, (const uint8_t*)ctx->draw.d_instance_data.p, c[1], c[1], "bytes");
 }
 
 int lmx_draw_read_group_data(LmxContext* ctx, void* out, size_t cap_bytes) {
@@ -300,10 +263,7 @@ int lmx_draw_read_group_data(LmxContext* ctx, void* out, size_t cap_bytes) {
 	uint32_t c[4];
 	if (int rc = host_counts(ctx, c)) return rc;
 	const size_t bytes = (size_t)c[3] * 48;
-	if (cap_bytes < bytes) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu bytes", bytes);
-	LMX_HIP(ctx, read_back((uint8_t*)out, ctx->draw.d_group_data.p, bytes, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, (uint8_t*)out, cap_bytes, (const uint8_t*)ctx->draw.d_group_data.p, bytes, bytes, "bytes");
 }
 
 int lmx_draw_device_outputs(LmxContext* ctx, const LmxDrawRun** d_runs, const void** d_instance_data, const void** d_group_data, const uint32_t** d_counts) {

@@ -413,8 +413,7 @@ int lmx_grass_read_quads(LmxGrass* g, LmxGrassQuad* out, uint32_t cap, uint32_t*
 	if (!n) return LMX_OK;
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	std::vector<LmxGrassQuad> all(g->n_slots);
-	LMX_HIP(ctx, read_back(all.data(), (const LmxGrassQuad*)g->d_quads.p, all.size(), ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = read_now(ctx, all.data(), (const LmxGrassQuad*)g->d_quads.p, all.size())) return rc;
 	for (uint32_t q = 0; q < n; ++q) out[q] = all[g->live[q].slot];
 	return LMX_OK;
 }
@@ -426,9 +425,7 @@ int lmx_grass_read_instances(LmxGrass* g, uint32_t slot, LmxGrassInstance* out, 
 	if (slot >= g->n_slots) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "slot %u of %u", slot, g->n_slots);
 	if (cap < LMX_GRASS_SLOT_INSTANCES) return fail(ctx, LMX_ERR_CAPACITY, "a slot holds %d records, cap %u", LMX_GRASS_SLOT_INSTANCES, cap);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LMX_HIP(ctx, read_back(out, (const LmxGrassInstance*)(g->d_pool.p + (size_t)slot * 2 * LMX_GRASS_SLOT_INSTANCES), LMX_GRASS_SLOT_INSTANCES, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, out, (const LmxGrassInstance*)(g->d_pool.p + (size_t)slot * 2 * LMX_GRASS_SLOT_INSTANCES), LMX_GRASS_SLOT_INSTANCES);
 }
 
 int lmx_grass_write_instances(LmxGrass* g, uint32_t slot, const LmxGrassInstance* in, uint32_t n) {
@@ -449,15 +446,12 @@ int lmx_grass_read_draws(LmxGrass* g, uint32_t view, LmxGrassDraw* out, uint32_t
 	if (!g->culled) return fail(ctx, LMX_ERR_NOT_BUILT, "no lmx_grass_cull has run");
 	if (view >= g->n_views) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "view %u of %u", view, g->n_views);
 	LmxGrassCounts c;
-	LMX_HIP(ctx, read_back(&c, (const LmxGrassCounts*)g->d_counts.p + view, 1, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = read_now(ctx, &c, (const LmxGrassCounts*)g->d_counts.p + view, 1)) return rc;
 	if (out_n) *out_n = c.draws;
 	if (cap < c.draws) return fail(ctx, LMX_ERR_CAPACITY, "%u draws, cap %u", c.draws, cap);
 	if (!c.draws) return LMX_OK;
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LMX_HIP(ctx, read_back(out, (const LmxGrassDraw*)g->d_draws.p + (size_t)view * g->draw_stride, c.draws, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, out, (const LmxGrassDraw*)g->d_draws.p + (size_t)view * g->draw_stride, c.draws);
 }
 
 int lmx_grass_counts(LmxGrass* g, LmxGrassCounts* out, uint32_t cap_views) {
@@ -467,9 +461,7 @@ int lmx_grass_counts(LmxGrass* g, LmxGrassCounts* out, uint32_t cap_views) {
 	if (!g->culled) return fail(ctx, LMX_ERR_NOT_BUILT, "no lmx_grass_cull has run");
 	if (cap_views < g->n_views) return fail(ctx, LMX_ERR_CAPACITY, "%u views, cap %u", g->n_views, cap_views);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LMX_HIP(ctx, read_back(out, (const LmxGrassCounts*)g->d_counts.p, g->n_views, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, out, (const LmxGrassCounts*)g->d_counts.p, g->n_views);
 }
 
 int lmx_grass_device_outputs(LmxGrass* g, LmxGrassDevice* out) {

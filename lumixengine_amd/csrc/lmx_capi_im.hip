@@ -292,8 +292,7 @@ int lmx_im_read_grid(LmxInstancedModels* im, uint32_t model, LmxImGrid* out) {
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (model >= im->models.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "unknown model %u", model);
 	ImGridDev g;
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, hipMemcpy(&g, im->d_grids.p + model, sizeof(g), hipMemcpyDeviceToHost));
+	if (int rc = read_now(ctx, &g, (const ImGridDev*)im->d_grids.p + model, 1)) return rc;
 	memset(out, 0, sizeof(*out));
 	for (int k = 0; k < 3; ++k) {
 		out->min[k] = g.mn[k];
@@ -328,10 +327,9 @@ int lmx_im_read_instances(LmxInstancedModels* im, uint32_t model, LmxImInstance*
 	const size_t first = im->table[model].first;
 	std::vector<float4> ps(n), rot(n);
 	std::vector<float> lod(n);
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, hipMemcpy(ps.data(), im->d_pos_scale.p + first, n * sizeof(float4), hipMemcpyDeviceToHost));
-	LMX_HIP(ctx, hipMemcpy(rot.data(), im->d_rot.p + first, n * sizeof(float4), hipMemcpyDeviceToHost));
-	LMX_HIP(ctx, hipMemcpy(lod.data(), im->d_lod.p + first, n * sizeof(float), hipMemcpyDeviceToHost));
+	LMX_HIP(ctx, read_back(ps.data(), (const float4*)im->d_pos_scale.p + first, n, ctx->stream));
+	LMX_HIP(ctx, read_back(rot.data(), (const float4*)im->d_rot.p + first, n, ctx->stream));
+	if (int rc = read_now(ctx, lod.data(), (const float*)im->d_lod.p + first, n)) return rc;
 	for (uint32_t i = 0; i < n; ++i) {
 		out[i].rot[0] = rot[i].x; out[i].rot[1] = rot[i].y; out[i].rot[2] = rot[i].z;
 		out[i].lod = lod[i];
@@ -351,9 +349,7 @@ int lmx_im_counts(LmxInstancedModels* im, uint32_t view_slot, LmxImCounts* out, 
 	if (!s.n_models) return LMX_OK;
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	static_assert(sizeof(ImCountsDev) == sizeof(LmxImCounts), "ImCountsDev mirrors LmxImCounts");
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, hipMemcpy(out, s.counts.p, s.n_models * sizeof(LmxImCounts), hipMemcpyDeviceToHost));
-	return LMX_OK;
+	return read_now(ctx, (ImCountsDev*)out, (const ImCountsDev*)s.counts.p, s.n_models);
 }
 
 int lmx_im_read_records(LmxInstancedModels* im, uint32_t view_slot, LmxImInstance* out, uint32_t cap, uint32_t* out_n) {
@@ -370,8 +366,7 @@ int lmx_im_read_records(LmxInstancedModels* im, uint32_t view_slot, LmxImInstanc
 	if (cap < total) return fail(ctx, LMX_ERR_CAPACITY, "%zu records, cap %u", total, cap);
 	if (!total) return LMX_OK;
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LMX_HIP(ctx, hipMemcpy(out, s.records.p, total * sizeof(LmxImInstance), hipMemcpyDeviceToHost));
-	return LMX_OK;
+	return read_now(ctx, out, (const LmxImInstance*)s.records.p, total);
 }
 
 int lmx_im_read_indirect(LmxInstancedModels* im, uint32_t view_slot, LmxImIndirect* out, uint32_t cap, uint32_t* out_n) {
@@ -384,9 +379,7 @@ int lmx_im_read_indirect(LmxInstancedModels* im, uint32_t view_slot, LmxImIndire
 	if (cap < s.n_indirect) return fail(ctx, LMX_ERR_CAPACITY, "%u indirect records, cap %u", s.n_indirect, cap);
 	if (!s.n_indirect) return LMX_OK;
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, hipMemcpy(out, s.indirect.p, s.n_indirect * sizeof(LmxImIndirect), hipMemcpyDeviceToHost));
-	return LMX_OK;
+	return read_now(ctx, out, (const LmxImIndirect*)s.indirect.p, s.n_indirect);
 }
 
 int lmx_im_device_outputs(LmxInstancedModels* im, uint32_t view_slot, const void** d_records, const void** d_indirect, const void** d_counts) {

@@ -138,9 +138,7 @@ int lmx_keys_set_instances(LmxContext* ctx, uint32_t n_entities, const int32_t* 
 		const LmxKeysModel& m = ks.models[model[e]];
 		for (uint32_t k = 0; k < m.mesh_count; ++k) dev_mm[material_offset[e] + k]._pad[0] = ks.mesh_types[m.first_mesh + k];
 	}
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ks.d_mesh_materials, dev_mm, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, ks.d_mesh_materials, dev_mm.data(), dev_mm.size())) return rc;
 	// one 64-byte record per entity (positions of an earlier lmx_keys_set_positions are kept)
 	ks.inst.resize(n_entities);
 	for (uint32_t e = 0; e < n_entities; ++e) {
@@ -445,9 +443,7 @@ int lmx_keys_run(LmxContext* ctx, uint32_t view, uint32_t frustum, const LmxKeys
 static int keys_host_counters(LmxContext* ctx, uint32_t* c) {
 	KeysState& ks = ctx->keys;
 	if (!ks.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_keys_run has not run");
-	LMX_HIP(ctx, read_back(c, ks.d_groups.p + ks.counters_at, KEYS_COUNTERS, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, c, (const uint32_t*)ks.d_groups.p + ks.counters_at, KEYS_COUNTERS);
 }
 
 int lmx_keys_counts(LmxContext* ctx, LmxKeysCounts* out) {
@@ -493,9 +489,7 @@ int lmx_keys_read_pairs(LmxContext* ctx, uint64_t* keys, uint64_t* values, uint3
 	const uint32_t n = c[KEYS_N_PAIRS];
 	if (cap < n) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u pairs", n);
 	LMX_HIP(ctx, read_back(keys, ks.d_keys.p, n, ctx->stream));
-	LMX_HIP(ctx, read_back(values, ks.d_values.p, n, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, values, (const uint64_t*)ks.d_values.p, n);
 }
 
 int lmx_keys_read_instancer(LmxContext* ctx, uint32_t* offsets, uint64_t* values, uint32_t cap_values) {
@@ -507,9 +501,7 @@ int lmx_keys_read_instancer(LmxContext* ctx, uint32_t* offsets, uint64_t* values
 	const uint32_t n = c[KEYS_N_RECS];
 	if (values && cap_values < n) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u instanced renderables", n);
 	LMX_HIP(ctx, read_back(offsets, ks.d_groups.p + ks.offsets_at, (size_t)ks.max_sort_key + 2, ctx->stream));
-	LMX_HIP(ctx, read_back(values, ks.d_group_values.p, n, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, values, (const uint64_t*)ks.d_group_values.p, n);
 }
 
 static int keys_read_list(LmxContext* ctx, int which, const int32_t* src, int32_t* entities, uint32_t cap) {
@@ -517,10 +509,7 @@ static int keys_read_list(LmxContext* ctx, int which, const int32_t* src, int32_
 	if (int rc = keys_host_counters(ctx, c)) return rc;
 	if (c[KEYS_OVERFLOW]) return fail(ctx, LMX_ERR_CAPACITY, "sort-key output overflowed (code %u)", c[KEYS_OVERFLOW]);
 	const uint32_t n = c[which];
-	if (cap < n) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u entities", n);
-	LMX_HIP(ctx, read_back(entities, src, n, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, entities, cap, src, n, n, "entities");
 }
 
 int lmx_keys_read_poses(LmxContext* ctx, int32_t* entities, uint32_t cap) {

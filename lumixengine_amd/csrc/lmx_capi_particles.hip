@@ -395,10 +395,10 @@ int build(LmxParticles* ps) {
 	for (size_t e = 0; e < n; ++e) { // the guards behind every channel
 		const ParticleEmitterDev& t = ps->table[e];
 		for (uint32_t c = 0; c < t.channels; ++c)
-			LMX_HIP(ctx, hipMemsetAsync(ps->d_channels.p + t.channel_base + (size_t)c * t.stride + t.capacity, 0xA5, PARTICLE_GUARD_FLOATS * 4, ctx->stream));
+			LMX_HIP(ctx, fill_guard(ps->d_channels.p + t.channel_base + (size_t)c * t.stride + t.capacity, PARTICLE_GUARD_FLOATS, ctx->stream));
 	}
 	LMX_HIP(ctx, hipMemsetAsync(ps->d_frame.p, 0, frame * sizeof(float), ctx->stream));
-	LMX_HIP(ctx, hipMemsetAsync(ps->d_frame.p + frame, 0xA5, PARTICLE_GUARD_FLOATS * 4, ctx->stream));
+	LMX_HIP(ctx, fill_guard(ps->d_frame.p + frame, PARTICLE_GUARD_FLOATS, ctx->stream));
 	LMX_HIP(ctx, hipMemsetAsync(ps->d_state.p, 0, std::max<size_t>(n, 1) * sizeof(ParticleStateDev), ctx->stream));
 	LMX_HIP(ctx, hipMemsetAsync(ps->d_kill.p, 0, std::max<uint32_t>(chunks_total, 1) * sizeof(uint32_t), ctx->stream));
 	LMX_HIP(ctx, hipMemsetAsync(ps->d_n_ops.p, 0, std::max<size_t>(n, 1) * sizeof(uint32_t), ctx->stream));
@@ -639,9 +639,7 @@ int lmx_particles_counts(LmxParticles* ps, LmxParticlesCounts* out, uint32_t cap
 	LMX_CHECK_PARTICLES(ps);
 	if (int rc = build(ps)) return rc;
 	if (cap < ps->emitters.size() || (!out && !ps->emitters.empty())) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu emitters", ps->emitters.size());
-	LMX_HIP(ctx, read_back((ParticleStateDev*)out, (const ParticleStateDev*)ps->d_state.p, ps->emitters.size(), ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, (ParticleStateDev*)out, (const ParticleStateDev*)ps->d_state.p, ps->emitters.size());
 }
 
 int lmx_particles_read_channels(LmxParticles* ps, uint32_t system, uint32_t emitter, float* out, uint32_t cap_floats, uint32_t* out_stride) {
@@ -653,8 +651,7 @@ int lmx_particles_read_channels(LmxParticles* ps, uint32_t system, uint32_t emit
 	const size_t need = (size_t)t.stride * t.channels;
 	if (out_stride) *out_stride = t.stride;
 	if (cap_floats < need || (!out && need)) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu floats", need);
-	LMX_HIP(ctx, read_back(out, (const float*)ps->d_channels.p + t.channel_base, need, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = read_now(ctx, out, (const float*)ps->d_channels.p + t.channel_base, need)) return rc;
 	if (t.ribbon_len && out) { // the reference's layout: ribbon r's ring at [r x max_len, (r + 1) x max_len); the rings no ribbon holds behind them
 		const LmxParticles::Emitter& em = ps->emitters[e];
 		std::vector<float> row(t.capacity);
@@ -676,9 +673,7 @@ int lmx_particles_read_slices(LmxParticles* ps, LmxParticleSlice* slices, uint32
 	const size_t bytes = ((size_t)ps->frame_floats + PARTICLE_GUARD_FLOATS) * 4;
 	if (data && cap_bytes < bytes) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu bytes", bytes);
 	LMX_HIP(ctx, read_back(slices, (const LmxParticleSlice*)ps->d_slices.p, ps->emitters.size(), ctx->stream));
-	LMX_HIP(ctx, read_back((float*)data, (const float*)ps->d_frame.p, bytes / 4, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, (float*)data, (const float*)ps->d_frame.p, bytes / 4);
 }
 
 int lmx_particles_set_emitter_options(LmxParticles* ps, uint32_t system, uint32_t emitter, const LmxParticleEmitterOptions* o) {

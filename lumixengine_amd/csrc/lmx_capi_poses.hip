@@ -18,7 +18,7 @@ int poses_reserve(LmxContext* ctx) {
 	LMX_HIP(ctx, ps.d_dual_quats.reserve(sk.bones_total * 2 + POSES_GUARD_BYTES / sizeof(float4)));
 	LMX_HIP(ctx, ps.d_state.reserve(POSES_STATE_WORDS));
 	LMX_HIP(ctx, ps.d_block_sum.reserve(POSE_GRID));
-	LMX_HIP(ctx, hipMemsetAsync(ps.d_dual_quats.p + sk.bones_total * 2, 0xA5, POSES_GUARD_BYTES, ctx->stream));
+	LMX_HIP(ctx, fill_guard(ps.d_dual_quats.p + sk.bones_total * 2, POSES_GUARD_BYTES / sizeof(float4), ctx->stream));
 	LMX_HIP(ctx, hipMemsetAsync(ps.d_state.p, 0, POSES_STATE_WORDS * sizeof(uint32_t), ctx->stream));
 	ps.cap_bytes = (uint32_t)(sk.bones_total * POSE_BONE_BYTES);
 	ps.reserved_bones = sk.bones_total;
@@ -82,9 +82,7 @@ int poses_pass(LmxContext* ctx, const int32_t* d_list, const uint32_t* d_count, 
 int host_counts(LmxContext* ctx, uint32_t c[4]) {
 	if (int rc = poses_ready(ctx)) return rc;
 	if (int rc = poses_reserve(ctx)) return rc;
-	LMX_HIP(ctx, read_back(c, ctx->poses.d_state.p, 4, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, c, ctx->poses.d_state.p, 4);
 }
 
 } // namespace
@@ -95,9 +93,7 @@ int lmx_poses_set_instances(LmxContext* ctx, uint32_t n_entities, const int32_t*
 	LMX_CHECK_CTX(ctx);
 	if (n_entities && !skin_instance) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null skin instance table");
 	PosesState& ps = ctx->poses;
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ps.d_skin_of_entity, skin_instance, n_entities, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, ps.d_skin_of_entity, skin_instance, n_entities)) return rc;
 	ps.n_entities = n_entities;
 	ps.have_instances = true;
 	ps.reserved_bones = ~(size_t)0; // the frame starts over
@@ -132,11 +128,7 @@ int lmx_poses_run_list(LmxContext* ctx, const int32_t* entities, uint32_t n) {
 	if (n && !entities) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null list");
 	PosesState& ps = ctx->poses;
 	if (int rc = poses_reserve(ctx)) return rc;
-	ps.list_n = n;
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ps.d_list, entities, n, ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(ps.d_state.p + POSES_LIST_N, &ps.list_n, 1, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_list(ctx, ps.d_list, entities, n, ps.d_state.p + POSES_LIST_N, ps.list_n)) return rc;
 	return poses_pass(ctx, ps.d_list.p, ps.d_state.p + POSES_LIST_N, n);
 }
 
@@ -156,21 +148,14 @@ int lmx_poses_read_slices(LmxContext* ctx, uint32_t* handle, uint32_t* offset, u
 	if (n_entities < ps.n_entities) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u entities", ps.n_entities);
 	if (int rc = poses_grow_tables(ctx)) return rc;
 	LMX_HIP(ctx, read_back(handle, ctx->draw.d_bones_handle.p, ps.n_entities, ctx->stream));
-	LMX_HIP(ctx, read_back(offset, ctx->draw.d_bones_offset.p, ps.n_entities, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_now(ctx, offset, (const uint32_t*)ctx->draw.d_bones_offset.p, ps.n_entities);
 }
 
 int lmx_poses_read_buffer(LmxContext* ctx, void* out, size_t cap_bytes) {
 	LMX_CHECK_CTX(ctx);
 	uint32_t c[4];
 	if (int rc = host_counts(ctx, c)) return rc;
-	if (cap_bytes < c[POSES_BYTES]) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u bytes", c[POSES_BYTES]);
-	// a larger array also gets what lies behind the frame's slices, up to the end of the guard
-	const size_t n = std::min<size_t>(cap_bytes, (size_t)ctx->poses.cap_bytes + POSES_GUARD_BYTES);
-	LMX_HIP(ctx, read_back((uint8_t*)out, (const uint8_t*)ctx->poses.d_dual_quats.p, n, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, (uint8_t*)out, cap_bytes, (const uint8_t*)ctx->poses.d_dual_quats.p, c[POSES_BYTES], (size_t)ctx->poses.cap_bytes + POSES_GUARD_BYTES, "bytes");
 }
 
 int lmx_poses_device_outputs(LmxContext* ctx, const void** d_dual_quats, const uint32_t** d_counts) {

@@ -37,10 +37,7 @@ int rays_im_pass(LmxContext* ctx, const RaysDevice& d, ImRaysDevice& q) {
 	if (int rc = im_ray_tables(rs.im, &t)) return rc;
 	if (rs.im_uploaded != t.n_models || rs.im_ray_models.size() != t.n_models) { // (models registered since the attach have no ray-table model)
 		rs.im_ray_models.resize(t.n_models, RayImModelRec{-1, -1});
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, rs.d_im_ray_models.reserve(std::max<size_t>(t.n_models, 1)));
-		LMX_HIP(ctx, upload_on_stream(rs.d_im_ray_models.p, rs.im_ray_models.data(), t.n_models, ctx->stream));
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (int rc = upload_settled(ctx, rs.d_im_ray_models, rs.im_ray_models.data(), t.n_models)) return rc;
 		rs.im_uploaded = t.n_models;
 	}
 	if (int rc = rays_im_reserve(ctx)) return rc;
@@ -77,25 +74,16 @@ int rays_upload_meshes(LmxContext* ctx) {
 
 int rays_pass(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 	RaysState& rs = ctx->rays;
-	DrawState& ds = ctx->draw;
 	if (!rs.have_models) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_set_models has not been called");
 	if (!rs.have_instances) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_set_instances has not been called");
 	if (!rs.reserved) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_reserve has not been called");
 	if (n > rs.max_rays) return fail(ctx, LMX_ERR_CAPACITY, "%u rays: %u reserved", n, rs.max_rays);
-	if (ds.use_world && !ctx->world.n) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
-	if (int rc = rays_upload_meshes(ctx)) return rc;
 	RaysDevice d;
 	memset(&d, 0, sizeof(d));
+	if (int rc = bind_entity_transforms(ctx, d)) return rc;
+	if (int rc = rays_upload_meshes(ctx)) return rc;
 	d.rays = d_rays; d.n_rays = n;
 	d.inst_model = rs.d_inst_model.p; d.inst_flags = rs.d_inst_flags.p; d.n_inst = rs.n_inst;
-	if (ds.use_world) {
-		WorldState& w = ctx->world;
-		d.wpx = w.pos[3].p; d.wpy = w.pos[4].p; d.wpz = w.pos[5].p; d.wrot = w.rot[1].p; d.wsx = w.scl[3].p; d.wsy = w.scl[4].p; d.wsz = w.scl[5].p;
-		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = w.n;
-	} else {
-		if (!ds.d_tr.p) LMX_HIP(ctx, ds.d_tr.reserve(1)); // (a non-null pointer selects the uploaded array; n_tr == 0 reads zeros)
-		d.tr = ds.d_tr.p; d.n_tr = ds.n_tr;
-	}
 	d.models = rs.d_models.p; d.n_models = rs.n_models;
 	d.meshes = rs.d_meshes.p; d.positions = rs.d_positions.p; d.skins = rs.d_skins.p; d.indices = rs.d_indices.p;
 	SkinState& sk = ctx->skin;
@@ -124,13 +112,6 @@ int rays_pass(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 	rs.ran = true;
 	rs.im_ran = rs.im != nullptr;
 	rs.scene_ran = rs.scene();
-	return LMX_OK;
-}
-
-int host_counts(LmxContext* ctx, uint32_t c[3]) {
-	if (!ctx->rays.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_cast has not run");
-	LMX_HIP(ctx, read_back(c, ctx->rays.d_state.p, 3, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
 
@@ -209,9 +190,7 @@ int lmx_rays_set_models(LmxContext* ctx, uint32_t n_models, const LmxRayModel* m
 		r.n_tris = tris;
 		r.last_skinned = in.mesh_count && rs.meshes[in.first_mesh + in.mesh_count - 1].skin_at != 0xffffffffu ? 1u : 0u;
 	}
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	LMX_HIP(ctx, upload_on_stream(rs.d_models, recs, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = upload_settled(ctx, rs.d_models, recs.data(), recs.size())) return rc;
 	rs.n_models = n_models;
 	rs.have_models = true;
 	return LMX_OK;
@@ -246,7 +225,7 @@ int lmx_rays_reserve(LmxContext* ctx, uint32_t max_rays, uint32_t max_candidates
 	LMX_HIP(ctx, rs.d_cand_best.reserve(std::max<size_t>(max_candidates, 1)));
 	LMX_HIP(ctx, rs.d_cand_t.reserve(std::max<size_t>(max_candidates, 1)));
 	LMX_HIP(ctx, rs.d_state.reserve(RAYS_STATE_WORDS));
-	LMX_HIP(ctx, hipMemsetAsync(rs.d_cand.p + max_candidates, 0xA5, GUARD_RECORDS * sizeof(RayCandidate), ctx->stream));
+	LMX_HIP(ctx, fill_guard(rs.d_cand.p + max_candidates, GUARD_RECORDS, ctx->stream));
 	LMX_HIP(ctx, hipMemsetAsync(rs.d_state.p, 0, RAYS_STATE_WORDS * sizeof(uint32_t), ctx->stream));
 	rs.max_rays = max_rays;
 	rs.max_cand = max_candidates;
@@ -277,8 +256,9 @@ int lmx_rays_cast_device(LmxContext* ctx, const LmxRay* d_rays, uint32_t n) {
 int lmx_rays_counts(LmxContext* ctx, LmxRaysCounts* out) {
 	LMX_CHECK_CTX(ctx);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
+	if (!ctx->rays.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_cast has not run");
 	uint32_t c[3];
-	if (int rc = host_counts(ctx, c)) return rc;
+	if (int rc = read_now(ctx, c, ctx->rays.d_state.p, 3)) return rc;
 	out->rays = c[RAYS_RAYS]; out->candidates = c[RAYS_CANDIDATES]; out->overflow = c[RAYS_OVERFLOW];
 	return LMX_OK;
 }
@@ -287,19 +267,14 @@ int lmx_rays_read_hits(LmxContext* ctx, LmxRayHit* out, uint32_t cap) {
 	LMX_CHECK_CTX(ctx);
 	RaysState& rs = ctx->rays;
 	if (!rs.ran) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_cast has not run");
-	if (cap < rs.n_rays) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u hits", rs.n_rays);
-	LMX_HIP(ctx, read_back(out, (const LmxRayHit*)rs.d_hits.p, rs.n_rays, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, out, cap, (const LmxRayHit*)rs.d_hits.p, rs.n_rays, rs.n_rays, "hits");
 }
 
 int lmx_rays_read_candidates(LmxContext* ctx, void* out, uint32_t cap) {
 	LMX_CHECK_CTX(ctx);
 	RaysState& rs = ctx->rays;
 	if (!rs.reserved) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_rays_reserve has not been called");
-	LMX_HIP(ctx, read_back((RayCandidate*)out, (const RayCandidate*)rs.d_cand.p, std::min<size_t>(cap, (size_t)rs.max_cand + GUARD_RECORDS), ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, (RayCandidate*)out, cap, (const RayCandidate*)rs.d_cand.p, 0, (size_t)rs.max_cand + GUARD_RECORDS, "candidates"); // (the buffer from its start: any capacity)
 }
 
 int lmx_rays_device_outputs(LmxContext* ctx, const LmxRayHit** d_hits, const uint32_t** d_counts) {
@@ -339,8 +314,7 @@ int lmx_rays_im_counts(LmxContext* ctx, LmxRaysImCounts* out) {
 	RaysState& rs = ctx->rays;
 	if (!rs.ran || !rs.im_ran) return fail(ctx, LMX_ERR_NOT_BUILT, "no cast with instanced models attached has run");
 	uint32_t c[3];
-	LMX_HIP(ctx, read_back(c, rs.d_im_state.p, 3, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = read_now(ctx, c, rs.d_im_state.p, 3)) return rc;
 	out->rays = c[RAYS_RAYS]; out->candidates = c[RAYS_CANDIDATES]; out->overflow = c[RAYS_OVERFLOW];
 	return LMX_OK;
 }
@@ -349,10 +323,7 @@ int lmx_rays_read_im_hits(LmxContext* ctx, LmxRayImHit* out, uint32_t cap) {
 	LMX_CHECK_CTX(ctx);
 	RaysState& rs = ctx->rays;
 	if (!rs.ran || !rs.im_ran) return fail(ctx, LMX_ERR_NOT_BUILT, "no cast with instanced models attached has run");
-	if (cap < rs.n_rays) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u hits", rs.n_rays);
-	LMX_HIP(ctx, read_back(out, (const LmxRayImHit*)rs.d_im_hits.p, rs.n_rays, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, out, cap, (const LmxRayImHit*)rs.d_im_hits.p, rs.n_rays, rs.n_rays, "hits");
 }
 
 int lmx_rays_device_im_outputs(LmxContext* ctx, const LmxRayImHit** d_hits, const uint32_t** d_counts) {

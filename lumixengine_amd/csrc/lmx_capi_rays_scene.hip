@@ -183,31 +183,22 @@ int lmx_rays_read_pg_hits(LmxContext* ctx, LmxRayPgHit* out, uint32_t cap) {
 	LMX_CHECK_CTX(ctx);
 	RaysState& rs = ctx->rays;
 	if (!rs.ran || !rs.scene_ran) return not_run(ctx);
-	if (cap < rs.n_rays) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u hits", rs.n_rays);
-	LMX_HIP(ctx, read_back(out, (const LmxRayPgHit*)rs.d_pg_hits.p, rs.n_rays, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, out, cap, (const LmxRayPgHit*)rs.d_pg_hits.p, rs.n_rays, rs.n_rays, "hits");
 }
 
 int lmx_rays_read_terrain_hits(LmxContext* ctx, LmxRayTerrainHit* out, uint32_t cap) {
 	LMX_CHECK_CTX(ctx);
 	RaysState& rs = ctx->rays;
 	if (!rs.ran || !rs.scene_ran) return not_run(ctx);
-	const uint64_t need = (uint64_t)rs.n_rays * rs.n_terrains;
-	if (cap < need) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u x %u hits", rs.n_rays, rs.n_terrains);
-	LMX_HIP(ctx, read_back(out, (const LmxRayTerrainHit*)rs.d_terrain_hits.p, (size_t)need, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	const size_t need = (size_t)rs.n_rays * rs.n_terrains;
+	return read_out(ctx, out, cap, (const LmxRayTerrainHit*)rs.d_terrain_hits.p, need, need, "hits (rays x terrains)");
 }
 
 int lmx_rays_read_scene_hits(LmxContext* ctx, LmxRaySceneHit* out, uint32_t cap) {
 	LMX_CHECK_CTX(ctx);
 	RaysState& rs = ctx->rays;
 	if (!rs.ran || !rs.scene_ran) return not_run(ctx);
-	if (cap < rs.n_rays) return fail(ctx, LMX_ERR_CAPACITY, "need room for %u hits", rs.n_rays);
-	LMX_HIP(ctx, read_back(out, (const LmxRaySceneHit*)rs.d_scene_hits.p, rs.n_rays, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return LMX_OK;
+	return read_out(ctx, out, cap, (const LmxRaySceneHit*)rs.d_scene_hits.p, rs.n_rays, rs.n_rays, "hits");
 }
 
 int lmx_rays_scene_counts(LmxContext* ctx, LmxRaysSceneCounts* out) {
@@ -216,8 +207,7 @@ int lmx_rays_scene_counts(LmxContext* ctx, LmxRaysSceneCounts* out) {
 	RaysState& rs = ctx->rays;
 	if (!rs.ran || !rs.scene_ran) return not_run(ctx);
 	uint32_t c[3];
-	LMX_HIP(ctx, read_back(c, rs.d_scene_state.p, 3, ctx->stream));
-	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (int rc = read_now(ctx, c, rs.d_scene_state.p, 3)) return rc;
 	out->rays = c[RAYS_RAYS]; out->candidates = c[RAYS_CANDIDATES]; out->overflow = c[RAYS_OVERFLOW];
 	return LMX_OK;
 }

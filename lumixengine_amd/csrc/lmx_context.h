@@ -62,40 +62,6 @@ template <typename T> struct DevBuf {
 	}
 };
 
-// Copies between host arrays and device buffers, counted in ELEMENTS: source and destination have one element type (cast at the call
-// site where a caller's array is declared otherwise). All return hipError_t for the caller's LMX_HIP; an empty copy issues no HIP call.
-//
-// Ordering: LmxContext::stream may be a caller's non-blocking stream, and a blocking hipMemcpy is NOT ordered behind such a stream.
-// A blocking copy into a buffer that an enqueued kernel may still read therefore needs a hipStreamSynchronize(ctx->stream) in front
-// of it. An on-stream copy is ordered by the stream, but returns before a pageable source has been read: the caller's array must
-// outlive a synchronize behind it. The synchronizes stay at the call sites, where many copies share one.
-//
-// A DevBuf destination is reserved for max(n, 1) elements first (launches want a non-null pointer for an empty table); a pointer
-// destination is copied to as it is. DevBuf::reserve frees the old allocation when it grows: the contents are lost, the pointer
-// changes, and a kernel still reading the old one must have finished - the same synchronize, in front of the reserve.
-
-// precondition: the stream whose kernels use `dst` was synchronized
-template <typename T> hipError_t upload_blocking(T* dst, const T* src, size_t n) { return n ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess; }
-template <typename T> hipError_t upload_blocking(DevBuf<T>& dst, const T* src, size_t n) {
-	const hipError_t e = dst.reserve(std::max<size_t>(n, 1));
-	return e != hipSuccess ? e : upload_blocking(dst.p, src, n);
-}
-template <typename D, typename T> hipError_t upload_blocking(D&& dst, const std::vector<T>& src) { return upload_blocking(dst, src.data(), src.size()); } // D: DevBuf<T>& or T*
-
-template <typename T> hipError_t upload_on_stream(T* dst, const T* src, size_t n, hipStream_t stream) { return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess; }
-template <typename T> hipError_t upload_on_stream(DevBuf<T>& dst, const T* src, size_t n, hipStream_t stream) {
-	const hipError_t e = dst.reserve(std::max<size_t>(n, 1));
-	return e != hipSuccess ? e : upload_on_stream(dst.p, src, n, stream);
-}
-template <typename D, typename T> hipError_t upload_on_stream(D&& dst, const std::vector<T>& src, hipStream_t stream) { return upload_on_stream(dst, src.data(), src.size(), stream); }
-
-// device -> host on the stream, skipped for a null `dst`; the host array is valid after the caller's next synchronize of `stream`
-template <typename T> hipError_t read_back(T* dst, const T* src, size_t n, hipStream_t stream) { return n && dst ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess; }
-
-// device -> device: the blocking kind under upload_blocking's precondition, the on-stream kind ordered by the stream
-template <typename T> hipError_t device_copy_blocking(T* dst, const T* src, size_t n) { return n ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice) : hipSuccess; }
-template <typename T> hipError_t device_copy_on_stream(T* dst, const T* src, size_t n, hipStream_t stream) { return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, stream) : hipSuccess; }
-
 struct CullView {
 	DevBuf<int32_t> out;      // raw result: [n_frusta][out_total], one window per output shard
 	DevBuf<uint32_t> counts;  // [2][cnt_words] shard counters, double-buffered: the cull kernel clears the half the NEXT cull uses
@@ -727,6 +693,99 @@ int cull_view_consolidate(LmxContext* ctx, CullView& v); // + one contiguous id 
 		hipError_t e_ = hipSetDevice((ctx)->device);                                                                   \
 		if (e_ != hipSuccess) return lmx::fail(ctx, LMX_ERR_NO_DEVICE, "hipSetDevice(%d): %s", (ctx)->device, hipGetErrorString(e_)); \
 	} while (0)
+
+// Copies between host arrays and device buffers, counted in ELEMENTS: source and destination have one element type (cast at the call
+// site where a caller's array is declared otherwise). All return hipError_t for the caller's LMX_HIP; an empty copy issues no HIP call.
+//
+// Ordering: LmxContext::stream may be a caller's non-blocking stream, and a blocking hipMemcpy is NOT ordered behind such a stream.
+// A blocking copy into a buffer that an enqueued kernel may still read therefore needs a hipStreamSynchronize(ctx->stream) in front
+// of it. An on-stream copy is ordered by the stream, but returns before a pageable source has been read: the caller's array must
+// outlive a synchronize behind it. upload_settled below is that pair of synchronizes around one table; an entry point that replaces several
+// tables writes the pair out once around its copies.
+//
+// A DevBuf destination is reserved for max(n, 1) elements first (launches want a non-null pointer for an empty table); a pointer
+// destination is copied to as it is. DevBuf::reserve frees the old allocation when it grows: the contents are lost, the pointer
+// changes, and a kernel still reading the old one must have finished - the same synchronize, in front of the reserve.
+
+// precondition: the stream whose kernels use `dst` was synchronized
+template <typename T> hipError_t upload_blocking(T* dst, const T* src, size_t n) { return n ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess; }
+template <typename T> hipError_t upload_blocking(DevBuf<T>& dst, const T* src, size_t n) {
+	const hipError_t e = dst.reserve(std::max<size_t>(n, 1));
+	return e != hipSuccess ? e : upload_blocking(dst.p, src, n);
+}
+template <typename D, typename T> hipError_t upload_blocking(D&& dst, const std::vector<T>& src) { return upload_blocking(dst, src.data(), src.size()); } // D: DevBuf<T>& or T*
+
+template <typename T> hipError_t upload_on_stream(T* dst, const T* src, size_t n, hipStream_t stream) { return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess; }
+template <typename T> hipError_t upload_on_stream(DevBuf<T>& dst, const T* src, size_t n, hipStream_t stream) {
+	const hipError_t e = dst.reserve(std::max<size_t>(n, 1));
+	return e != hipSuccess ? e : upload_on_stream(dst.p, src, n, stream);
+}
+template <typename D, typename T> hipError_t upload_on_stream(D&& dst, const std::vector<T>& src, hipStream_t stream) { return upload_on_stream(dst, src.data(), src.size(), stream); }
+
+// device -> host on the stream, skipped for a null `dst`; the host array is valid after the caller's next synchronize of `stream`
+template <typename T> hipError_t read_back(T* dst, const T* src, size_t n, hipStream_t stream) { return n && dst ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess; }
+
+// device -> device: the blocking kind under upload_blocking's precondition, the on-stream kind ordered by the stream
+template <typename T> hipError_t device_copy_blocking(T* dst, const T* src, size_t n) { return n ? hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice) : hipSuccess; }
+template <typename T> hipError_t device_copy_on_stream(T* dst, const T* src, size_t n, hipStream_t stream) { return n ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, stream) : hipSuccess; }
+
+// ---- the host side of a pass: a new unit takes its table uploads, read-outs, guards and transform source from here -------
+
+// A table replaced as a whole: the stream drains (a queued kernel may still read the old table, and a reserve that grows frees it), the
+// copy goes on the stream, the stream drains again (a pageable source has been read when this returns).
+template <typename T> int upload_settled(LmxContext* ctx, DevBuf<T>& dst, const T* src, size_t n) {
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(dst, src, n, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return LMX_OK;
+}
+
+// device -> host, valid on return (read_back's null guard included: a unit that refuses a null array checks in front)
+template <typename T> int read_now(LmxContext* ctx, T* dst, const T* src, size_t n) {
+	LMX_HIP(ctx, read_back(dst, src, n, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return LMX_OK;
+}
+
+// The read-out of a run's output: `used` elements are what the run left, `room` what the buffer holds - used again, or with a guard behind
+// it n + guard, and a larger array then also gets what lies behind the run's output up to the end of the guard.
+template <typename T> int read_out(LmxContext* ctx, T* out, size_t cap, const T* src, size_t used, size_t room, const char* what) {
+	if (cap < used) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu %s", used, what);
+	return read_now(ctx, out, src, std::min(cap, room));
+}
+
+// A guarded output holds `guard` elements behind the n a kernel may write: reserved with them (n + guard), filled here, never written by
+// a kernel, read back by a read_out with room = n + guard. The fill is a stream operation: it keeps its place behind the reserves of
+// its entry point.
+constexpr int GUARD_FILL = 0xA5;
+template <typename T> hipError_t fill_guard(T* behind, size_t guard, hipStream_t stream) { return hipMemsetAsync(behind, GUARD_FILL, guard * sizeof(T), stream); }
+
+// The entity transforms of a pass, as lmx_entity_tr.h reads them from the pass's device struct: the world hierarchy's arrays when
+// lmx_draw_bind_world is on, otherwise the table of lmx_draw_set_transforms (a non-null pointer selects it; n_tr == 0 reads zeros).
+template <typename D> int bind_entity_transforms(LmxContext* ctx, D& d) {
+	DrawState& ds = ctx->draw;
+	WorldState& w = ctx->world;
+	if (ds.use_world) {
+		if (!w.n) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_draw_bind_world: no world hierarchy built");
+		d.wpx = w.pos[3].p; d.wpy = w.pos[4].p; d.wpz = w.pos[5].p; d.wrot = w.rot[1].p; d.wsx = w.scl[3].p; d.wsy = w.scl[4].p; d.wsz = w.scl[5].p;
+		d.slot_of_entity = w.d_slot_of_entity.p; d.n_world = w.n;
+	} else {
+		if (!ds.d_tr.p) LMX_HIP(ctx, ds.d_tr.reserve(1));
+		d.tr = ds.d_tr.p; d.n_tr = ds.n_tr;
+	}
+	return LMX_OK;
+}
+
+// A caller's entity list and its length where a pass reads them: d_list <- entities[0, n), *d_count <- n by way of `n_kept`, a member
+// that outlives the copy.
+inline int upload_list(LmxContext* ctx, DevBuf<int32_t>& d_list, const int32_t* entities, uint32_t n, uint32_t* d_count, uint32_t& n_kept) {
+	n_kept = n;
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(d_list, entities, n, ctx->stream));
+	LMX_HIP(ctx, upload_on_stream(d_count, &n_kept, 1, ctx->stream));
+	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return LMX_OK;
+}
 
 struct ProfScope { // records HIP events around one launch on the launch stream when profiling is enabled
 	LmxContext* ctx;
