@@ -419,6 +419,25 @@ SYMBOLS = {
     "lmx_grass_counts": (_ci, [_vp, _vp, _u32]),
     "lmx_grass_write_instances": (_ci, [_vp, _u32, _vp, _u32]),
     "lmx_grass_device_outputs": (_ci, [_vp, _vp]),
+    "lmx_voxels_grid": (_ci, [_vp, _vp, _u32, _vp]),
+    "lmx_voxels_rng_skip": (_ci, [_u32, _u32, C.c_uint64, C.POINTER(_u32), C.POINTER(_u32)]),
+    "lmx_voxels_create": (_ci, [_vp, C.POINTER(_vp)]),
+    "lmx_voxels_destroy": (None, [_vp]),
+    "lmx_voxels_set": (_ci, [_vp, _vp]),
+    "lmx_voxels_begin_raster": (_ci, [_vp, _vp, _vp, _u32]),
+    "lmx_voxels_raster": (_ci, [_vp, _vp, _u32, _u32, _vp, _u32, _u32]),
+    "lmx_voxels_voxelize": (_ci, [_vp, _vp, _u32, _u32]),
+    "lmx_voxels_compute_ao": (_ci, [_vp, _u32, _u32, _u32]),
+    "lmx_voxels_rng_state": (_ci, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "lmx_voxels_blur_ao": (_ci, [_vp]),
+    "lmx_voxels_set_option": (_ci, [_vp, _ci, _ci]),
+    "lmx_voxels_sample": (_ci, [_vp, _vp, _u32, _vp, _vp]),
+    "lmx_voxels_sample_ao": (_ci, [_vp, _vp, _u32, _vp, _vp]),
+    "lmx_voxels_bake_vertex_ao": (_ci, [_vp, _vp, _u32, _u32, _f32, _vp]),
+    "lmx_voxels_info": (_ci, [_vp, _vp]),
+    "lmx_voxels_read": (_ci, [_vp, _vp, _u32]),
+    "lmx_voxels_read_ao": (_ci, [_vp, _vp, _u32]),
+    "lmx_voxels_device_outputs": (_ci, [_vp, _vp]),
     "lmx_version": (C.c_char_p, []),
 }
 
@@ -2224,4 +2243,150 @@ class Grass:
     def deviceOutputs(self) -> LmxGrassDevice:
         d = LmxGrassDevice()
         self.ctx.check(self.lib.lmx_grass_device_outputs(self.h, C.byref(d)))
+        return d
+
+
+# ---- Voxels (renderer/voxels.cpp) ---------------------------------------------------------------------------------------
+VOXELS_INFO = np.dtype([("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3), ("voxel_size", "<f4"), ("resolution", "<i4", 3)])  # LmxVoxelsInfo
+VOXEL_BLOCK, VOXEL_AO_LDS_WORDS = 256, 10240  # lmx_voxels.h (tests/test_isa_voxel_kernels.py holds them to the compiled kernels)
+VOXEL_RNG_M_U, VOXEL_RNG_M_V = 36969 * 65536 - 1, 18000 * 65536 - 1
+VOXELS_OPT_AO_LDS = 0  # LMX_VOXELS_OPT_AO_LDS
+
+
+class LmxVoxelsMesh(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("stride_bytes", _u32), ("n_vertices", _u32), ("indices", C.c_void_p), ("index_bytes", _u32), ("index_count", _u32)]
+
+
+class LmxVoxelsDevice(C.Structure):
+    _fields_ = [("d_voxels", C.c_void_p), ("d_ao", C.c_void_p), ("n_cells", _u32), ("pad", _u32)]
+
+
+def voxels_grid(aabb_min, aabb_max, max_res: int) -> np.ndarray:
+    """Voxels::beginRaster's arithmetic on the host (lmx_voxels_grid): one VOXELS_INFO record. Needs no device."""
+    lib = load_library()
+    out = np.zeros(1, VOXELS_INFO)
+    rc = lib.lmx_voxels_grid(_ptr(_f32x3(aabb_min)), _ptr(_f32x3(aabb_max)), max_res, _ptr(out))
+    if rc != 0:
+        raise LumixError(rc, "lmx_voxels_grid refused the box")
+    return out[0]
+
+
+def voxels_rng_skip(u: int, v: int, n: int):
+    """The generator's halves n draws behind (u, v) (lmx_voxels_rng_skip). Needs no device."""
+    lib = load_library()
+    uo, vo = _u32(), _u32()
+    rc = lib.lmx_voxels_rng_skip(u, v, n, C.byref(uo), C.byref(vo))
+    if rc != 0:
+        raise LumixError(rc, "lmx_voxels_rng_skip")
+    return uo.value, vo.value
+
+
+def _voxel_mesh(positions, indices):
+    """(positions: float32 (n, >= 3) rows - any row stride -, indices: uint16 or uint32) -> (LmxVoxelsMesh, the arrays it points into)"""
+    p = np.asarray(positions)
+    assert p.dtype == np.float32 and p.ndim == 2 and p.shape[1] >= 3 and (len(p) == 0 or p.strides[1] == 4), "positions: float32 rows"
+    i = np.ascontiguousarray(indices)
+    assert i.dtype in (np.uint16, np.uint32), "indices: uint16 or uint32"
+    i = i.reshape(-1)
+    stride = p.strides[0] if len(p) else 12
+    return LmxVoxelsMesh(p.ctypes.data if len(p) else None, stride, len(p), i.ctypes.data if len(i) else None, i.dtype.itemsize, len(i)), (p, i)
+
+
+class Voxels:
+    """Voxels of renderer/voxels.cpp on the device (lmx_voxels_*): raster, computeAO, blurAO, the lookups and the importer's vertex bake."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(self.lib.lmx_voxels_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.lib.lmx_voxels_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set(self, src: "Voxels"):
+        self.ctx.check(self.lib.lmx_voxels_set(self.h, src.h))
+
+    def beginRaster(self, aabb_min, aabb_max, max_res: int):
+        self.ctx.check(self.lib.lmx_voxels_begin_raster(self.h, _ptr(_f32x3(aabb_min)), _ptr(_f32x3(aabb_max)), max_res))
+
+    def raster(self, positions, indices):
+        m, keep = _voxel_mesh(positions, indices)
+        self.ctx.check(self.lib.lmx_voxels_raster(self.h, m.positions, m.stride_bytes, m.n_vertices, m.indices, m.index_bytes, m.index_count))
+
+    def voxelize(self, meshes, max_res: int):
+        """meshes: a list of (positions, indices)"""
+        recs = (LmxVoxelsMesh * max(len(meshes), 1))()
+        keep = []
+        for k, (p, i) in enumerate(meshes):
+            recs[k], arrays = _voxel_mesh(p, i)
+            keep.append(arrays)
+        self.ctx.check(self.lib.lmx_voxels_voxelize(self.h, C.cast(recs, C.c_void_p), len(meshes), max_res))
+
+    def computeAO(self, ray_count: int, seed_u: int, seed_v: int):
+        self.ctx.check(self.lib.lmx_voxels_compute_ao(self.h, ray_count, seed_u, seed_v))
+
+    def rngState(self):
+        u, v = _u32(), _u32()
+        self.ctx.check(self.lib.lmx_voxels_rng_state(self.h, C.byref(u), C.byref(v)))
+        return u.value, v.value
+
+    def blurAO(self):
+        self.ctx.check(self.lib.lmx_voxels_blur_ao(self.h))
+
+    def setOption(self, option: int, value: int):
+        self.ctx.check(self.lib.lmx_voxels_set_option(self.h, option, value))
+
+    def sample(self, points, fill: int = 0xEE):
+        """-> (voxel bytes, inside flags); a byte keeps `fill` where the point lies outside"""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        out, inside = np.full(len(p), fill, np.uint8), np.zeros(len(p), np.uint8)
+        self.ctx.check(self.lib.lmx_voxels_sample(self.h, _ptr(p) if len(p) else None, len(p), _ptr(out), _ptr(inside)))
+        return out, inside
+
+    def sampleAO(self, points, fill: float = -7.0):
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        out, inside = np.full(len(p), fill, np.float32), np.zeros(len(p), np.uint8)
+        self.ctx.check(self.lib.lmx_voxels_sample_ao(self.h, _ptr(p) if len(p) else None, len(p), _ptr(out), _ptr(inside)))
+        return out, inside
+
+    def bakeVertexAO(self, positions, min_ao: float, fill: int = 0xEE) -> np.ndarray:
+        p = np.asarray(positions)
+        assert p.dtype == np.float32 and p.ndim == 2 and p.shape[1] >= 3 and (len(p) == 0 or p.strides[1] == 4)
+        out = np.full(len(p), fill, np.uint8)
+        self.ctx.check(self.lib.lmx_voxels_bake_vertex_ao(self.h, p.ctypes.data if len(p) else None, p.strides[0] if len(p) else 12, len(p), min_ao, _ptr(out)))
+        return out
+
+    def info(self) -> np.ndarray:
+        out = np.zeros(1, VOXELS_INFO)
+        self.ctx.check(self.lib.lmx_voxels_info(self.h, _ptr(out)))
+        return out[0]
+
+    def _cells(self) -> int:
+        r = self.info()["resolution"]
+        return int(r[0]) * int(r[1]) * int(r[2])
+
+    def read(self) -> np.ndarray:
+        out = np.zeros(max(self._cells(), 1), np.uint8)
+        self.ctx.check(self.lib.lmx_voxels_read(self.h, _ptr(out), len(out)))
+        return out[: self._cells()]
+
+    def readAO(self) -> np.ndarray:
+        out = np.zeros(max(self._cells(), 1), np.float32)
+        self.ctx.check(self.lib.lmx_voxels_read_ao(self.h, _ptr(out), len(out)))
+        return out[: self._cells()]
+
+    def deviceOutputs(self) -> LmxVoxelsDevice:
+        d = LmxVoxelsDevice()
+        self.ctx.check(self.lib.lmx_voxels_device_outputs(self.h, C.byref(d)))
         return d
