@@ -438,6 +438,20 @@ SYMBOLS = {
     "lmx_voxels_read": (_ci, [_vp, _vp, _u32]),
     "lmx_voxels_read_ao": (_ci, [_vp, _vp, _u32]),
     "lmx_voxels_device_outputs": (_ci, [_vp, _vp]),
+    "lmx_probes_batch_bytes": (_ci, [_u32, _u32, C.POINTER(C.c_uint64)]),
+    "lmx_probes_create": (_ci, [_vp, C.POINTER(_vp)]),
+    "lmx_probes_destroy": (None, [_vp]),
+    "lmx_probes_set_cubemaps": (_ci, [_vp, _u32, _u32, _vp]),
+    "lmx_probes_sh_run": (_ci, [_vp]),
+    "lmx_probes_mips_run": (_ci, [_vp]),
+    "lmx_probes_read_sh": (_ci, [_vp, _vp, _u32]),
+    "lmx_probes_read_mips": (_ci, [_vp, _vp, C.c_uint64]),
+    "lmx_probes_device_outputs": (_ci, [_vp, _vp]),
+    "lmx_probes_ggx_samples": (_ci, [_u32, _vp]),
+    "lmx_probes_filter_run": (_ci, [_vp]),
+    "lmx_probes_sample": (_ci, [_vp, _u32, _u32, _vp, _vp, _vp]),
+    "lmx_probes_read_filtered": (_ci, [_vp, _vp, C.c_uint64]),
+    "lmx_probes_read_rgbm": (_ci, [_vp, _vp, C.c_uint64]),
     "lmx_version": (C.c_char_p, []),
 }
 
@@ -2389,4 +2403,153 @@ class Voxels:
     def deviceOutputs(self) -> LmxVoxelsDevice:
         d = LmxVoxelsDevice()
         self.ctx.check(self.lib.lmx_voxels_device_outputs(self.h, C.byref(d)))
+        return d
+
+
+# ---- Probe bake (EnvironmentProbePlugin, renderer/editor/render_plugins.cpp) -------------------------------------------
+PROBES_MAX_BATCH_BYTES = 1 << 30  # LMX_PROBES_MAX_BATCH_BYTES
+PROBE_BLOCK, SH_CHUNK, SH_STRIDE = 256, 256, 29  # lmx_probes.h (tests/test_isa_probe_kernels.py holds them to the compiled kernels)
+
+
+class LmxProbesDevice(C.Structure):
+    _fields_ = [("d_cubemaps", C.c_void_p), ("d_sh", C.c_void_p), ("d_mips", C.c_void_p), ("d_filtered", C.c_void_p), ("d_rgbm", C.c_void_p), ("n", _u32), ("size", _u32)]
+
+
+def probes_batch_bytes(n: int, size: int) -> int:
+    """The bytes of a batch of n cubemaps of one size, with lmx_probes_set_cubemaps' refusals (lmx_probes_batch_bytes). Needs no device."""
+    lib = load_library()
+    out = C.c_uint64()
+    rc = lib.lmx_probes_batch_bytes(n, size, C.byref(out))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_probes_batch_bytes refused {n} cubemaps of size {size}")
+    return out.value
+
+
+def probe_mip_texels(size: int) -> int:
+    """texels of mips 1 .. log2 size of one cubemap"""
+    return sum(6 * (size >> m) ** 2 for m in range(1, size.bit_length()))
+
+
+def probes_ggx_samples(level: int) -> np.ndarray:
+    """ImportanceSampleGGX's tangent-space H of the 128 Hammersley points at roughness level / 4 (lmx_probes_ggx_samples). Needs no device."""
+    lib = load_library()
+    out = np.zeros((128, 3), np.float32)
+    rc = lib.lmx_probes_ggx_samples(level, _ptr(out))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_probes_ggx_samples refused level {level}")
+    return out
+
+
+PROBE_LEVELS = 5  # roughness_levels
+
+
+class ProbeBaker:
+    """The probe bake on the device (lmx_probes_*): SphericalHarmonics::compute, and the reflection probe's mip chain, radiance levels and
+    RGBM bytes, for a batch of cubemaps."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(self.lib.lmx_probes_create(ctx.h, C.byref(h)))
+        self.h = h
+        self.n = self.size = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.lib.lmx_probes_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setCubemaps(self, rgba):
+        """rgba: float32 (n, 6, S, S, 4)"""
+        a = np.ascontiguousarray(rgba, np.float32)
+        assert a.ndim == 5 and a.shape[1] == 6 and a.shape[2] == a.shape[3] and a.shape[4] == 4, "cubemaps: (n, 6, S, S, 4)"
+        self.ctx.check(self.lib.lmx_probes_set_cubemaps(self.h, a.shape[0], a.shape[2], _ptr(a) if a.size else None))
+        self.n, self.size = a.shape[0], a.shape[2]
+
+    def shRun(self):
+        self.ctx.check(self.lib.lmx_probes_sh_run(self.h))
+
+    def readSH(self) -> np.ndarray:
+        """-> float32 (n, 9, 3): LmxEnvProbe::sh_coefs per probe"""
+        out = np.zeros((max(self.n, 1), 9, 3), np.float32)
+        self.ctx.check(self.lib.lmx_probes_read_sh(self.h, _ptr(out), len(out)))
+        return out[: self.n]
+
+    def mipsRun(self):
+        self.ctx.check(self.lib.lmx_probes_mips_run(self.h))
+
+    def readMips(self):
+        """-> per probe a list of float32 (6, s, s, 4), mips 1 .. log2 S"""
+        per = 4 * probe_mip_texels(self.size)
+        out = np.zeros(max(self.n * per, 1), np.float32)
+        self.ctx.check(self.lib.lmx_probes_read_mips(self.h, _ptr(out), out.size))
+        res = []
+        for p in range(self.n):
+            at, mips = p * per, []
+            for m in range(1, self.size.bit_length()):
+                s = self.size >> m
+                mips.append(out[at: at + 24 * s * s].reshape(6, s, s, 4))
+                at += 24 * s * s
+            res.append(mips)
+        return res
+
+    def filterRun(self):
+        self.ctx.check(self.lib.lmx_probes_filter_run(self.h))
+
+    def sample(self, probe: int, dirs, lods) -> np.ndarray:
+        """the cube sampler alone: dirs (k, 3), lods (k,) -> float32 (k, 3)"""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        l = np.ascontiguousarray(lods, np.float32).reshape(-1)
+        assert len(d) == len(l)
+        out = np.zeros((max(len(d), 1), 3), np.float32)
+        self.ctx.check(self.lib.lmx_probes_sample(self.h, probe, len(d), _ptr(d) if len(d) else None, _ptr(l) if len(l) else None, _ptr(out)))
+        return out[: len(d)]
+
+    def _level_texels(self) -> int:
+        return sum(6 * (self.size >> k) ** 2 for k in range(PROBE_LEVELS))
+
+    def readFiltered(self):
+        """-> per probe a list of float32 (6, s, s, 4), levels 0 .. 4"""
+        per = 4 * self._level_texels()
+        out = np.zeros(max(self.n * per, 1), np.float32)
+        self.ctx.check(self.lib.lmx_probes_read_filtered(self.h, _ptr(out), out.size))
+        res = []
+        for p in range(self.n):
+            at, levels = p * per, []
+            for k in range(PROBE_LEVELS):
+                s = self.size >> k
+                levels.append(out[at: at + 24 * s * s].reshape(6, s, s, 4))
+                at += 24 * s * s
+            res.append(levels)
+        return res
+
+    def readRGBM(self):
+        """-> per probe, per face a list of uint8 (s, s, 4), levels 0 .. 4: the images of TextureCompressor::Input::add(face, 0, level)"""
+        per = 4 * self._level_texels()
+        out = np.zeros(max(self.n * per, 1), np.uint8)
+        self.ctx.check(self.lib.lmx_probes_read_rgbm(self.h, _ptr(out), out.size))
+        res = []
+        for p in range(self.n):
+            at, faces = p * per, []
+            for f in range(6):
+                levels = []
+                for k in range(PROBE_LEVELS):
+                    s = self.size >> k
+                    levels.append(out[at: at + 4 * s * s].reshape(s, s, 4))
+                    at += 4 * s * s
+                faces.append(levels)
+            res.append(faces)
+        return res
+
+    def deviceOutputs(self) -> LmxProbesDevice:
+        d = LmxProbesDevice()
+        self.ctx.check(self.lib.lmx_probes_device_outputs(self.h, C.byref(d)))
         return d
