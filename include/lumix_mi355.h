@@ -1387,6 +1387,66 @@ LMX_API int lmx_probes_read_rgbm(LmxProbeBaker* pb, uint8_t* out, uint64_t cap_b
 /* Device pointers for GPU consumers, valid until the next set_cubemaps or run; stream-ordered */
 LMX_API int lmx_probes_device_outputs(LmxProbeBaker* pb, LmxProbesDevice* out);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * Texture compressor: TextureCompressor::compress's per-block loops (renderer/editor/render_plugins.cpp:226,261,291) for a batch of RGBA8
+ * images (lumixengine_amd/host/gpu_texture_compressor.h; mip generation and coverage scaling stay with the engine: DESIGN.md 7). A BC1 block is
+ * rgbcx's encoder (external/rgbcx/rgbcx.h) in its exhaustive mode - level 10's flow (the solid-block shortcut, the initial endpoints, two
+ * least-squares passes, check-2 selectors) with all 969 (3 colours: 153) selector histograms tried instead of the 20 (8) of a trained
+ * table, in lexicographic order, the lowest index among the trials of least error winning: per block never a larger error than level 10
+ * (DESIGN.md 4.23). BC4 / BC5 and BC3's alpha half are encode_bc4, byte for byte.
+ *   LMX_TEX_BC1  8 bytes per block, 3-colour blocks allowed (compressBC1)
+ *   LMX_TEX_BC3  16 bytes: BC4 of channel 3, then a 4-colour BC1 block (compressBC3)
+ *   LMX_TEX_BC4  8 bytes: channel 0
+ *   LMX_TEX_BC5  16 bytes: BC4 of channel 0, BC4 of channel 1 (compressBC5)
+ * Input: n images of any sizes >= 1, RGBA8, tightly packed one behind the other. Output: per image ((w + 3) >> 2) * ((h + 3) >> 2) blocks in
+ * row-major block order, images in input order: for a batch in compress()'s slice, face, mip order the payload of the .lbc file behind its
+ * header. Texels of a block outside its image are 0, 0, 0, 0 in every format.
+ * Refusals: LMX_ERR_INVALID_ARGUMENT for n == 0, a zero dimension, an unknown format, null pointers, device pixels that are no multiple of
+ * 4 bytes; LMX_ERR_CAPACITY for a batch above LMX_TEXCOMP_MAX_BATCH_BYTES of pixels and a read into too small an array; LMX_ERR_NOT_BUILT
+ * for a run before a set, a read before a run (a set drops the blocks of the batch before), set_from_probes before filter_run.
+ * ------------------------------------------------------------------------------------------------------------------------------------ */
+typedef struct LmxTexCompressor LmxTexCompressor;
+#define LMX_TEXCOMP_MAX_BATCH_BYTES (1ull << 30)
+enum { LMX_TEX_BC1 = 0, LMX_TEX_BC3 = 1, LMX_TEX_BC4 = 2, LMX_TEX_BC5 = 3 };
+typedef struct LmxTexImage {
+	uint32_t w, h;
+} LmxTexImage;
+typedef struct LmxTexCompDevice {
+	const uint8_t* d_rgba;   /* the batch's pixels (the compressor's copy, the caller's or the probe baker's) */
+	const uint8_t* d_blocks; /* NULL before a run */
+	uint64_t bytes;          /* of d_blocks */
+	uint32_t n_images, n_blocks;
+	int32_t format;          /* of the last run; -1 before */
+} LmxTexCompDevice;
+/* Host utilities (no context, no device): the bytes a run of `format` leaves for this batch, with the sets' refusals; */
+LMX_API int lmx_texcomp_output_bytes(uint32_t n, const LmxTexImage* descs, int format, uint64_t* out);
+/* the blocks the search kernel's largest grid takes in one round - one per wave, 1024 workgroups of four waves: 4096; a batch of more blocks
+ * is walked with that stride; */
+LMX_API uint32_t lmx_texcomp_blocks_per_round(void);
+/* the tables a compressor generates at creation, as the kernels read them (22432 bytes): 969 + 153 histograms of {f1 | f2 << 8 | f3 << 16 |
+ * any16 << 24, iz00, iz10, iz11}, the 32 + 64 midpoints, the four single-colour match tables of 256 x (hi | lo << 8 | e << 16); */
+LMX_API int lmx_texcomp_tables(void* out, uint64_t cap_bytes);
+/* the place of a histogram (colours = 4 or 3 counts that sum to 16) in the lexicographic order the search tries them in; */
+LMX_API int lmx_texcomp_hist_index(uint32_t colours, const uint8_t* hist, uint32_t* out);
+/* the kernels' arithmetic run on the host, one block after the other: rgba = n_blocks x 16 pixels, out = n_blocks blocks of `format`,
+ * err (may be NULL) = the BC1 half's squared error as the encoder counts it (0 for a solid block and for BC4 / BC5). */
+LMX_API int lmx_texcomp_encode_host(int format, uint32_t n_blocks, const uint8_t* rgba, uint8_t* out, uint32_t* err);
+LMX_API int lmx_texcomp_create(LmxContext* ctx, LmxTexCompressor** out);
+LMX_API void lmx_texcomp_destroy(LmxTexCompressor* tc);
+/* copies the batch to the device before it returns */
+LMX_API int lmx_texcomp_set_images(LmxTexCompressor* tc, uint32_t n, const LmxTexImage* descs, const uint8_t* rgba);
+/* the same from a device pointer: stream-ordered, the pixels are not copied and must stay until the run has finished */
+LMX_API int lmx_texcomp_set_images_device(LmxTexCompressor* tc, uint32_t n, const LmxTexImage* descs, const uint8_t* d_rgba);
+/* the RGBM bytes of a finished lmx_probes_filter_run as the batch: per probe, per face, levels 0 .. 4 - what saveCubemap hands the compressor
+ * with has_alpha = is_cubemap = true; a following run(LMX_TEX_BC3) leaves each probe's .lbc payload. No host wait. */
+LMX_API int lmx_texcomp_set_from_probes(LmxTexCompressor* tc, LmxProbeBaker* pb);
+/* Async: no host synchronisation */
+LMX_API int lmx_texcomp_run(LmxTexCompressor* tc, int format);
+/* waits for the stream; cap_bytes >= lmx_texcomp_output_bytes */
+LMX_API int lmx_texcomp_read(LmxTexCompressor* tc, uint8_t* out, uint64_t cap_bytes);
+/* Device pointers for GPU consumers, valid until the next set or run; stream-ordered */
+LMX_API int lmx_texcomp_device_outputs(LmxTexCompressor* tc, LmxTexCompDevice* out);
+
 LMX_API const char* lmx_version(void);
 
 #ifdef __cplusplus

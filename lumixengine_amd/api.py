@@ -452,6 +452,19 @@ SYMBOLS = {
     "lmx_probes_sample": (_ci, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "lmx_probes_read_filtered": (_ci, [_vp, _vp, C.c_uint64]),
     "lmx_probes_read_rgbm": (_ci, [_vp, _vp, C.c_uint64]),
+    "lmx_texcomp_output_bytes": (_ci, [_u32, _vp, _ci, C.POINTER(C.c_uint64)]),
+    "lmx_texcomp_blocks_per_round": (_u32, []),
+    "lmx_texcomp_tables": (_ci, [_vp, C.c_uint64]),
+    "lmx_texcomp_hist_index": (_ci, [_u32, _vp, C.POINTER(_u32)]),
+    "lmx_texcomp_encode_host": (_ci, [_ci, _u32, _vp, _vp, _vp]),
+    "lmx_texcomp_create": (_ci, [_vp, C.POINTER(_vp)]),
+    "lmx_texcomp_destroy": (None, [_vp]),
+    "lmx_texcomp_set_images": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_texcomp_set_images_device": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_texcomp_set_from_probes": (_ci, [_vp, _vp]),
+    "lmx_texcomp_run": (_ci, [_vp, _ci]),
+    "lmx_texcomp_read": (_ci, [_vp, _vp, C.c_uint64]),
+    "lmx_texcomp_device_outputs": (_ci, [_vp, _vp]),
     "lmx_version": (C.c_char_p, []),
 }
 
@@ -2552,4 +2565,138 @@ class ProbeBaker:
     def deviceOutputs(self) -> LmxProbesDevice:
         d = LmxProbesDevice()
         self.ctx.check(self.lib.lmx_probes_device_outputs(self.h, C.byref(d)))
+        return d
+
+
+# ---- texture compressor (lmx_texcomp_*) ---------------------------------------------------------------------------------------------------
+TEX_BC1, TEX_BC3, TEX_BC4, TEX_BC5 = 0, 1, 2, 3
+TEX_BLOCK_BYTES = {TEX_BC1: 8, TEX_BC3: 16, TEX_BC4: 8, TEX_BC5: 16}
+TEXCOMP_GUARD_BYTES = 256  # behind the blocks of a run (a larger read returns them: 0xA5 each)
+
+
+class LmxTexCompDevice(C.Structure):
+    _fields_ = [("d_rgba", C.c_void_p), ("d_blocks", C.c_void_p), ("bytes", C.c_uint64), ("n_images", _u32), ("n_blocks", _u32), ("format", C.c_int32)]
+
+
+# lmx_texcomp_tables' bytes: TcTables of csrc/lmx_texcomp.h
+_TEX_HIST = np.dtype([("f", "<u4"), ("iz00", "<f4"), ("iz10", "<f4"), ("iz11", "<f4")])
+TEX_TABLES = np.dtype([("hist4", _TEX_HIST, (969,)), ("hist3", _TEX_HIST, (153,)), ("mid5", "<f4", (32,)), ("mid6", "<f4", (64,)), ("match", "<u4", (4, 256))])
+
+
+def _tex_descs(sizes) -> np.ndarray:
+    d = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint32).reshape(-1, 2))  # rows of (w, h)
+    return d
+
+
+def texcomp_output_bytes(sizes, fmt: int) -> int:
+    """The bytes a run of `fmt` leaves for images of these (w, h), with the sets' refusals (lmx_texcomp_output_bytes). Needs no device."""
+    lib = load_library()
+    d = _tex_descs(sizes)
+    out = C.c_uint64()
+    rc = lib.lmx_texcomp_output_bytes(len(d), _ptr(d) if len(d) else None, fmt, C.byref(out))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_texcomp_output_bytes refused {len(d)} images, format {fmt}")
+    return out.value
+
+
+def texcomp_blocks_per_round() -> int:
+    """The blocks the search kernel's largest grid takes in one round; more are walked with that stride (lmx_texcomp_blocks_per_round). Needs no device."""
+    return int(load_library().lmx_texcomp_blocks_per_round())
+
+
+def texcomp_tables() -> np.ndarray:
+    """The generated tables (lmx_texcomp_tables) as one record of TEX_TABLES. Needs no device."""
+    lib = load_library()
+    out = np.zeros(1, TEX_TABLES)
+    rc = lib.lmx_texcomp_tables(_ptr(out), out.nbytes)
+    if rc != 0:
+        raise LumixError(rc, "lmx_texcomp_tables failed")
+    return out[0]
+
+
+def texcomp_hist_index(hist) -> int:
+    """The place of a histogram of 4 or 3 counts in the order the search tries them in (lmx_texcomp_hist_index). Needs no device."""
+    lib = load_library()
+    h = np.ascontiguousarray(hist, np.uint8)
+    out = _u32()
+    rc = lib.lmx_texcomp_hist_index(len(h), _ptr(h), C.byref(out))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_texcomp_hist_index refused {h.tolist()}")
+    return out.value
+
+
+def texcomp_encode_host(fmt: int, blocks):
+    """The kernels' arithmetic on the host (lmx_texcomp_encode_host): blocks uint8 (n, 16, 4) -> (uint8 (n, bytes per block), uint32 (n,) errors)."""
+    lib = load_library()
+    px = np.ascontiguousarray(blocks, np.uint8).reshape(-1, 16, 4)
+    out = np.zeros((len(px), TEX_BLOCK_BYTES.get(fmt, 16)), np.uint8)
+    err = np.zeros(max(len(px), 1), np.uint32)
+    rc = lib.lmx_texcomp_encode_host(fmt, len(px), _ptr(px) if len(px) else _ptr(err), _ptr(out) if len(px) else _ptr(err), _ptr(err))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_texcomp_encode_host refused format {fmt}")
+    return out, err[: len(px)]
+
+
+class TexCompressor:
+    """TextureCompressor::compress's block loops on the device (lmx_texcomp_*): BC1, BC3, BC4 and BC5 blocks of a batch of RGBA8 images."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(self.lib.lmx_texcomp_create(ctx.h, C.byref(h)))
+        self.h = h
+        self.sizes = np.zeros((0, 2), np.uint32)
+        self.format = -1
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.lib.lmx_texcomp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setImages(self, images):
+        """images: a list of uint8 (h, w, 4)"""
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+        assert all(im.ndim == 3 and im.shape[2] == 4 for im in imgs), "images: (h, w, 4)"
+        d = _tex_descs([(im.shape[1], im.shape[0]) for im in imgs])
+        flat = np.concatenate([im.reshape(-1) for im in imgs]) if imgs else np.zeros(0, np.uint8)
+        self.ctx.check(self.lib.lmx_texcomp_set_images(self.h, len(d), _ptr(d) if len(d) else None, _ptr(flat) if flat.size else None))
+        self.sizes, self.format = d, -1
+
+    def setImagesDevice(self, sizes, d_rgba: int):
+        """sizes: rows of (w, h); d_rgba: a device address of the tightly packed pixels (not copied)"""
+        d = _tex_descs(sizes)
+        self.ctx.check(self.lib.lmx_texcomp_set_images_device(self.h, len(d), _ptr(d) if len(d) else None, C.c_void_p(d_rgba)))
+        self.sizes, self.format = d, -1
+
+    def setFromProbes(self, baker: "ProbeBaker"):
+        self.ctx.check(self.lib.lmx_texcomp_set_from_probes(self.h, baker.h))
+        self.sizes = _tex_descs([(baker.size >> k, baker.size >> k) for _ in range(baker.n) for _ in range(6) for k in range(PROBE_LEVELS)])
+        self.format = -1
+
+    def run(self, fmt: int):
+        self.ctx.check(self.lib.lmx_texcomp_run(self.h, fmt))
+        self.format = fmt
+
+    def blockCounts(self) -> np.ndarray:
+        return ((self.sizes[:, 0] + 3) >> 2) * ((self.sizes[:, 1] + 3) >> 2)
+
+    def read(self, guard: bool = False) -> np.ndarray:
+        """-> uint8 (blocks, bytes per block) of the last run, images one behind the other; guard: (bytes + TEXCOMP_GUARD_BYTES,) with what lies behind"""
+        per = TEX_BLOCK_BYTES.get(self.format, 16)
+        n = int(self.blockCounts().sum()) if self.format >= 0 else 0
+        out = np.zeros(max(n * per, 1) + (TEXCOMP_GUARD_BYTES if guard else 0), np.uint8)
+        self.ctx.check(self.lib.lmx_texcomp_read(self.h, _ptr(out), out.size))
+        return out if guard else out[: n * per].reshape(n, per)
+
+    def deviceOutputs(self) -> LmxTexCompDevice:
+        d = LmxTexCompDevice()
+        self.ctx.check(self.lib.lmx_texcomp_device_outputs(self.h, C.byref(d)))
         return d
