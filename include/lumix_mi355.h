@@ -1389,7 +1389,7 @@ LMX_API int lmx_probes_device_outputs(LmxProbeBaker* pb, LmxProbesDevice* out);
 
 /* ------------------------------------------------------------------------------------------------------------------------------------
  * Texture compressor: TextureCompressor::compress's per-block loops (renderer/editor/render_plugins.cpp:226,261,291) for a batch of RGBA8
- * images (lumixengine_amd/host/gpu_texture_compressor.h; mip generation and coverage scaling stay with the engine: DESIGN.md 7). A BC1 block is
+ * images (lumixengine_amd/host/gpu_texture_compressor.h; the mip chains of generate_mipmaps are further down: DESIGN.md 4.24). A BC1 block is
  * rgbcx's encoder (external/rgbcx/rgbcx.h) in its exhaustive mode - level 10's flow (the solid-block shortcut, the initial endpoints, two
  * least-squares passes, check-2 selectors) with all 969 (3 colours: 153) selector histograms tried instead of the 20 (8) of a trained
  * table, in lexicographic order, the lowest index among the trials of least error winning: per block never a larger error than level 10
@@ -1446,6 +1446,45 @@ LMX_API int lmx_texcomp_run(LmxTexCompressor* tc, int format);
 LMX_API int lmx_texcomp_read(LmxTexCompressor* tc, uint8_t* out, uint64_t cap_bytes);
 /* Device pointers for GPU consumers, valid until the next set or run; stream-ordered */
 LMX_API int lmx_texcomp_device_outputs(LmxTexCompressor* tc, LmxTexCompDevice* out);
+
+/* Mip chains: compress() with generate_mipmaps (render_plugins.cpp:359-401) - computeMip in its three forms, computeCoverage and
+ * scaleCoverage - built where the compressor reads them. A chain is a level-0 image followed by its 1 + log2(max(w, h))
+ * - 1 generated levels, level m of max(w >> m, 1) x max(h >> m, 1) texels; the batch becomes n x levels images in (image, mip) order, so for
+ * level-0 images in slice, face order a run leaves the .lbc payload.
+ *   LMX_TEXMIP_STOCHASTIC  downsampleNormal, bit for bit (sides up to 4096: above, the reference's own index can leave a row)
+ *   LMX_TEXMIP_SRGB        a Mitchell downsample in linear light of sRGB colour; LMX_TEXMIP_LINEAR the same on the bytes as they are.
+ *                          stb_image_resize2's filter with this library's order of sums: every byte within 1 of stbir_resize_uint8_srgb /
+ *                          _linear with STBIR_RGBA on the same source level.
+ *   scale_coverage_ref >= 0: scaleCoverage after every generated level, bit for bit, the wanted coverage taken once from image 0's level 0;
+ *                          level m + 1 is computed from the scaled level m. Where alpha * scale is a NaN the byte written is 0.
+ * Refusals: LMX_ERR_INVALID_ARGUMENT for null pointers, n == 0, a zero side, an unknown mode, device pixels that are no multiple of 4 bytes;
+ * LMX_ERR_CAPACITY for chains above LMX_TEXCOMP_MAX_BATCH_BYTES, a side above 2^24 (texel centres are exact in fp32 up to there), more than
+ * 65535 chains, a stochastic chain with a side above 4096;
+ * LMX_ERR_NOT_BUILT for generate_mips without set_chains, and for read_pixels or run on chains before generate_mips. */
+enum { LMX_TEXMIP_LINEAR = 0, LMX_TEXMIP_SRGB = 1, LMX_TEXMIP_STOCHASTIC = 2 };
+typedef struct LmxTexMipOptions {
+	int32_t mode;             /* LMX_TEXMIP_* */
+	float scale_coverage_ref; /* < 0: no coverage scaling */
+} LmxTexMipOptions;
+/* Host utilities (no context, no device): the levels of a chain (0 for a zero side), and the bytes of n chains of RGBA8 with set_chains' refusals */
+LMX_API uint32_t lmx_texcomp_chain_levels(uint32_t w, uint32_t h);
+LMX_API int lmx_texcomp_chain_bytes(uint32_t n, uint32_t w, uint32_t h, uint64_t* out);
+/* n level-0 images of w x h, tightly packed; each goes to the head of its chain with one strided copy. Copies before it returns; */
+LMX_API int lmx_texcomp_set_chains(LmxTexCompressor* tc, uint32_t n, uint32_t w, uint32_t h, const uint8_t* rgba);
+/* the same from a device pointer: stream-ordered, the pixels are copied on the stream and must stay until that copy has finished. Both forms
+ * wait for the stream first where the chains or their tables need a larger device buffer than the compressor holds (queued kernels may still
+ * use the one that is freed), or where the set before is still being copied; a set of chains no larger than one before does not wait. */
+LMX_API int lmx_texcomp_set_chains_device(LmxTexCompressor* tc, uint32_t n, uint32_t w, uint32_t h, const uint8_t* d_rgba);
+/* Async: no host synchronisation. Levels 1 .. of every chain - one launch per level down to the first whose sides are both at most 32, one
+ * more for all levels behind it; afterwards run / read / device_outputs work on the n x levels images */
+LMX_API int lmx_texcomp_generate_mips(LmxTexCompressor* tc, const LmxTexMipOptions* options);
+/* the chains' RGBA8 (the payload of an uncompressed .lbc); waits for the stream; cap_bytes >= lmx_texcomp_chain_bytes */
+LMX_API int lmx_texcomp_read_pixels(LmxTexCompressor* tc, uint8_t* out, uint64_t cap_bytes);
+/* The chain's arithmetic on the host. The taps of one axis of a filtered level, `in` -> `out` texels (out <= in): `out` records of 64 bytes,
+ * {uint32 n0, n; float c[14]} - source texels n0 .. n0 + n - 1, coefficients normalised; cap_rows >= out; */
+LMX_API int lmx_texmips_coeffs(uint32_t in, uint32_t out, void* rows, uint32_t cap_rows);
+/* whole chains, sequentially: rgba = n level-0 images, out = lmx_texcomp_chain_bytes bytes. */
+LMX_API int lmx_texmips_host(const LmxTexMipOptions* options, uint32_t n, uint32_t w, uint32_t h, const uint8_t* rgba, uint8_t* out);
 
 LMX_API const char* lmx_version(void);
 

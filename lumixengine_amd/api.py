@@ -465,6 +465,14 @@ SYMBOLS = {
     "lmx_texcomp_run": (_ci, [_vp, _ci]),
     "lmx_texcomp_read": (_ci, [_vp, _vp, C.c_uint64]),
     "lmx_texcomp_device_outputs": (_ci, [_vp, _vp]),
+    "lmx_texcomp_chain_levels": (_u32, [_u32, _u32]),
+    "lmx_texcomp_chain_bytes": (_ci, [_u32, _u32, _u32, C.POINTER(C.c_uint64)]),
+    "lmx_texcomp_set_chains": (_ci, [_vp, _u32, _u32, _u32, _vp]),
+    "lmx_texcomp_set_chains_device": (_ci, [_vp, _u32, _u32, _u32, _vp]),
+    "lmx_texcomp_generate_mips": (_ci, [_vp, _vp]),
+    "lmx_texcomp_read_pixels": (_ci, [_vp, _vp, C.c_uint64]),
+    "lmx_texmips_coeffs": (_ci, [_u32, _u32, _vp, _u32]),
+    "lmx_texmips_host": (_ci, [_vp, _u32, _u32, _u32, _vp, _vp]),
     "lmx_version": (C.c_char_p, []),
 }
 
@@ -2637,8 +2645,69 @@ def texcomp_encode_host(fmt: int, blocks):
     return out, err[: len(px)]
 
 
+# mip chains (csrc/lmx_texmips.h)
+TEXMIP_LINEAR, TEXMIP_SRGB, TEXMIP_STOCHASTIC = 0, 1, 2
+TEXMIP_MAX_TAPS = 14
+TEXMIP_ROW = np.dtype([("n0", "<u4"), ("n", "<u4"), ("c", "<f4", (TEXMIP_MAX_TAPS,))])  # lmx_texmips_coeffs' records
+
+
+class LmxTexMipOptions(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("scale_coverage_ref", C.c_float)]
+
+
+def texcomp_chain_levels(w: int, h: int) -> int:
+    """1 + log2(max(w, h)), the levels of a w x h chain (lmx_texcomp_chain_levels). Needs no device."""
+    return int(load_library().lmx_texcomp_chain_levels(w, h))
+
+
+def texcomp_chain_sizes(w: int, h: int):
+    """the (w, h) of every level of a chain"""
+    return [(max(w >> m, 1), max(h >> m, 1)) for m in range(texcomp_chain_levels(w, h))]
+
+
+def texcomp_chain_bytes(n: int, w: int, h: int) -> int:
+    """The bytes of n chains of w x h RGBA8, with set_chains' refusals (lmx_texcomp_chain_bytes). Needs no device."""
+    out = C.c_uint64()
+    rc = load_library().lmx_texcomp_chain_bytes(n, w, h, C.byref(out))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_texcomp_chain_bytes refused {n} chains of {w} x {h}")
+    return out.value
+
+
+def texmips_coeffs(n_in: int, n_out: int) -> np.ndarray:
+    """The taps of one axis of a filtered level (lmx_texmips_coeffs): n_out records of TEXMIP_ROW. Needs no device."""
+    rows = np.zeros(max(n_out, 1), TEXMIP_ROW)
+    rc = load_library().lmx_texmips_coeffs(n_in, n_out, _ptr(rows), len(rows))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_texmips_coeffs refused {n_in} -> {n_out}")
+    return rows[:n_out]
+
+
+def texmips_host(images, mode: int, scale_coverage_ref: float = -1.0) -> np.ndarray:
+    """The chains' arithmetic on the host (lmx_texmips_host): images uint8 (n, h, w, 4) -> uint8 (n, chain bytes)."""
+    px = np.ascontiguousarray(images, np.uint8)
+    assert px.ndim == 4 and px.shape[3] == 4, "images: (n, h, w, 4)"
+    n, h, w = px.shape[:3]
+    out = np.zeros((n, texcomp_chain_bytes(n, w, h) // n), np.uint8)
+    opt = LmxTexMipOptions(mode, scale_coverage_ref)
+    rc = load_library().lmx_texmips_host(C.byref(opt), n, w, h, _ptr(px), _ptr(out))
+    if rc != 0:
+        raise LumixError(rc, f"lmx_texmips_host refused mode {mode}, {n} x {w} x {h}")
+    return out
+
+
+def texcomp_split_chain(chain, w: int, h: int):
+    """one chain's bytes -> its levels, uint8 (h_m, w_m, 4) each"""
+    flat, at, out = np.asarray(chain, np.uint8).reshape(-1), 0, []
+    for lw, lh in texcomp_chain_sizes(w, h):
+        out.append(flat[at: at + 4 * lw * lh].reshape(lh, lw, 4))
+        at += 4 * lw * lh
+    return out
+
+
 class TexCompressor:
-    """TextureCompressor::compress's block loops on the device (lmx_texcomp_*): BC1, BC3, BC4 and BC5 blocks of a batch of RGBA8 images."""
+    """TextureCompressor::compress's block loops on the device (lmx_texcomp_*): BC1, BC3, BC4 and BC5 blocks of a batch of RGBA8 images,
+    and the mip chains of compress() with generate_mipmaps (setChains, generateMips)."""
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
@@ -2680,6 +2749,36 @@ class TexCompressor:
         self.ctx.check(self.lib.lmx_texcomp_set_from_probes(self.h, baker.h))
         self.sizes = _tex_descs([(baker.size >> k, baker.size >> k) for _ in range(baker.n) for _ in range(6) for k in range(PROBE_LEVELS)])
         self.format = -1
+
+    def setChains(self, images):
+        """images: uint8 (n, h, w, 4), the level-0 images in slice, face order; the batch becomes n x levels images in (image, mip) order"""
+        px = np.ascontiguousarray(images, np.uint8)
+        assert px.ndim == 4 and px.shape[3] == 4, "images: (n, h, w, 4)"
+        n, h, w = px.shape[:3]
+        self.ctx.check(self.lib.lmx_texcomp_set_chains(self.h, n, w, h, _ptr(px) if px.size else None))
+        self._chains_set(n, w, h)
+
+    def setChainsDevice(self, n: int, w: int, h: int, d_rgba: int):
+        """d_rgba: a device address of the n tightly packed level-0 images (copied on the stream)"""
+        self.ctx.check(self.lib.lmx_texcomp_set_chains_device(self.h, n, w, h, C.c_void_p(d_rgba)))
+        self._chains_set(n, w, h)
+
+    def _chains_set(self, n, w, h):
+        self.chain = (n, w, h)
+        self.sizes, self.format = _tex_descs(texcomp_chain_sizes(w, h) * n), -1
+
+    def generateMips(self, mode: int, scale_coverage_ref: float = -1.0):
+        opt = LmxTexMipOptions(mode, scale_coverage_ref)
+        self.ctx.check(self.lib.lmx_texcomp_generate_mips(self.h, C.byref(opt)))
+        self.format = -1
+
+    def readPixels(self, guard: bool = False) -> np.ndarray:
+        """-> uint8 (n, chain bytes): every chain's levels one behind the other; guard: (bytes + TEXCOMP_GUARD_BYTES,) with what lies behind"""
+        n, w, h = getattr(self, "chain", (0, 0, 0))
+        total = texcomp_chain_bytes(n, w, h) if n else 0
+        out = np.zeros(max(total, 1) + (TEXCOMP_GUARD_BYTES if guard else 0), np.uint8)
+        self.ctx.check(self.lib.lmx_texcomp_read_pixels(self.h, _ptr(out), out.size))
+        return out if guard else out[:total].reshape(n, total // n)
 
     def run(self, fmt: int):
         self.ctx.check(self.lib.lmx_texcomp_run(self.h, fmt))

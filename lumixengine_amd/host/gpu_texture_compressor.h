@@ -8,8 +8,9 @@
 //     not followed); is_normalmap -> BC5, has_alpha -> BC3, else BC1;
 //   - the LBCHeader (writeLBCHeader, :312-322);
 //   - the images in the loop's order as one batch, one lmx_texcomp_run, the blocks appended behind the header.
-// Mip generation (computeMip), computeCoverage and scaleCoverage stay with the engine: with options.generate_mipmaps set compress returns
-// false and the caller runs the engine's own path, as it does wherever the library refuses (lastError() says why).
+// With options.generate_mipmaps set compress returns false, as it does wherever the library refuses (lastError() says why): such an input
+// goes to compressWithMips, which has the chains built on the device (computeMip, computeCoverage, scaleCoverage: DESIGN.md §4.24) and
+// compresses them where they lie.
 //
 // `InputT` is TextureCompressor::Input-shaped (w, h, slices, mips, is_normalmap, has_alpha, is_cubemap, has(face, slice, mip) and
 // get(face, slice, mip).pixels with data() and size()), `OptionsT` Options-shaped (compress, generate_mipmaps), `StreamT`
@@ -109,6 +110,68 @@ struct GpuTextureCompressor {
 		const size_t payload = (size_t)dst.size();
 		dst.resize(payload + (size_t)out_bytes);
 		if (lmx_texcomp_read(m_tc, (uint8_t*)dst.getMutableData() + payload, out_bytes) != LMX_OK) {
+			dst.resize(start);
+			return false;
+		}
+		return true;
+	}
+
+	// TextureCompressor::compress(src, options, dst, allocator) for options.generate_mipmaps == true (:359-401): the chains are built on the
+	// device - computeMip by options.stochastic_mipmap / src.is_srgb, scaleCoverage for options.scale_coverage_ref >= 0 - and compressed
+	// where they lie. `OptionsT` has stochastic_mipmap and scale_coverage_ref besides, `InputT` is_srgb. A size that stays RGBA8 gets the
+	// chains' pixels as its payload. A false return leaves dst as it was.
+	template <typename InputT, typename OptionsT, typename StreamT> bool compressWithMips(const InputT& src, const OptionsT& options, StreamT& dst) {
+		if (!m_tc || !options.generate_mipmaps || src.mips != 1) return false; // isValid (:403-413): generated chains start from one mip
+		const u32 faces = src.is_cubemap ? 6u : 1u;
+		for (u32 slice = 0; slice < src.slices; ++slice)
+			for (u32 face = 0; face < faces; ++face)
+				if (!src.has(face, slice, 0)) return false;
+		const gpu::TextureFormat format = formatOf(src, options);
+		const u32 mips = lmx_texcomp_chain_levels(src.w, src.h); // 1 + log2(maximum(w, h)) (:420)
+		const u32 n = src.slices * faces;
+		uint64_t chain_bytes = 0, out_bytes = 0;
+		// (everything that can refuse comes before the first byte is written)
+		if (!mips || !n || lmx_texcomp_chain_bytes(n, src.w, src.h, &chain_bytes) != LMX_OK) return false;
+		const size_t image_bytes = 4 * (size_t)src.w * src.h;
+		m_batch.resize(image_bytes * n);
+		size_t at = 0;
+		for (u32 slice = 0; slice < src.slices; ++slice)
+			for (u32 face = 0; face < faces; ++face) {
+				const auto& pixels = src.get(face, slice, 0).pixels;
+				if ((size_t)pixels.size() != image_bytes) return false;
+				memcpy(m_batch.data() + at, pixels.data(), image_bytes);
+				at += image_bytes;
+			}
+		LmxTexMipOptions mip_options;
+		mip_options.mode = options.stochastic_mipmap ? LMX_TEXMIP_STOCHASTIC : src.is_srgb ? LMX_TEXMIP_SRGB : LMX_TEXMIP_LINEAR; // computeMip's order (:202-215)
+		mip_options.scale_coverage_ref = options.scale_coverage_ref;
+		int lmx_format = LMX_TEX_BC1;
+		if (format == gpu::TextureFormat::BC5) lmx_format = LMX_TEX_BC5;
+		else if (format == gpu::TextureFormat::BC3) lmx_format = LMX_TEX_BC3;
+		if (format != gpu::TextureFormat::RGBA8) {
+			m_descs.clear();
+			for (u32 i = 0; i < n; ++i)
+				for (u32 mip = 0; mip < mips; ++mip) m_descs.push_back(LmxTexImage{mipSize(src.w, mip), mipSize(src.h, mip)});
+			if (lmx_texcomp_output_bytes((u32)m_descs.size(), m_descs.data(), lmx_format, &out_bytes) != LMX_OK) return false;
+		}
+		if (lmx_texcomp_set_chains(m_tc, n, src.w, src.h, m_batch.data()) != LMX_OK) return false;
+		if (lmx_texcomp_generate_mips(m_tc, &mip_options) != LMX_OK) return false;
+		if (format != gpu::TextureFormat::RGBA8 && lmx_texcomp_run(m_tc, lmx_format) != LMX_OK) return false;
+		LBCHeader header; // writeLBCHeader (:312-322)
+		header.w = src.w;
+		header.h = src.h;
+		header.slices = src.slices;
+		header.mips = mips;
+		header.format = format;
+		if (src.is_cubemap) header.flags |= LBCHeader::CUBEMAP;
+		const size_t start = (size_t)dst.size();
+		dst.write(&header, sizeof(header));
+		const size_t payload = (size_t)dst.size();
+		const uint64_t bytes = format == gpu::TextureFormat::RGBA8 ? chain_bytes : out_bytes;
+		dst.resize(payload + (size_t)bytes);
+		uint8_t* out = (uint8_t*)dst.getMutableData() + payload;
+		const int rc = format == gpu::TextureFormat::RGBA8 ? lmx_texcomp_read_pixels(m_tc, out, bytes) : lmx_texcomp_read(m_tc, out, bytes);
+		if (rc != LMX_OK) {
 			dst.resize(start);
 			return false;
 		}
