@@ -269,6 +269,59 @@ typedef struct LmxAnimation {
 	const float* root_pose_rotations;        /* RootMotion::pose_rotations, (frame_count + 1) x 4 */
 } LmxAnimation;
 
+/* ---- animation clip compressor (lmx_animcomp_*, lumix_mi355.h "Animation compressor") ---- */
+
+typedef struct LmxAnimKey { /* ModelImporter::Key: one bone at one sample */
+	float pos[3];
+	float rot[4];
+} LmxAnimKey;
+
+/* a clip's status: 0, or the smallest code that applies to it */
+enum {
+	LMX_ANIMCOMP_OK = 0,
+	LMX_ANIMCOMP_NO_SAMPLES = 1,     /* n_samples == 0 */
+	LMX_ANIMCOMP_BAD_ERROR = 2,      /* an error that is not finite and positive */
+	LMX_ANIMCOMP_NONFINITE_BIND = 3, /* of a bone with keys */
+	LMX_ANIMCOMP_NONFINITE_KEY = 4,
+	LMX_ANIMCOMP_QUOTIENT_RANGE = 5, /* range / constant / error is 2^32 or more */
+	LMX_ANIMCOMP_CHANNEL_BITS = 6,   /* a channel above 30 bits */
+	LMX_ANIMCOMP_ENTRY_BITS = 7,     /* an entry above 57 bits (lmx_anim_add's limit) */
+	LMX_ANIMCOMP_FRAME_BITS = 8      /* a frame above 65535 bits (offset_bits is 16 bits wide) */
+};
+
+typedef struct LmxAnimCompClip {
+	uint32_t n_bones;              /* 1 .. LMX_MAX_BONES */
+	uint32_t n_samples;
+	float fps;                     /* not used by the compressor: carried for the file's header */
+	float translation_error;       /* ModelMeta::anim_translation_error */
+	float rotation_error;          /* ModelMeta::anim_rotation_error */
+	uint32_t _pad;
+	const uint8_t* has_keys;       /* n_bones bytes, 0: the bone's key array is empty; NULL: every bone has keys */
+	const float* bind_positions;   /* n_bones x 3: each bone's local bind position */
+	uint64_t key_offset;           /* of the clip's first record in `keys`; the clip holds n_samples x n_bones records, sample-major */
+} LmxAnimCompClip;
+
+typedef struct LmxAnimCompInfo {
+	uint32_t n_const_translations, n_translations, n_const_rotations, n_rotations;
+	uint32_t translations_frame_size_bits, rotations_frame_size_bits;
+	uint64_t translation_stream_size, rotation_stream_size; /* bytes: (frame size x n_samples + 7) / 8 */
+	uint32_t frame_count;          /* n_samples - 1 */
+	uint32_t status;               /* LMX_ANIMCOMP_*; a refused clip has zero counts and sizes */
+} LmxAnimCompInfo;
+
+/* the caller's arrays lmx_animcomp_read_clip fills, shaped like LmxAnimation's; a NULL array is skipped */
+typedef struct LmxAnimCompOutput {
+	LmxAnimConstTranslation* const_translations;
+	LmxAnimTranslationTrack* translations;
+	LmxAnimConstRotation* const_rotations;
+	LmxAnimRotationTrack* rotations;
+	uint8_t* translation_stream;
+	uint8_t* rotation_stream;
+	uint32_t cap_tracks;           /* records each of the four tables has room for */
+	uint32_t _pad;
+	uint64_t cap_translation_stream, cap_rotation_stream; /* bytes */
+} LmxAnimCompOutput;
+
 /* One SAMPLE instruction of an Animator's blend stack (anim::BlendStackInstructions::SAMPLE, controller.cpp:282-289: slot, weight,
  * time, looped as the controller's nodes wrote them; `animation` is the id lmx_anim_add returned for RuntimeContext::animations[slot]). */
 typedef struct LmxBlendSample {

@@ -1486,6 +1486,56 @@ LMX_API int lmx_texmips_coeffs(uint32_t in, uint32_t out, void* rows, uint32_t c
 /* whole chains, sequentially: rgba = n level-0 images, out = lmx_texcomp_chain_bytes bytes. */
 LMX_API int lmx_texmips_host(const LmxTexMipOptions* options, uint32_t n, uint32_t w, uint32_t h, const uint8_t* rgba, uint8_t* out);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * Animation compressor: what ModelImporter::writeAnimations (renderer/editor/model_importer.cpp:1508-1754) does between all_keys and the
+ * last bit_writer.write, for a batch of clips, as an object beside the context. Per clip: the tracks in bone order, shaped
+ * like LmxAnimation's tables with bone_index = the bone's position in the clip, and the two bit streams of n_samples frames.
+ * Where the reference is undefined the library defines: a zero-range channel of an animated track packs the field 0; log2 of 0 is 0; a clip
+ * with a quotient of 2^32 or more, a channel above 30 bits, an entry above 57 bits or a frame above 65535 bits is refused, as is one with
+ * n_samples == 0, an error that is not finite and positive, a non-finite key, or a non-finite bind position of a bone with keys. A refused
+ * clip reports its LMX_ANIMCOMP_* status in its info, has no tracks and no streams, and leaves the other clips of the batch as they are.
+ * Refusals of a whole batch: LMX_ERR_INVALID_ARGUMENT for n == 0, null pointers, a clip with n_bones == 0 or above LMX_MAX_BONES, device
+ * keys that are no multiple of 4 bytes; LMX_ERR_CAPACITY for keys above LMX_ANIMCOMP_MAX_BATCH_BYTES and for reads into too small arrays;
+ * LMX_ERR_NOT_BUILT for a run before a set and a read before a run.
+ * ------------------------------------------------------------------------------------------------------------------------------------ */
+typedef struct LmxAnimCompressor LmxAnimCompressor;
+#define LMX_ANIMCOMP_MAX_BATCH_BYTES (1ull << 30)
+typedef struct LmxAnimCompDevice {
+	const LmxAnimKey* d_keys;                           /* the batch's keys (the compressor's copy or the caller's); everything below is NULL before a run */
+	const LmxAnimCompInfo* d_infos;                     /* n_clips */
+	const LmxAnimConstTranslation* d_const_translations; /* clip c's records start at bone_offset[c], the bones of the clips before it */
+	const LmxAnimTranslationTrack* d_translations;
+	const LmxAnimConstRotation* d_const_rotations;
+	const LmxAnimRotationTrack* d_rotations;
+	const uint8_t* d_translation_streams;               /* clip c's stream starts at translation_offset[c] bytes (a multiple of 4) */
+	const uint8_t* d_rotation_streams;
+	uint32_t n_clips, n_bones;                          /* n_bones: of all clips */
+} LmxAnimCompDevice;
+LMX_API int lmx_animcomp_create(LmxContext* ctx, LmxAnimCompressor** out);
+LMX_API void lmx_animcomp_destroy(LmxAnimCompressor* ac);
+/* keys: the 28-byte records of all clips; copies the batch to the device before it returns */
+LMX_API int lmx_animcomp_set_clips(LmxAnimCompressor* ac, uint32_t n, const LmxAnimCompClip* descs, const LmxAnimKey* keys);
+/* the same with the keys at a device pointer: not copied, they must stay until the run has finished (has_keys and bind_positions are host arrays) */
+LMX_API int lmx_animcomp_set_clips_device(LmxAnimCompressor* ac, uint32_t n, const LmxAnimCompClip* descs, const LmxAnimKey* d_keys);
+/* ranges, layout and both streams of every clip. Waits for the stream once, between the layout and the pack, to size the streams */
+LMX_API int lmx_animcomp_run(LmxAnimCompressor* ac);
+/* after a run; no device call */
+LMX_API int lmx_animcomp_clip_info(LmxAnimCompressor* ac, uint32_t clip, LmxAnimCompInfo* out);
+/* fills the caller's arrays; waits for the stream. With `length` and the root-motion fields set the result is an LmxAnimation for lmx_anim_add */
+LMX_API int lmx_animcomp_read_clip(LmxAnimCompressor* ac, uint32_t clip, LmxAnimCompOutput* out);
+/* Device pointers for GPU consumers, valid until the next set or run; stream-ordered. bone_offset, translation_offset and rotation_offset
+ * (each may be NULL) get n_clips entries; the two stream offsets are zeros before a run */
+LMX_API int lmx_animcomp_device_outputs(LmxAnimCompressor* ac, LmxAnimCompDevice* out, uint32_t* bone_offset, uint64_t* translation_offset, uint64_t* rotation_offset);
+/* A compressed clip of a finished run into the context's animation tables, as lmx_anim_add would take it from lmx_animcomp_read_clip: the
+ * same validation (a clip of one sample has frame_count 0 and is refused), the same tables, fps from the clip's descriptor, no root motion
+ * (-1). The track records are read to the host (the stream drains); the two streams are copied device to device into a buffer of the
+ * context's own, so the compressor may be reused or destroyed afterwards. */
+LMX_API int lmx_anim_add_compressed(LmxContext* ctx, LmxAnimCompressor* ac, uint32_t clip, uint32_t length, uint32_t* out_animation);
+/* One clip with the kernels' arithmetic on the host (no context, no device): keys = the clip's own n_samples x n_bones records (key_offset is
+ * not used). Returns LMX_OK for a refused clip too (info->status says so); LMX_ERR_CAPACITY where out's arrays are too small (a NULL `out`
+ * asks for the info alone). */
+LMX_API int lmx_animcomp_compress_host(const LmxAnimCompClip* desc, const LmxAnimKey* keys, LmxAnimCompInfo* info, LmxAnimCompOutput* out);
+
 LMX_API const char* lmx_version(void);
 
 #ifdef __cplusplus

@@ -473,6 +473,16 @@ SYMBOLS = {
     "lmx_texcomp_read_pixels": (_ci, [_vp, _vp, C.c_uint64]),
     "lmx_texmips_coeffs": (_ci, [_u32, _u32, _vp, _u32]),
     "lmx_texmips_host": (_ci, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "lmx_animcomp_create": (_ci, [_vp, C.POINTER(_vp)]),
+    "lmx_animcomp_destroy": (None, [_vp]),
+    "lmx_animcomp_set_clips": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_animcomp_set_clips_device": (_ci, [_vp, _u32, _vp, _vp]),
+    "lmx_animcomp_run": (_ci, [_vp]),
+    "lmx_animcomp_clip_info": (_ci, [_vp, _u32, _vp]),
+    "lmx_animcomp_read_clip": (_ci, [_vp, _u32, _vp]),
+    "lmx_animcomp_device_outputs": (_ci, [_vp, _vp, _vp, _vp, _vp]),
+    "lmx_animcomp_compress_host": (_ci, [_vp, _vp, _vp, _vp]),
+    "lmx_anim_add_compressed": (_ci, [_vp, _vp, _u32, _u32, C.POINTER(_u32)]),
     "lmx_version": (C.c_char_p, []),
 }
 
@@ -2799,3 +2809,156 @@ class TexCompressor:
         d = LmxTexCompDevice()
         self.ctx.check(self.lib.lmx_texcomp_device_outputs(self.h, C.byref(d)))
         return d
+
+
+# ---- animation compressor (lmx_animcomp_*) --------------------------------------------------------------------------------------------------
+ANIM_KEY = np.dtype([("pos", "<f4", 3), ("rot", "<f4", 4)])  # LmxAnimKey
+ANIMCOMP_STATUS = {0: "OK", 1: "NO_SAMPLES", 2: "BAD_ERROR", 3: "NONFINITE_BIND", 4: "NONFINITE_KEY", 5: "QUOTIENT_RANGE", 6: "CHANNEL_BITS", 7: "ENTRY_BITS", 8: "FRAME_BITS"}  # LMX_ANIMCOMP_*
+ANIMCOMP_GUARD_BYTES = 256  # behind the streams of a run
+
+
+class LmxAnimCompClip(C.Structure):
+    _fields_ = [("n_bones", C.c_uint32), ("n_samples", C.c_uint32), ("fps", C.c_float), ("translation_error", C.c_float), ("rotation_error", C.c_float),
+                ("_pad", C.c_uint32), ("has_keys", C.c_void_p), ("bind_positions", C.c_void_p), ("key_offset", C.c_uint64)]
+
+
+class LmxAnimCompInfo(C.Structure):
+    _fields_ = [("n_const_translations", C.c_uint32), ("n_translations", C.c_uint32), ("n_const_rotations", C.c_uint32), ("n_rotations", C.c_uint32),
+                ("translations_frame_size_bits", C.c_uint32), ("rotations_frame_size_bits", C.c_uint32), ("translation_stream_size", C.c_uint64),
+                ("rotation_stream_size", C.c_uint64), ("frame_count", C.c_uint32), ("status", C.c_uint32)]
+
+
+class LmxAnimCompOutput(C.Structure):
+    _fields_ = [("const_translations", C.c_void_p), ("translations", C.c_void_p), ("const_rotations", C.c_void_p), ("rotations", C.c_void_p),
+                ("translation_stream", C.c_void_p), ("rotation_stream", C.c_void_p), ("cap_tracks", C.c_uint32), ("_pad", C.c_uint32),
+                ("cap_translation_stream", C.c_uint64), ("cap_rotation_stream", C.c_uint64)]
+
+
+class LmxAnimCompDevice(C.Structure):
+    _fields_ = [("d_keys", C.c_void_p), ("d_infos", C.c_void_p), ("d_const_translations", C.c_void_p), ("d_translations", C.c_void_p), ("d_const_rotations", C.c_void_p),
+                ("d_rotations", C.c_void_p), ("d_translation_streams", C.c_void_p), ("d_rotation_streams", C.c_void_p), ("n_clips", C.c_uint32), ("n_bones", C.c_uint32)]
+
+
+def _animcomp_descs(clips):
+    """clips: dicts of keys (n_samples, n_bones) ANIM_KEY, bind (n_bones, 3), optional has_keys (n_bones,), fps, translation_error, rotation_error
+    -> (the descriptor array, all records one clip behind the other, keep-alive list)"""
+    descs = (LmxAnimCompClip * max(len(clips), 1))()
+    keep, flat, at = [], [], 0
+    for i, c in enumerate(clips):
+        keys = np.ascontiguousarray(c["keys"], ANIM_KEY)
+        assert keys.ndim == 2, "keys: (n_samples, n_bones)"
+        bind = np.ascontiguousarray(c["bind"], np.float32).reshape(keys.shape[1], 3)
+        has = None if c.get("has_keys") is None else np.ascontiguousarray(c["has_keys"], np.uint8).reshape(keys.shape[1])
+        keep += [bind, has]
+        descs[i] = LmxAnimCompClip(keys.shape[1], keys.shape[0], float(c.get("fps", 30.0)), float(c.get("translation_error", 1.0)), float(c.get("rotation_error", 1.0)), 0,
+                                   _ptr(has), _ptr(bind), at)
+        flat.append(keys.reshape(-1))
+        at += keys.size
+    records = np.concatenate(flat) if flat else np.zeros(0, ANIM_KEY)
+    if records.size == 0:
+        records = np.zeros(1, ANIM_KEY)  # (a non-null pointer for a batch of clips without samples)
+    return descs, records, keep
+
+
+def _animcomp_result(info: LmxAnimCompInfo):
+    """the info as a dict, and arrays with room for the clip's tables and streams"""
+    d = {name: int(getattr(info, name)) for name, _ in LmxAnimCompInfo._fields_}
+    arrays = [np.zeros(d["n_const_translations"], ANIM_CONST_TRANSLATION), np.zeros(d["n_translations"], ANIM_TRANSLATION_TRACK),
+              np.zeros(d["n_const_rotations"], ANIM_CONST_ROTATION), np.zeros(d["n_rotations"], ANIM_ROTATION_TRACK),
+              np.zeros(d["translation_stream_size"], np.uint8), np.zeros(d["rotation_stream_size"], np.uint8)]
+    out = LmxAnimCompOutput(*[_ptr(a) if a.size else None for a in arrays], max(len(a) for a in arrays[:4]), 0, arrays[4].size, arrays[5].size)
+    d.update(zip(("const_translations", "translations", "const_rotations", "rotations", "translation_stream", "rotation_stream"), arrays))
+    return d, out
+
+
+def animcomp_compress_host(clip: dict) -> dict:
+    """One clip with the kernels' arithmetic on the host (lmx_animcomp_compress_host): the info's fields, and for a clip that was not refused
+    its four tables and two streams. Needs no device."""
+    lib = load_library()
+    descs, records, keep = _animcomp_descs([clip])
+    info = LmxAnimCompInfo()
+    rc = lib.lmx_animcomp_compress_host(C.byref(descs[0]), _ptr(records), C.byref(info), None)
+    if rc != 0:
+        raise LumixError(rc, "lmx_animcomp_compress_host refused the clip's descriptor")
+    d, out = _animcomp_result(info)
+    if d["status"] == 0:
+        rc = lib.lmx_animcomp_compress_host(C.byref(descs[0]), _ptr(records), C.byref(info), C.byref(out))
+        if rc != 0:
+            raise LumixError(rc, "lmx_animcomp_compress_host: the arrays sized from its own info are too small")
+    return d
+
+
+def animcomp_animation(result: dict, fps: float, length: int) -> dict:
+    """a compressed clip as the dict animation_struct takes, without root motion"""
+    a = {k: result[k] for k in ("const_translations", "translations", "const_rotations", "rotations", "translation_stream", "rotation_stream",
+                                "frame_count", "translations_frame_size_bits", "rotations_frame_size_bits")}
+    a.update(fps=fps, length=length, root_translation_track=-1, root_rotation_track=-1, root_pose_translations=np.zeros(0, np.float32), root_pose_rotations=np.zeros(0, np.float32))
+    return a
+
+
+class AnimCompressor:
+    """ModelImporter::writeAnimations' loops on the device (lmx_animcomp_*): a batch of clips of sampled keys -> each clip's track tables and
+    its two bit streams."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(self.lib.lmx_animcomp_create(ctx.h, C.byref(h)))
+        self.h = h
+        self.n = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                self.lib.lmx_animcomp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setClips(self, clips):
+        """clips: see _animcomp_descs"""
+        descs, records, keep = _animcomp_descs(clips)
+        self.ctx.check(self.lib.lmx_animcomp_set_clips(self.h, len(clips), C.byref(descs) if len(clips) else None, _ptr(records)))
+        self.n = len(clips)
+
+    def setClipsDevice(self, clips, d_keys: int):
+        """the same with the records of all clips, one clip behind the other, at the device address d_keys (not copied); the dicts' keys
+        give the shapes"""
+        descs, records, keep = _animcomp_descs(clips)
+        self.ctx.check(self.lib.lmx_animcomp_set_clips_device(self.h, len(clips), C.byref(descs) if len(clips) else None, C.c_void_p(d_keys)))
+        self.n = len(clips)
+
+    def run(self):
+        self.ctx.check(self.lib.lmx_animcomp_run(self.h))
+
+    def clipInfo(self, clip: int) -> dict:
+        info = LmxAnimCompInfo()
+        self.ctx.check(self.lib.lmx_animcomp_clip_info(self.h, clip, C.byref(info)))
+        return _animcomp_result(info)[0]
+
+    def readClip(self, clip: int) -> dict:
+        """the info's fields, and for a clip that was not refused its four tables and two streams"""
+        info = LmxAnimCompInfo()
+        self.ctx.check(self.lib.lmx_animcomp_clip_info(self.h, clip, C.byref(info)))
+        d, out = _animcomp_result(info)
+        if d["status"] == 0:
+            self.ctx.check(self.lib.lmx_animcomp_read_clip(self.h, clip, C.byref(out)))
+        return d
+
+    def addTo(self, clip: int, length: int) -> int:
+        """lmx_anim_add_compressed: the clip into the context's animation tables, its streams copied device to device -> the animation's id"""
+        out = C.c_uint32()
+        self.ctx.check(self.lib.lmx_anim_add_compressed(self.ctx.h, self.h, clip, length, C.byref(out)))
+        return int(out.value)
+
+    def deviceOutputs(self):
+        """-> (LmxAnimCompDevice, bone_offset (n,), translation_offset (n,), rotation_offset (n,))"""
+        d = LmxAnimCompDevice()
+        bone, t_at, r_at = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.uint64), np.zeros(max(self.n, 1), np.uint64)
+        self.ctx.check(self.lib.lmx_animcomp_device_outputs(self.h, C.byref(d), _ptr(bone), _ptr(t_at), _ptr(r_at)))
+        return d, bone[: self.n], t_at[: self.n], r_at[: self.n]

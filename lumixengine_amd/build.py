@@ -19,9 +19,9 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "liblumix_mi355.so")
 SOURCES = ["cull_kernels.hip", "xform_kernels.hip", "skin_kernels.hip", "lmx_capi_ctx.hip", "lmx_capi_cull.hip", "lmx_capi_cull_set.hip", "lmx_capi_cull_async.hip", "lmx_capi_cull_results.hip", "lmx_capi_world.hip", "world_edit_kernels.hip", "lmx_capi_world_edit.hip",
-           "lmx_capi_skin.hip", "lmx_capi_exchange.hip", "keys_kernels.hip", "lmx_capi_keys.hip", "anim_kernels.hip", "lmx_capi_anim.hip", "im_kernels.hip", "lmx_capi_im.hip", "draw_kernels.hip", "lmx_capi_draw.hip", "pose_kernels.hip", "lmx_capi_poses.hip", "cluster_kernels.hip", "lmx_capi_clusters.hip", "ray_kernels.hip", "lmx_capi_rays.hip", "ray_scene_kernels.hip", "lmx_capi_rays_scene.hip", "particle_kernels.hip", "lmx_capi_particles.hip", "grass_kernels.hip", "lmx_capi_grass.hip", "animator_kernels.hip", "lmx_capi_animators.hip", "voxel_kernels.hip", "lmx_capi_voxels.hip", "probe_kernels.hip", "lmx_capi_probes.hip", "texcomp_kernels.hip", "texmips_kernels.hip", "lmx_capi_texcomp.hip",
+           "lmx_capi_skin.hip", "lmx_capi_exchange.hip", "keys_kernels.hip", "lmx_capi_keys.hip", "anim_kernels.hip", "lmx_capi_anim.hip", "im_kernels.hip", "lmx_capi_im.hip", "draw_kernels.hip", "lmx_capi_draw.hip", "pose_kernels.hip", "lmx_capi_poses.hip", "cluster_kernels.hip", "lmx_capi_clusters.hip", "ray_kernels.hip", "lmx_capi_rays.hip", "ray_scene_kernels.hip", "lmx_capi_rays_scene.hip", "particle_kernels.hip", "lmx_capi_particles.hip", "grass_kernels.hip", "lmx_capi_grass.hip", "animator_kernels.hip", "lmx_capi_animators.hip", "voxel_kernels.hip", "lmx_capi_voxels.hip", "probe_kernels.hip", "lmx_capi_probes.hip", "texcomp_kernels.hip", "texmips_kernels.hip", "lmx_capi_texcomp.hip", "animcomp_kernels.hip", "lmx_capi_animcomp.hip",
            "lmx_frustum.cpp", "lmx_cluster_planes.cpp", "lmx_world_blob.cpp", "lmx_particle_program.cpp", "lmx_blend_stack.cpp", "lmx_controller_program.cpp"]
-HEADERS = [os.path.join(CSRC, "lmx_math.h"), os.path.join(CSRC, "lmx_kernels.h"), os.path.join(CSRC, "lmx_cull_layout.h"), os.path.join(CSRC, "lmx_context.h"), os.path.join(CSRC, "lmx_cull_host.h"), os.path.join(CSRC, "lmx_im.h"), os.path.join(CSRC, "lmx_entity_tr.h"), os.path.join(CSRC, "lmx_ray_math.h"), os.path.join(CSRC, "lmx_skin_eval.h"), os.path.join(CSRC, "lmx_particles.h"), os.path.join(CSRC, "lmx_particle_program.h"), os.path.join(CSRC, "lmx_blend_stack.h"), os.path.join(CSRC, "lmx_controller_program.h"), os.path.join(CSRC, "lmx_terrain_height.h"), os.path.join(CSRC, "lmx_grass.h"), os.path.join(CSRC, "lmx_wave.h"), os.path.join(CSRC, "lmx_world_edit_host.h"), os.path.join(CSRC, "lmx_voxels.h"), os.path.join(CSRC, "lmx_probes.h"), os.path.join(CSRC, "lmx_texcomp.h"), os.path.join(CSRC, "lmx_texmips.h"), os.path.join(ROOT, "include", "lumix_mi355.h"),
+HEADERS = [os.path.join(CSRC, "lmx_math.h"), os.path.join(CSRC, "lmx_kernels.h"), os.path.join(CSRC, "lmx_cull_layout.h"), os.path.join(CSRC, "lmx_context.h"), os.path.join(CSRC, "lmx_cull_host.h"), os.path.join(CSRC, "lmx_im.h"), os.path.join(CSRC, "lmx_entity_tr.h"), os.path.join(CSRC, "lmx_ray_math.h"), os.path.join(CSRC, "lmx_skin_eval.h"), os.path.join(CSRC, "lmx_particles.h"), os.path.join(CSRC, "lmx_particle_program.h"), os.path.join(CSRC, "lmx_blend_stack.h"), os.path.join(CSRC, "lmx_controller_program.h"), os.path.join(CSRC, "lmx_terrain_height.h"), os.path.join(CSRC, "lmx_grass.h"), os.path.join(CSRC, "lmx_wave.h"), os.path.join(CSRC, "lmx_world_edit_host.h"), os.path.join(CSRC, "lmx_voxels.h"), os.path.join(CSRC, "lmx_probes.h"), os.path.join(CSRC, "lmx_texcomp.h"), os.path.join(CSRC, "lmx_texmips.h"), os.path.join(CSRC, "lmx_animcomp.h"), os.path.join(ROOT, "include", "lumix_mi355.h"),
            os.path.join(ROOT, "include", "lmx_types.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + os.environ.get("LMX_HIPCC_EXTRA", "").split()  # experiments: -DLMX_...=n

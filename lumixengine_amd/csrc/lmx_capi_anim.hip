@@ -21,6 +21,7 @@ int anim_upload_tables(LmxContext* ctx) {
 	LMX_HIP(ctx, upload_blocking(an.d_rt, an.rt));
 	LMX_HIP(ctx, upload_blocking(an.d_tstream, an.tstream));
 	LMX_HIP(ctx, upload_blocking(an.d_rstream, an.rstream));
+	for (const AnimDeviceStream& d : an.device_streams) LMX_HIP(ctx, device_copy_blocking((d.rotation ? an.d_rstream.p : an.d_tstream.p) + d.at, (const uint8_t*)d.copy.p, d.bytes));
 	LMX_HIP(ctx, upload_blocking(an.d_root_t, an.root_t));
 	LMX_HIP(ctx, upload_blocking(an.d_root_r, an.root_r));
 	LMX_HIP(ctx, upload_blocking(an.d_rel_pos, an.rel_pos));
@@ -31,10 +32,10 @@ int anim_upload_tables(LmxContext* ctx) {
 
 } // namespace lmx
 
-extern "C" {
+namespace {
 
-int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation) {
-	LMX_CHECK_CTX(ctx);
+// lmx_anim_add; d_streams: the clip's two streams are on the device (translation, rotation; a->translation_stream / rotation_stream are not read)
+int anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation, const uint8_t* const* d_streams) {
 	if (!a || !out_animation) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null animation / out");
 	if (!(a->fps > 0.f) || !a->frame_count || !a->length) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "fps, frame_count and length must be positive");
 	if ((a->n_const_translations && !a->const_translations) || (a->n_translations && !a->translations) || (a->n_const_rotations && !a->const_rotations) ||
@@ -51,7 +52,9 @@ int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation
 	// and the clamp is at most frame_count; above, (float)frame_count can round up and sample_idx would pass the frames stored here
 	if (a->frame_count > (1u << 24)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "frame_count %u exceeds 2^24: the sample point is computed in fp32", a->frame_count);
 	const uint64_t t_need = (t_bits + 7) / 8, r_need = (r_bits + 7) / 8;
-	if ((a->n_translations && (!a->translation_stream || a->translation_stream_size < t_need)) || (a->n_rotations && (!a->rotation_stream || a->rotation_stream_size < r_need)))
+	const uint8_t* t_src = d_streams ? d_streams[0] : a->translation_stream;
+	const uint8_t* r_src = d_streams ? d_streams[1] : a->rotation_stream;
+	if ((a->n_translations && (!t_src || a->translation_stream_size < t_need)) || (a->n_rotations && (!r_src || a->rotation_stream_size < r_need)))
 		return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "track streams must hold frame_count + 1 frames (animation.cpp:464): need %llu / %llu bytes", (unsigned long long)t_need, (unsigned long long)r_need);
 	if ((a->root_translation_track >= 0 && ((uint32_t)a->root_translation_track >= a->n_translations || !a->root_pose_translations)) ||
 		(a->root_rotation_track >= 0 && ((uint32_t)a->root_rotation_track >= a->n_rotations || !a->root_pose_rotations)))
@@ -93,6 +96,18 @@ int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation
 		if (t.offset_bits + 1u + t.bitsizes[0] + t.bitsizes[1] + t.bitsizes[2] > a->rotations_frame_size_bits) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "rotation track %u exceeds the frame size", i);
 		if (t.skipped_channel > 3) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "rotation track %u: skipped_channel %u", i, t.skipped_channel);
 	}
+	// a device stream gets the library's own copy first: nothing below can fail once the tables have grown
+	AnimDeviceStream own[2];
+	if (d_streams) {
+		const uint64_t need[2] = {t_store ? t_need : 0, r_store ? r_need : 0};
+		for (int k = 0; k < 2; ++k) {
+			own[k].rotation = k == 1;
+			own[k].bytes = (size_t)need[k];
+			if (!need[k]) continue;
+			LMX_HIP(ctx, own[k].copy.reserve((size_t)need[k]));
+			LMX_HIP(ctx, device_copy_on_stream(own[k].copy.p, d_streams[k], (size_t)need[k], ctx->stream));
+		}
+	}
 	AnimDevice d;
 	memset(&d, 0, sizeof(d));
 	d.fps = a->fps; d.frame_count = a->frame_count; d.length = a->length; d.tfs_bits = a->translations_frame_size_bits; d.rfs_bits = a->rotations_frame_size_bits;
@@ -111,17 +126,26 @@ int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation
 	// sample point's upper clamp frame_count - 0.00001f is frame_count in fp32) decodes frames frame_count and frame_count + 1, which the
 	// reference leaves to whatever follows its stream. So: the caller's frame_count + 1 frames to the bit (the tail of their last byte is
 	// cleared), one more frame of zero bits, then 16 bytes of slack for the 64-bit reads; every clip starts 8-byte aligned.
+	// (a device stream: zeros stand in its place here, and the copy above is laid over them whenever the tables go up; the compressor has
+	// cleared the tail of its last byte)
 	auto append_stream = [](std::vector<uint8_t>& dst, const uint8_t* src_bytes, uint64_t bits, uint64_t need, uint64_t store) {
 		const size_t start = dst.size();
 		if (store) {
-			dst.insert(dst.end(), src_bytes, src_bytes + need);
-			if (bits & 7) dst.back() &= (uint8_t)((1u << (bits & 7)) - 1u);
+			if (src_bytes) {
+				dst.insert(dst.end(), src_bytes, src_bytes + need);
+				if (bits & 7) dst.back() &= (uint8_t)((1u << (bits & 7)) - 1u);
+			}
 			dst.resize(start + store, 0);
 		}
 		dst.resize((dst.size() + 16 + 7) & ~(size_t)7, 0);
 	};
-	append_stream(an.tstream, a->translation_stream, t_bits, t_need, t_store);
-	append_stream(an.rstream, a->rotation_stream, r_bits, r_need, r_store);
+	append_stream(an.tstream, d_streams ? nullptr : a->translation_stream, t_bits, t_need, t_store);
+	append_stream(an.rstream, d_streams ? nullptr : a->rotation_stream, r_bits, r_need, r_store);
+	if (d_streams) {
+		own[0].at = d.tstream_off, own[1].at = d.rstream_off;
+		for (int k = 0; k < 2; ++k)
+			if (own[k].bytes) an.device_streams.push_back(std::move(own[k]));
+	}
 	for (size_t f = 0; f < (size_t)frames_in; ++f) { // frame_count + 1 entries of the caller's, then one of zeros (the same definition)
 		for (int k = 0; k < 3; ++k) an.root_t.push_back(a->root_translation_track >= 0 ? a->root_pose_translations[3 * f + k] : 0.f);
 		an.root_r.push_back(a->root_rotation_track >= 0 ? make_float4(a->root_pose_rotations[4 * f], a->root_pose_rotations[4 * f + 1], a->root_pose_rotations[4 * f + 2], a->root_pose_rotations[4 * f + 3])
@@ -133,6 +157,32 @@ int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation
 	an.anims.push_back(d);
 	an.tables_dirty = true;
 	return LMX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int lmx_anim_add(LmxContext* ctx, const LmxAnimation* a, uint32_t* out_animation) {
+	LMX_CHECK_CTX(ctx);
+	return anim_add(ctx, a, out_animation, nullptr);
+}
+
+int lmx_anim_add_compressed(LmxContext* ctx, LmxAnimCompressor* ac, uint32_t clip, uint32_t length, uint32_t* out_animation) {
+	LMX_CHECK_CTX(ctx);
+	if (!ac || !out_animation) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null compressor / out");
+	AnimCompClipView v;
+	if (int rc = animcomp_clip_view(ctx, ac, clip, &v)) return rc;
+	LmxAnimation a;
+	memset(&a, 0, sizeof(a));
+	a.fps = v.fps, a.frame_count = v.info.frame_count, a.length = length;
+	a.translations_frame_size_bits = v.info.translations_frame_size_bits, a.rotations_frame_size_bits = v.info.rotations_frame_size_bits;
+	a.n_const_translations = v.info.n_const_translations, a.n_translations = v.info.n_translations, a.n_const_rotations = v.info.n_const_rotations, a.n_rotations = v.info.n_rotations;
+	a.const_translations = v.ct.data(), a.translations = v.tt.data(), a.const_rotations = v.cr.data(), a.rotations = v.rt.data();
+	a.translation_stream_size = v.info.translation_stream_size, a.rotation_stream_size = v.info.rotation_stream_size;
+	a.root_translation_track = a.root_rotation_track = -1;
+	const uint8_t* d_streams[2] = {v.d_translation_stream, v.d_rotation_stream};
+	return anim_add(ctx, &a, out_animation, d_streams);
 }
 
 int lmx_anim_set_model_pose(LmxContext* ctx, uint32_t model, const LmxLocalRigidTransform* relative, uint32_t n_bones) {

@@ -563,6 +563,14 @@ struct RaysState {
 	bool scene() const { return n_pg != 0 || n_terrains != 0; }
 };
 
+// a clip's stream that never was on the host (lmx_anim_add_compressed): the library's own device copy, laid over the zeros the host
+// tables hold in its place every time they go up
+struct AnimDeviceStream {
+	bool rotation;
+	size_t at, bytes; // in tstream / rstream
+	DevBuf<uint8_t> copy;
+};
+
 // animation sampling (lmx_capi_anim.hip): Animation resources flattened into concatenated tables, one Animable per skin instance
 struct AnimState {
 	std::vector<AnimDevice> anims;
@@ -572,6 +580,7 @@ struct AnimState {
 	std::vector<LmxAnimConstRotation> cr;
 	std::vector<LmxAnimRotationTrack> rt;
 	std::vector<uint8_t> tstream, rstream;
+	std::vector<AnimDeviceStream> device_streams;
 	std::vector<float> root_t;
 	std::vector<float4> root_r;
 	std::vector<float> rel_pos;    // Model::Bone::relative_transform of every skin model, by model bone offset
@@ -670,6 +679,19 @@ int keys_before_tombstones(LmxContext* ctx, const PatchId* d_patches, uint32_t n
 int keys_upload_instances(LmxContext* ctx); // ... the host mirror of the per-entity records goes up if it changed (lmx_keys_run, the draw pass)
 void prof_drain(LmxContext* ctx);
 int anim_upload_tables(LmxContext* ctx);  // lmx_capi_anim.hip: make the device copy of the animation tables current
+// lmx_capi_animcomp.hip: a compressed clip for lmx_anim_add_compressed - its info, its tables read to the host (the stream drains), and where
+// its streams lie on the device
+struct AnimCompClipView {
+	LmxAnimCompInfo info;
+	std::vector<LmxAnimConstTranslation> ct;
+	std::vector<LmxAnimTranslationTrack> tt;
+	std::vector<LmxAnimConstRotation> cr;
+	std::vector<LmxAnimRotationTrack> rt;
+	const uint8_t* d_translation_stream;
+	const uint8_t* d_rotation_stream;
+	float fps;
+};
+int animcomp_clip_view(LmxContext* ctx, LmxAnimCompressor* ac, uint32_t clip, AnimCompClipView* out);
 int rays_scene_reserve(LmxContext* ctx);  // lmx_capi_rays_scene.hip: the scene stages' buffers for the current reserve and tables (may wait for the stream when they grow)
 int rays_scene_pass(LmxContext* ctx, const RaysDevice& d, const LmxRay* rays, const LmxRayImHit* im_hits); // ... enqueues them behind the entity stage `d`; rays: the caller's
 int cull_flush(LmxContext* ctx);          // lmx_capi_cull.hip: make the device copy of the culling sets current
