@@ -571,6 +571,31 @@ class Context:
         return ms.value, n.value
 
 
+class _ContextObject:
+    """An object beside the context: lmx_<UNIT>_create(ctx, &h) at construction, lmx_<UNIT>_destroy(h) at close() or collection."""
+
+    UNIT = ""  # the subclass's part of the two names
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx.check(getattr(self.lib, f"lmx_{self.UNIT}_create")(ctx.h, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):  # (the destroy reads its context: behind Context.close() there is nothing left to call it on)
+                getattr(self.lib, f"lmx_{self.UNIT}_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- frusta (host mirror of core/geometry.cpp) ----------------------------------------------------------------
 def viewport_frustum(is_ortho=False, fov=float(np.deg2rad(60.0)), ortho_size=100.0, w=1920, h=1080, pos=(0, 0, 0), rot=(0, 0, 0, 1), near=0.1,
                      far=10000.0) -> np.ndarray:
@@ -1100,29 +1125,15 @@ def im_view(camera_pos=(0, 0, 0), lod_multiplier=1.0, time_delta=1 / 60, is_shad
     return v
 
 
-class InstancedModels:
+class InstancedModels(_ContextObject):
     """InstancedModel grids + encodeInstancedModels on the device (lmx_im_*). Model ids are dense: addModel appends."""
 
+    UNIT = "im"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx.check(self.lib.lmx_im_create(ctx.h, C.byref(h)))
-        self.h = h
+        super().__init__(ctx)
         self.n_models = 0
         self.n = []
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):  # (lmx_im_destroy reads its context: behind Context.close() there is nothing left to call it on)
-                self.lib.lmx_im_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def setModel(self, model: int, lod_distances, lod_indices, origin_radius: float, indices_count):
         ld = np.ascontiguousarray(lod_distances, np.float32).reshape(4)
@@ -2010,33 +2021,18 @@ class LmxParticlesDevice(C.Structure):
     _fields_ = [("d_frame", C.c_void_p), ("d_slices", C.c_void_p), ("d_counts", C.c_void_p), ("n_emitters", _u32), ("frame_bytes", _u32)]
 
 
-class ParticleSystems:
+class ParticleSystems(_ContextObject):
     """ParticleSystem::update and Emitter::fillInstanceData of every registered system on the device (lmx_particles_*)."""
 
+    UNIT = "particles"
     ALL = 0xFFFFFFFF
 
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx.check(self.lib.lmx_particles_create(ctx.h, C.byref(h)))
-        self.h = h
+        super().__init__(ctx)
         self.emitters = []  # (system, emitter) by global emitter index
         self.capacity = {}
         self.outputs = {}
         self._ribbon = {}
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.lib.lmx_particles_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def addSystem(self, n_emitters: int, n_globals: int = 0) -> int:
         s = _u32()
@@ -2181,32 +2177,18 @@ class LmxGrassDevice(C.Structure):
                 ("n_views", _u32), ("n_live", _u32)]
 
 
-class Grass:
+class Grass(_ContextObject):
     """Terrain::createGrass of every terrain and renderGrass's quad loop of every view on the device (lmx_grass_*).
 
     A terrain is a dict: entity, heightmap (2-D uint16 = R16 or uint32 = RGBA8), scale (3), optional ready / format; splatmap (2-D uint32, or
     None), optional splat_format / splat_ready; types: a list of (spacing, distance, rotation_mode, usable)."""
 
+    UNIT = "grass"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx.check(self.lib.lmx_grass_create(ctx.h, C.byref(h)))
-        self.h = h
+        super().__init__(ctx)
         self.n_terrains = 0
         self.n_views = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.lib.lmx_grass_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def setTerrains(self, terrains):
         recs = np.zeros(len(terrains), GRASS_TERRAIN)
@@ -2337,27 +2319,10 @@ def _voxel_mesh(positions, indices):
     return LmxVoxelsMesh(p.ctypes.data if len(p) else None, stride, len(p), i.ctypes.data if len(i) else None, i.dtype.itemsize, len(i)), (p, i)
 
 
-class Voxels:
+class Voxels(_ContextObject):
     """Voxels of renderer/voxels.cpp on the device (lmx_voxels_*): raster, computeAO, blurAO, the lookups and the importer's vertex bake."""
 
-    def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx.check(self.lib.lmx_voxels_create(ctx.h, C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.lib.lmx_voxels_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    UNIT = "voxels"
 
     def set(self, src: "Voxels"):
         self.ctx.check(self.lib.lmx_voxels_set(self.h, src.h))
@@ -2474,29 +2439,15 @@ def probes_ggx_samples(level: int) -> np.ndarray:
 PROBE_LEVELS = 5  # roughness_levels
 
 
-class ProbeBaker:
+class ProbeBaker(_ContextObject):
     """The probe bake on the device (lmx_probes_*): SphericalHarmonics::compute, and the reflection probe's mip chain, radiance levels and
     RGBM bytes, for a batch of cubemaps."""
 
+    UNIT = "probes"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx.check(self.lib.lmx_probes_create(ctx.h, C.byref(h)))
-        self.h = h
+        super().__init__(ctx)
         self.n = self.size = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.lib.lmx_probes_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def setCubemaps(self, rgba):
         """rgba: float32 (n, 6, S, S, 4)"""
@@ -2715,30 +2666,16 @@ def texcomp_split_chain(chain, w: int, h: int):
     return out
 
 
-class TexCompressor:
+class TexCompressor(_ContextObject):
     """TextureCompressor::compress's block loops on the device (lmx_texcomp_*): BC1, BC3, BC4 and BC5 blocks of a batch of RGBA8 images,
     and the mip chains of compress() with generate_mipmaps (setChains, generateMips)."""
 
+    UNIT = "texcomp"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx.check(self.lib.lmx_texcomp_create(ctx.h, C.byref(h)))
-        self.h = h
+        super().__init__(ctx)
         self.sizes = np.zeros((0, 2), np.uint32)
         self.format = -1
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.lib.lmx_texcomp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def setImages(self, images):
         """images: a list of uint8 (h, w, 4)"""
@@ -2896,29 +2833,15 @@ def animcomp_animation(result: dict, fps: float, length: int) -> dict:
     return a
 
 
-class AnimCompressor:
+class AnimCompressor(_ContextObject):
     """ModelImporter::writeAnimations' loops on the device (lmx_animcomp_*): a batch of clips of sampled keys -> each clip's track tables and
     its two bit streams."""
 
+    UNIT = "animcomp"
+
     def __init__(self, ctx: Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx.check(self.lib.lmx_animcomp_create(ctx.h, C.byref(h)))
-        self.h = h
+        super().__init__(ctx)
         self.n = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                self.lib.lmx_animcomp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def setClips(self, clips):
         """clips: see _animcomp_descs"""

@@ -325,12 +325,10 @@ int lmx_animators_update(LmxContext* ctx, float time_delta) {
 		LMX_HIP(ctx, upload_blocking(an.d_parents, sk.parents.data(), sk.parents.size()));
 		an.parents_uploaded = sk.parents.size();
 	}
-	if (an.d_first_sample.cap < (size_t)as.n + 1 || an.d_instrs.cap < std::max<size_t>(as.total_slots, 1) || an.d_samples.cap < std::max<size_t>(as.total_slots, 1)) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the buffers are shared with lmx_anim_eval_blend_*: a call there may have come first, or none)
-		LMX_HIP(ctx, an.d_first_sample.reserve((size_t)as.n + 1));
-		LMX_HIP(ctx, an.d_instrs.reserve(std::max<size_t>(as.total_slots, 1)));
-		LMX_HIP(ctx, an.d_samples.reserve(std::max<size_t>(as.total_slots, 1)));
-	}
+	Grow grow{ctx}; // (the buffers are shared with lmx_anim_eval_blend_*: a call there may have come first, or none)
+	if (int rc = grow(an.d_first_sample, (size_t)as.n + 1)) return rc;
+	if (int rc = grow(an.d_instrs, std::max<size_t>(as.total_slots, 1))) return rc;
+	if (int rc = grow(an.d_samples, std::max<size_t>(as.total_slots, 1))) return rc;
 	AnimatorTables at;
 	at.headers = as.d_headers.p; at.nodes = as.d_nodes.p; at.ops = as.d_ops.p; at.exprs = as.d_exprs.p; at.aux = as.d_aux.p; at.slots = as.d_slots.p;
 	at.ik_leaf = as.d_ik_leaf.p; at.clips = as.d_clips.p; at.rm_t = as.d_rm_t.p; at.rm_r = as.d_rm_r.p;

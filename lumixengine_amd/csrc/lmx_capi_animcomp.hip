@@ -4,7 +4,6 @@
 #include "lmx_context.h"
 #include "lmx_animcomp.h"
 
-#include <memory>
 #include <new>
 
 using namespace lmx;
@@ -41,11 +40,6 @@ struct LmxAnimCompressor {
 namespace {
 
 constexpr size_t AC_GUARD_WORDS = 64; // behind the streams of a run: filled, never written by a kernel (lmx_context.h, fill_guard)
-
-#define LMX_ANIMCOMP_ENTER(ac)                         \
-	if (!(ac)) return LMX_ERR_INVALID_ARGUMENT;        \
-	LmxContext* ctx = (ac)->ctx;                       \
-	LMX_CHECK_CTX(ctx)
 
 // the batch's layout from its descriptors; `what`: what was wrong, for the message
 int lay_out(uint32_t n, const LmxAnimCompClip* descs, LmxAnimCompressor* ac, const char** what) {
@@ -183,36 +177,24 @@ int animcomp_clip_view(LmxContext* ctx, LmxAnimCompressor* ac, uint32_t clip, An
 
 extern "C" {
 
-int lmx_animcomp_create(LmxContext* ctx, LmxAnimCompressor** out) {
-	LMX_CHECK_CTX(ctx);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	*out = nullptr;
-	std::unique_ptr<LmxAnimCompressor> ac(new (std::nothrow) LmxAnimCompressor());
-	if (!ac) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "animcomp: host allocation failed");
-	ac->ctx = ctx;
-	*out = ac.release();
-	return LMX_OK;
-}
+int lmx_animcomp_create(LmxContext* ctx, LmxAnimCompressor** out) { return object_create(ctx, out, "animcomp"); }
 
 void lmx_animcomp_destroy(LmxAnimCompressor* ac) {
-	if (!ac) return;
-	(void)hipSetDevice(ac->ctx->device);
-	(void)hipStreamSynchronize(ac->ctx->stream);
-	delete ac;
+	if (ac) object_destroy(ac);
 }
 
 int lmx_animcomp_set_clips(LmxAnimCompressor* ac, uint32_t n, const LmxAnimCompClip* descs, const LmxAnimKey* keys) {
-	LMX_ANIMCOMP_ENTER(ac);
+	LMX_ENTER(ac);
 	return set_clips(ac, n, descs, keys, false);
 }
 
 int lmx_animcomp_set_clips_device(LmxAnimCompressor* ac, uint32_t n, const LmxAnimCompClip* descs, const LmxAnimKey* d_keys) {
-	LMX_ANIMCOMP_ENTER(ac);
+	LMX_ENTER(ac);
 	return set_clips(ac, n, descs, d_keys, true);
 }
 
 int lmx_animcomp_run(LmxAnimCompressor* ac) {
-	LMX_ANIMCOMP_ENTER(ac);
+	LMX_ENTER(ac);
 	if (!ac->n_clips || !ac->d_keys) return fail(ctx, LMX_ERR_NOT_BUILT, "animcomp: run before a batch was set");
 	const uint32_t n = ac->n_clips;
 	ac->ran = false;
@@ -257,7 +239,7 @@ int lmx_animcomp_run(LmxAnimCompressor* ac) {
 }
 
 int lmx_animcomp_clip_info(LmxAnimCompressor* ac, uint32_t clip, LmxAnimCompInfo* out) {
-	LMX_ANIMCOMP_ENTER(ac);
+	LMX_ENTER(ac);
 	if (!ac->ran) return fail(ctx, LMX_ERR_NOT_BUILT, "animcomp: no run on this batch");
 	if (!out || clip >= ac->n_clips) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "animcomp: null out, or clip %u of %u", clip, ac->n_clips);
 	*out = ac->h_infos[clip];
@@ -265,7 +247,7 @@ int lmx_animcomp_clip_info(LmxAnimCompressor* ac, uint32_t clip, LmxAnimCompInfo
 }
 
 int lmx_animcomp_read_clip(LmxAnimCompressor* ac, uint32_t clip, LmxAnimCompOutput* out) {
-	LMX_ANIMCOMP_ENTER(ac);
+	LMX_ENTER(ac);
 	if (!ac->ran) return fail(ctx, LMX_ERR_NOT_BUILT, "animcomp: no run on this batch");
 	if (!out || clip >= ac->n_clips) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "animcomp: null out, or clip %u of %u", clip, ac->n_clips);
 	const LmxAnimCompInfo& info = ac->h_infos[clip];
@@ -286,7 +268,7 @@ int lmx_animcomp_read_clip(LmxAnimCompressor* ac, uint32_t clip, LmxAnimCompOutp
 }
 
 int lmx_animcomp_device_outputs(LmxAnimCompressor* ac, LmxAnimCompDevice* out, uint32_t* bone_offset, uint64_t* translation_offset, uint64_t* rotation_offset) {
-	LMX_ANIMCOMP_ENTER(ac);
+	LMX_ENTER(ac);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (!ac->n_clips) return fail(ctx, LMX_ERR_NOT_BUILT, "animcomp: no batch");
 	memset(out, 0, sizeof(*out));

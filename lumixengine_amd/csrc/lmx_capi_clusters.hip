@@ -51,10 +51,7 @@ int clusters_pass(LmxContext* ctx, const LmxClusterView* cv, const int32_t* d_li
 	memset(&d, 0, sizeof(d));
 	if (int rc = bind_entity_transforms(ctx, d)) return rc;
 	list_cap = std::min<size_t>(list_cap, 1u << 30);
-	if (cl.d_ranges.cap < std::max<size_t>(list_cap, 1)) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a pass of the previous view may still read the old ranges)
-		LMX_HIP(ctx, cl.d_ranges.reserve(std::max<size_t>(list_cap, 1)));
-	}
+	if (int rc = Grow{ctx}(cl.d_ranges, std::max<size_t>(list_cap, 1))) return rc; // (a pass of the previous view may still read the old ranges)
 	d.list = d_list; d.list_count = d_count; d.list_cap = (uint32_t)list_cap;
 	d.light_tab = cl.d_light_tab.p; d.n_light_tab = cl.n_light_tab;
 	if (cl.have_atlas) { d.atlas = cl.d_atlas.p; d.n_atlas = cl.n_atlas; }

@@ -142,27 +142,14 @@ void rebuild_live(LmxGrass* g) {
 
 extern "C" {
 
-int lmx_grass_create(LmxContext* ctx, LmxGrass** out) {
-	LMX_CHECK_CTX(ctx);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LmxGrass* g = new (std::nothrow) LmxGrass();
-	if (!g) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "grass: host allocation failed");
-	g->ctx = ctx;
-	*out = g;
-	return LMX_OK;
-}
+int lmx_grass_create(LmxContext* ctx, LmxGrass** out) { return object_create(ctx, out, "grass"); }
 
 void lmx_grass_destroy(LmxGrass* g) {
-	if (!g) return;
-	(void)hipSetDevice(g->ctx->device);
-	(void)hipStreamSynchronize(g->ctx->stream);
-	delete g;
+	if (g) object_destroy(g);
 }
 
 int lmx_grass_set_terrains(LmxGrass* g, uint32_t n, const LmxGrassTerrain* terrains) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (n && !terrains) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null terrain table");
 	if (n > LMX_GRASS_MAX_TERRAINS) return fail(ctx, LMX_ERR_CAPACITY, "%u terrains: at most %d", n, LMX_GRASS_MAX_TERRAINS);
 	std::vector<GrassTerrainDev> recs(n);
@@ -224,9 +211,7 @@ int lmx_grass_set_terrains(LmxGrass* g, uint32_t n, const LmxGrassTerrain* terra
 }
 
 int lmx_grass_invalidate(LmxGrass* g, uint32_t terrain) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (terrain != 0xffffffffu && terrain >= g->terrains.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "unknown terrain %u (%zu set)", terrain, g->terrains.size());
 	for (uint32_t k = 0; k < g->terrains.size(); ++k)
 		if (terrain == 0xffffffffu || terrain == k) drop_terrain_quads(g, k);
@@ -235,9 +220,7 @@ int lmx_grass_invalidate(LmxGrass* g, uint32_t terrain) {
 }
 
 int lmx_grass_set_positions(LmxGrass* g, uint32_t n, const double* pos_xyz) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (n > g->terrains.size() || (n && !pos_xyz)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "%u positions for %zu terrains", n, g->terrains.size());
 	for (uint32_t k = 0; k < n; ++k)
 		for (int c = 0; c < 3; ++c) g->terrains[k].pos[c] = pos_xyz[3 * (size_t)k + c];
@@ -246,9 +229,7 @@ int lmx_grass_set_positions(LmxGrass* g, uint32_t n, const double* pos_xyz) {
 }
 
 int lmx_grass_reserve(LmxGrass* g, uint32_t slots) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (slots > (1u << 20)) return fail(ctx, LMX_ERR_CAPACITY, "%u slots: at most 2^20 (64 GiB of instances)", slots);
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	LMX_HIP(ctx, g->d_pool.reserve(std::max<size_t>((size_t)slots * 2 * LMX_GRASS_SLOT_INSTANCES, 1)));
@@ -260,9 +241,7 @@ int lmx_grass_reserve(LmxGrass* g, uint32_t slots) {
 }
 
 int lmx_grass_update(LmxGrass* g, uint32_t frame, uint32_t n, const float* center_xz) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (!g->have_terrains) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_grass_set_terrains has not been called");
 	if (n != g->terrains.size() || (n && !center_xz)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "%u centres for %zu terrains", n, g->terrains.size());
 	// 1. what the call would do, without doing it: the quads it evicts, touches and creates
@@ -338,10 +317,7 @@ int lmx_grass_update(LmxGrass* g, uint32_t frame, uint32_t n, const float* cente
 		}
 	}
 	if (jobs.empty()) return LMX_OK;
-	if (g->d_jobs.cap < jobs.size()) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a launch may still read the old list)
-		LMX_HIP(ctx, g->d_jobs.reserve(jobs.size()));
-	}
+	if (int rc = Grow{ctx}(g->d_jobs, jobs.size())) return rc;
 	LMX_HIP(ctx, g->s_jobs.upload(g->d_jobs.p, jobs.data(), jobs.size(), ctx->stream));
 	GrassQuadsDevice d;
 	d.terrains = g->d_terrains.p; d.texels = g->d_texels.p; d.jobs = g->d_jobs.p; d.n_jobs = (uint32_t)jobs.size();
@@ -351,19 +327,14 @@ int lmx_grass_update(LmxGrass* g, uint32_t frame, uint32_t n, const float* cente
 }
 
 int lmx_grass_cull(LmxGrass* g, uint32_t n_views, const LmxGrassView* views) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (!n_views) return LMX_OK;
 	if (!views) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null views");
 	if (!g->have_terrains) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_grass_set_terrains has not been called");
 	if (n_views > LMX_MAX_VIEWS) return fail(ctx, LMX_ERR_CAPACITY, "%u views: at most %d", n_views, LMX_MAX_VIEWS);
 	if (g->live_dirty) {
 		rebuild_live(g);
-		if (g->d_live.cap < std::max<size_t>(g->live.size(), 1)) {
-			LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			LMX_HIP(ctx, g->d_live.reserve(std::max<size_t>(g->live.size(), 1)));
-		}
+		if (int rc = Grow{ctx}(g->d_live, std::max<size_t>(g->live.size(), 1))) return rc;
 		LMX_HIP(ctx, g->s_live.upload(g->d_live.p, g->live.data(), g->live.size(), ctx->stream));
 		g->live_dirty = false;
 	}
@@ -376,12 +347,10 @@ int lmx_grass_cull(LmxGrass* g, uint32_t n_views, const LmxGrassView* views) {
 	}
 	const uint32_t n_live = (uint32_t)g->live.size();
 	const uint32_t stride = std::max<uint32_t>(n_live, 1);
-	if (g->d_views.cap < n_views || g->d_counts.cap < n_views || g->d_draws.cap < (size_t)n_views * stride) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, g->d_views.reserve(n_views));
-		LMX_HIP(ctx, g->d_counts.reserve(n_views));
-		LMX_HIP(ctx, g->d_draws.reserve((size_t)n_views * stride));
-	}
+	Grow grow{ctx}; // (behind the copies of the live list and the positions: a Grow of its own)
+	if (int rc = grow(g->d_views, n_views)) return rc;
+	if (int rc = grow(g->d_counts, n_views)) return rc;
+	if (int rc = grow(g->d_draws, (size_t)n_views * stride)) return rc;
 	std::vector<GrassViewDev> vd(n_views);
 	for (uint32_t v = 0; v < n_views; ++v) {
 		memset(&vd[v], 0, sizeof(GrassViewDev));
@@ -403,9 +372,7 @@ int lmx_grass_cull(LmxGrass* g, uint32_t n_views, const LmxGrassView* views) {
 }
 
 int lmx_grass_read_quads(LmxGrass* g, LmxGrassQuad* out, uint32_t cap, uint32_t* out_n) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (g->live_dirty) rebuild_live(g); // (the device list goes up with the next cull: live_dirty stays set)
 	const uint32_t n = (uint32_t)g->live.size();
 	if (out_n) *out_n = n;
@@ -419,19 +386,14 @@ int lmx_grass_read_quads(LmxGrass* g, LmxGrassQuad* out, uint32_t cap, uint32_t*
 }
 
 int lmx_grass_read_instances(LmxGrass* g, uint32_t slot, LmxGrassInstance* out, uint32_t cap) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (slot >= g->n_slots) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "slot %u of %u", slot, g->n_slots);
-	if (cap < LMX_GRASS_SLOT_INSTANCES) return fail(ctx, LMX_ERR_CAPACITY, "a slot holds %d records, cap %u", LMX_GRASS_SLOT_INSTANCES, cap);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const LmxGrassInstance*)(g->d_pool.p + (size_t)slot * 2 * LMX_GRASS_SLOT_INSTANCES), LMX_GRASS_SLOT_INSTANCES);
+	return read_out(ctx, out, cap, (const LmxGrassInstance*)(g->d_pool.p + (size_t)slot * 2 * LMX_GRASS_SLOT_INSTANCES), LMX_GRASS_SLOT_INSTANCES, LMX_GRASS_SLOT_INSTANCES,
+		"records of a slot", NullOut::Refused);
 }
 
 int lmx_grass_write_instances(LmxGrass* g, uint32_t slot, const LmxGrassInstance* in, uint32_t n) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (slot >= g->n_slots || n > LMX_GRASS_SLOT_INSTANCES) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "slot %u of %u, %u records", slot, g->n_slots, n);
 	if (n && !in) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null records");
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -440,34 +402,23 @@ int lmx_grass_write_instances(LmxGrass* g, uint32_t slot, const LmxGrassInstance
 }
 
 int lmx_grass_read_draws(LmxGrass* g, uint32_t view, LmxGrassDraw* out, uint32_t cap, uint32_t* out_n) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (!g->culled) return fail(ctx, LMX_ERR_NOT_BUILT, "no lmx_grass_cull has run");
 	if (view >= g->n_views) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "view %u of %u", view, g->n_views);
 	LmxGrassCounts c;
 	if (int rc = read_now(ctx, &c, (const LmxGrassCounts*)g->d_counts.p + view, 1)) return rc;
 	if (out_n) *out_n = c.draws;
-	if (cap < c.draws) return fail(ctx, LMX_ERR_CAPACITY, "%u draws, cap %u", c.draws, cap);
-	if (!c.draws) return LMX_OK;
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const LmxGrassDraw*)g->d_draws.p + (size_t)view * g->draw_stride, c.draws);
+	return read_out(ctx, out, cap, (const LmxGrassDraw*)g->d_draws.p + (size_t)view * g->draw_stride, c.draws, c.draws, "draws", NullOut::Refused);
 }
 
 int lmx_grass_counts(LmxGrass* g, LmxGrassCounts* out, uint32_t cap_views) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (!g->culled) return fail(ctx, LMX_ERR_NOT_BUILT, "no lmx_grass_cull has run");
-	if (cap_views < g->n_views) return fail(ctx, LMX_ERR_CAPACITY, "%u views, cap %u", g->n_views, cap_views);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const LmxGrassCounts*)g->d_counts.p, g->n_views);
+	return read_out(ctx, out, cap_views, (const LmxGrassCounts*)g->d_counts.p, g->n_views, g->n_views, "views' counts", NullOut::Refused); // (a cull has at least one view)
 }
 
 int lmx_grass_device_outputs(LmxGrass* g, LmxGrassDevice* out) {
-	if (!g) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = g->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(g);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (!g->n_slots) return fail(ctx, LMX_ERR_NOT_BUILT, "lmx_grass_reserve has not been called");
 	memset(out, 0, sizeof(*out));

@@ -166,29 +166,17 @@ int im_ray_tables(LmxInstancedModels* im, ImRayTables* out) {
 
 extern "C" {
 
-int lmx_im_create(LmxContext* ctx, LmxInstancedModels** out) {
-	LMX_CHECK_CTX(ctx);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LmxInstancedModels* im = new (std::nothrow) LmxInstancedModels();
-	if (!im) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "instanced models: host allocation failed");
-	im->ctx = ctx;
-	*out = im;
-	return LMX_OK;
-}
+int lmx_im_create(LmxContext* ctx, LmxInstancedModels** out) { return object_create(ctx, out, "instanced models"); }
 
 void lmx_im_destroy(LmxInstancedModels* im) {
 	if (!im) return;
-	(void)hipSetDevice(im->ctx->device);
-	(void)hipStreamSynchronize(im->ctx->stream);
 	if (im->ctx->rays.im == im) im->ctx->rays.im = nullptr; // (the ray casts no longer see it)
-	delete im;
+	object_destroy(im);
 }
 
 int lmx_im_set_model(LmxInstancedModels* im, uint32_t model, const float lod_distances[4], const LmxLodIndices lod_indices[5], float origin_radius,
 	uint32_t mesh_count, const uint32_t* indices_count) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (!lod_distances || !lod_indices || (mesh_count && !indices_count)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null model array");
 	if (model > im->models.size() || model >= LMX_IM_MAX_MODELS) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "model %u: ids are dense (%zu registered)", model, im->models.size());
 	if (mesh_count > LMX_IM_MAX_MESHES) return fail(ctx, LMX_ERR_CAPACITY, "%u meshes: encodeInstancedModels takes fewer than 32", mesh_count);
@@ -215,9 +203,7 @@ int lmx_im_set_model(LmxInstancedModels* im, uint32_t model, const float lod_dis
 }
 
 int lmx_im_set_instances(LmxInstancedModels* im, uint32_t model, uint32_t n, const LmxImInstance* instances) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (model >= im->models.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "unknown model %u (%zu registered)", model, im->models.size());
 	if (n && !instances) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null instances");
 	if ((uint64_t)n + im->total_instances - im->models[model].n > 0x7fffffffull) return fail(ctx, LMX_ERR_CAPACITY, "more than 2^31 instances");
@@ -234,9 +220,7 @@ int lmx_im_set_instances(LmxInstancedModels* im, uint32_t model, uint32_t n, con
 }
 
 int lmx_im_set_origins(LmxInstancedModels* im, uint32_t n_models, const double* pos_xyz) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (n_models > im->models.size() || (n_models && !pos_xyz)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "%u origins for %zu models", n_models, im->models.size());
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	for (uint32_t m = 0; m < n_models; ++m)
@@ -246,9 +230,7 @@ int lmx_im_set_origins(LmxInstancedModels* im, uint32_t n_models, const double* 
 }
 
 int lmx_im_run(LmxInstancedModels* im, uint32_t view_slot, const LmxImView* view, const LmxShiftedFrustum* frustum) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (!view || !frustum) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null view / frustum");
 	if (view_slot >= LMX_MAX_VIEWS) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "view slot %u out of range (LMX_MAX_VIEWS = %d)", view_slot, LMX_MAX_VIEWS);
 	if (im->dirty) {
@@ -257,13 +239,10 @@ int lmx_im_run(LmxInstancedModels* im, uint32_t view_slot, const LmxImView* view
 	}
 	LmxInstancedModels::Slot& s = im->slots[view_slot];
 	const uint32_t nm = (uint32_t)im->models.size();
-	const size_t want_records = std::max<size_t>(2 * im->total_instances, 1);
-	if (s.records.cap < want_records || s.indirect.cap < std::max<size_t>(im->n_indirect, 1) || s.counts.cap < std::max<size_t>(nm, 1)) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, s.records.reserve(want_records));
-		LMX_HIP(ctx, s.indirect.reserve(std::max<size_t>(im->n_indirect, 1)));
-		LMX_HIP(ctx, s.counts.reserve(std::max<size_t>(nm, 1)));
-	}
+	Grow grow{ctx};
+	if (int rc = grow(s.records, std::max<size_t>(2 * im->total_instances, 1))) return rc;
+	if (int rc = grow(s.indirect, std::max<size_t>(im->n_indirect, 1))) return rc;
+	if (int rc = grow(s.counts, std::max<size_t>(nm, 1))) return rc;
 	if (!im->d_masks.p) LMX_HIP(ctx, im->d_masks.reserve(1));
 	ImViewDev v;
 	memset(&v, 0, sizeof(v));
@@ -286,9 +265,7 @@ int lmx_im_run(LmxInstancedModels* im, uint32_t view_slot, const LmxImView* view
 }
 
 int lmx_im_read_grid(LmxInstancedModels* im, uint32_t model, LmxImGrid* out) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (model >= im->models.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "unknown model %u", model);
 	ImGridDev g;
@@ -312,9 +289,7 @@ int lmx_im_read_grid(LmxInstancedModels* im, uint32_t model, LmxImGrid* out) {
 }
 
 int lmx_im_read_instances(LmxInstancedModels* im, uint32_t model, LmxImInstance* out, uint32_t cap) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (model >= im->models.size()) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "unknown model %u", model);
 	const uint32_t n = im->models[model].n;
 	if (cap < n) return fail(ctx, LMX_ERR_CAPACITY, "model %u holds %u instances, cap %u", model, n, cap);
@@ -340,22 +315,15 @@ int lmx_im_read_instances(LmxInstancedModels* im, uint32_t model, LmxImInstance*
 }
 
 int lmx_im_counts(LmxInstancedModels* im, uint32_t view_slot, LmxImCounts* out, uint32_t cap_models) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (int rc = im_check_slot(im, view_slot)) return rc;
 	const LmxInstancedModels::Slot& s = im->slots[view_slot];
-	if (cap_models < s.n_models) return fail(ctx, LMX_ERR_CAPACITY, "%u models, cap %u", s.n_models, cap_models);
-	if (!s.n_models) return LMX_OK;
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	static_assert(sizeof(ImCountsDev) == sizeof(LmxImCounts), "ImCountsDev mirrors LmxImCounts");
-	return read_now(ctx, (ImCountsDev*)out, (const ImCountsDev*)s.counts.p, s.n_models);
+	return read_out(ctx, (ImCountsDev*)out, cap_models, (const ImCountsDev*)s.counts.p, s.n_models, s.n_models, "models' counts", NullOut::Refused);
 }
 
 int lmx_im_read_records(LmxInstancedModels* im, uint32_t view_slot, LmxImInstance* out, uint32_t cap, uint32_t* out_n) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (int rc = im_check_slot(im, view_slot)) return rc;
 	const LmxInstancedModels::Slot& s = im->slots[view_slot];
 	std::vector<LmxImCounts> c(std::max<uint32_t>(s.n_models, 1));
@@ -363,23 +331,15 @@ int lmx_im_read_records(LmxInstancedModels* im, uint32_t view_slot, LmxImInstanc
 	size_t total = 0;
 	for (uint32_t m = 0; m < s.n_models; ++m) total += (size_t)c[m].bin_count[0] + c[m].bin_count[1] + c[m].bin_count[2] + c[m].bin_count[3];
 	if (out_n) *out_n = (uint32_t)total;
-	if (cap < total) return fail(ctx, LMX_ERR_CAPACITY, "%zu records, cap %u", total, cap);
-	if (!total) return LMX_OK;
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const LmxImInstance*)s.records.p, total);
+	return read_out(ctx, out, cap, (const LmxImInstance*)s.records.p, total, total, "records", NullOut::Refused);
 }
 
 int lmx_im_read_indirect(LmxInstancedModels* im, uint32_t view_slot, LmxImIndirect* out, uint32_t cap, uint32_t* out_n) {
-	if (!im) return LMX_ERR_INVALID_ARGUMENT;
-	LmxContext* ctx = im->ctx;
-	LMX_CHECK_CTX(ctx);
+	LMX_ENTER(im);
 	if (int rc = im_check_slot(im, view_slot)) return rc;
 	const LmxInstancedModels::Slot& s = im->slots[view_slot];
 	if (out_n) *out_n = s.n_indirect;
-	if (cap < s.n_indirect) return fail(ctx, LMX_ERR_CAPACITY, "%u indirect records, cap %u", s.n_indirect, cap);
-	if (!s.n_indirect) return LMX_OK;
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const LmxImIndirect*)s.indirect.p, s.n_indirect);
+	return read_out(ctx, out, cap, (const LmxImIndirect*)s.indirect.p, s.n_indirect, s.n_indirect, "indirect records", NullOut::Refused);
 }
 
 int lmx_im_device_outputs(LmxInstancedModels* im, uint32_t view_slot, const void** d_records, const void** d_indirect, const void** d_counts) {

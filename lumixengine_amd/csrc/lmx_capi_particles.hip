@@ -107,9 +107,8 @@ static_assert(sizeof(LmxParticlesCounts) == sizeof(ParticleStateDev), "lmx_parti
 namespace {
 
 #define LMX_CHECK_PARTICLES(ps)                                                         \
-	if (!(ps) || (ps)->magic != PARTICLES_MAGIC) return LMX_ERR_INVALID_ARGUMENT;      \
-	LmxContext* ctx = (ps)->ctx;                                                        \
-	LMX_CHECK_CTX(ctx)
+	if ((ps) && (ps)->magic != PARTICLES_MAGIC) return LMX_ERR_INVALID_ARGUMENT;       \
+	LMX_ENTER(ps)
 
 int find_emitter(LmxParticles* ps, uint32_t system, uint32_t emitter, uint32_t* out) {
 	if (system >= ps->systems.size()) return fail(ps->ctx, LMX_ERR_INVALID_ARGUMENT, "particle system %u: %zu registered", system, ps->systems.size());
@@ -418,22 +417,12 @@ int build(LmxParticles* ps) {
 
 extern "C" {
 
-int lmx_particles_create(LmxContext* ctx, LmxParticles** out) {
-	LMX_CHECK_CTX(ctx);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LmxParticles* ps = new (std::nothrow) LmxParticles();
-	if (!ps) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "particles: host allocation failed");
-	ps->ctx = ctx;
-	*out = ps;
-	return LMX_OK;
-}
+int lmx_particles_create(LmxContext* ctx, LmxParticles** out) { return object_create(ctx, out, "particles"); }
 
 void lmx_particles_destroy(LmxParticles* ps) {
 	if (!ps || ps->magic != PARTICLES_MAGIC) return;
-	(void)hipSetDevice(ps->ctx->device);
-	(void)hipStreamSynchronize(ps->ctx->stream);
 	ps->magic = 0;
-	delete ps;
+	object_destroy(ps);
 }
 
 int lmx_particles_add_system(LmxParticles* ps, uint32_t n_emitters, uint32_t n_globals, uint32_t* out_system) {

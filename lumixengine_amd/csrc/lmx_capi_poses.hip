@@ -59,10 +59,7 @@ int poses_pass(LmxContext* ctx, const int32_t* d_list, const uint32_t* d_count, 
 	if (int rc = poses_reserve(ctx)) return rc;
 	if (int rc = poses_grow_tables(ctx)) return rc;
 	list_cap = std::min<size_t>(list_cap, 1u << 31);
-	if (ps.d_entries.cap < list_cap) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a pass of the previous view may still read the old records)
-		LMX_HIP(ctx, ps.d_entries.reserve(list_cap));
-	}
+	if (int rc = Grow{ctx}(ps.d_entries, list_cap)) return rc; // (a pass of the previous view may still read the old records)
 	PosesDevice d;
 	memset(&d, 0, sizeof(d));
 	d.list = d_list; d.list_count = d_count; d.list_cap = (uint32_t)list_cap;

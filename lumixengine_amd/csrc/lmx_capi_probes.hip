@@ -19,11 +19,6 @@ struct LmxProbeBaker {
 
 namespace {
 
-#define LMX_PROBES_ENTER(pb)                           \
-	if (!(pb)) return LMX_ERR_INVALID_ARGUMENT;        \
-	LmxContext* ctx = (pb)->ctx;                       \
-	LMX_CHECK_CTX(ctx)
-
 // the first channel of `n` floats that is not finite, or n
 size_t first_non_finite(const float* p, size_t n) {
 	for (size_t i = 0; i < n; ++i)
@@ -31,15 +26,13 @@ size_t first_non_finite(const float* p, size_t n) {
 	return n;
 }
 
+size_t mip_floats(const LmxProbeBaker* pb) { return 4 * (size_t)probe_mip_offset(pb->size, probe_log2(pb->size) + 1) * pb->n; }
+
 int run_mips(LmxProbeBaker* pb) {
 	LmxContext* ctx = pb->ctx;
 	if (!probe_is_pow2(pb->size) || pb->size < 16) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "probes: a reflection probe's size is a power of two of 16 or more, not %u", pb->size);
 	if (pb->n > 65535) return fail(ctx, LMX_ERR_CAPACITY, "probes: %u reflection probes in one batch (65535 at most)", pb->n);
-	const size_t floats = 4 * (size_t)probe_mip_offset(pb->size, probe_log2(pb->size) + 1) * pb->n;
-	if (pb->d_mips.cap < floats) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a queued kernel may still read the buffer a reserve frees)
-		LMX_HIP(ctx, pb->d_mips.reserve(floats));
-	}
+	if (int rc = Grow{ctx}(pb->d_mips, mip_floats(pb))) return rc;
 	LMX_HIP(ctx, launch_probe_mips(ctx->stream, pb->d_rgba.p, pb->n, pb->size, pb->d_mips.p));
 	pb->has_mips = true;
 	return LMX_OK;
@@ -75,25 +68,14 @@ int lmx_probes_batch_bytes(uint32_t n, uint32_t size, uint64_t* out) {
 	return LMX_OK;
 }
 
-int lmx_probes_create(LmxContext* ctx, LmxProbeBaker** out) {
-	LMX_CHECK_CTX(ctx);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LmxProbeBaker* pb = new (std::nothrow) LmxProbeBaker();
-	if (!pb) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "probes: host allocation failed");
-	pb->ctx = ctx;
-	*out = pb;
-	return LMX_OK;
-}
+int lmx_probes_create(LmxContext* ctx, LmxProbeBaker** out) { return object_create(ctx, out, "probes"); }
 
 void lmx_probes_destroy(LmxProbeBaker* pb) {
-	if (!pb) return;
-	(void)hipSetDevice(pb->ctx->device);
-	(void)hipStreamSynchronize(pb->ctx->stream);
-	delete pb;
+	if (pb) object_destroy(pb);
 }
 
 int lmx_probes_set_cubemaps(LmxProbeBaker* pb, uint32_t n, uint32_t size, const float* rgba) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (n == 0 || size == 0) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "probes: a batch of %u cubemaps of size %u", n, size);
 	const uint64_t bytes = probe_batch_bytes(n, size);
 	if (bytes == 0) return fail(ctx, LMX_ERR_CAPACITY, "probes: %u cubemaps of size %u are above the batch cap of %llu bytes", n, size, (unsigned long long)PROBES_MAX_BATCH_BYTES);
@@ -109,7 +91,7 @@ int lmx_probes_set_cubemaps(LmxProbeBaker* pb, uint32_t n, uint32_t size, const 
 }
 
 int lmx_probes_sh_run(LmxProbeBaker* pb) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->n) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: sh_run before set_cubemaps");
 	if (pb->table_size != pb->size) {
 		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a queued kernel may still read the table a reserve frees)
@@ -118,31 +100,26 @@ int lmx_probes_sh_run(LmxProbeBaker* pb) {
 		LMX_HIP(ctx, launch_sh_table(ctx->stream, pb->size, pb->d_sh_table.p));
 		pb->table_size = pb->size;
 	}
-	if (pb->d_sh.cap < 27 * (size_t)pb->n) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, pb->d_sh.reserve(27 * (size_t)pb->n));
-	}
+	if (int rc = Grow{ctx}(pb->d_sh, 27 * (size_t)pb->n)) return rc; // (behind the table's launch: a Grow of its own)
 	LMX_HIP(ctx, launch_sh_accumulate(ctx->stream, pb->d_rgba.p, pb->d_sh_table.p, pb->n, pb->size, pb->d_sh.p));
 	pb->has_sh = true;
 	return LMX_OK;
 }
 
 int lmx_probes_read_sh(LmxProbeBaker* pb, float* out, uint32_t cap_probes) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->has_sh) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: no sh_run on this batch");
-	if (cap_probes < pb->n) return fail(ctx, LMX_ERR_CAPACITY, "probes: %u probes, cap %u", pb->n, cap_probes);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const float*)pb->d_sh.p, 27 * (size_t)pb->n);
+	return read_out(ctx, out, 27 * (size_t)cap_probes, (const float*)pb->d_sh.p, 27 * (size_t)pb->n, 27 * (size_t)pb->n, "floats of SH (27 per probe)", NullOut::Refused);
 }
 
 int lmx_probes_mips_run(LmxProbeBaker* pb) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->n) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: mips_run before set_cubemaps");
 	return run_mips(pb);
 }
 
 int lmx_probes_filter_run(LmxProbeBaker* pb) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->n) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: filter_run before set_cubemaps");
 	if (int rc = run_mips(pb)) return rc;
 	if (!pb->has_ggx) {
@@ -152,11 +129,9 @@ int lmx_probes_filter_run(LmxProbeBaker* pb) {
 		pb->has_ggx = true;
 	}
 	const size_t texels = filtered_texels(pb);
-	if (pb->d_filtered.cap < 4 * texels || pb->d_rgbm.cap < 4 * texels) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		LMX_HIP(ctx, pb->d_filtered.reserve(4 * texels));
-		LMX_HIP(ctx, pb->d_rgbm.reserve(4 * texels));
-	}
+	Grow grow{ctx};
+	if (int rc = grow(pb->d_filtered, 4 * texels)) return rc;
+	if (int rc = grow(pb->d_rgbm, 4 * texels)) return rc;
 	LMX_HIP(ctx, launch_probe_filter(ctx->stream, chain_of(pb), pb->d_ggx.p, pb->d_filtered.p));
 	LMX_HIP(ctx, launch_probe_rgbm(ctx->stream, pb->d_filtered.p, pb->n, pb->size, pb->d_rgbm.p));
 	pb->has_filtered = true;
@@ -164,7 +139,7 @@ int lmx_probes_filter_run(LmxProbeBaker* pb) {
 }
 
 int lmx_probes_sample(LmxProbeBaker* pb, uint32_t probe, uint32_t n, const float* dirs, const float* lods, float* out) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->has_mips) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: sample before mips_run / filter_run");
 	if (probe >= pb->n) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "probes: probe %u of %u", probe, pb->n);
 	if (!n) return LMX_OK;
@@ -176,40 +151,34 @@ int lmx_probes_sample(LmxProbeBaker* pb, uint32_t probe, uint32_t n, const float
 	}
 	if (int rc = upload_settled(ctx, pb->d_dirs, dirs, 3 * (size_t)n)) return rc;
 	if (int rc = upload_settled(ctx, pb->d_lods, lods, (size_t)n)) return rc;
+	// (the stream has drained: nothing reads the buffer a reserve frees)
 	LMX_HIP(ctx, pb->d_sampled.reserve(3 * (size_t)n));
 	LMX_HIP(ctx, launch_probe_sample(ctx->stream, chain_of(pb), probe, pb->d_dirs.p, pb->d_lods.p, n, pb->d_sampled.p));
 	return read_now(ctx, out, (const float*)pb->d_sampled.p, 3 * (size_t)n);
 }
 
 int lmx_probes_read_mips(LmxProbeBaker* pb, float* out, uint64_t cap_floats) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->has_mips) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: no mips_run on this batch");
-	const size_t floats = 4 * (size_t)probe_mip_offset(pb->size, probe_log2(pb->size) + 1) * pb->n;
-	if (cap_floats < floats) return fail(ctx, LMX_ERR_CAPACITY, "probes: %zu floats of mips, cap %llu", floats, (unsigned long long)cap_floats);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const float*)pb->d_mips.p, floats);
+	return read_out(ctx, out, (size_t)cap_floats, (const float*)pb->d_mips.p, mip_floats(pb), mip_floats(pb), "floats of mips", NullOut::Refused);
 }
 
 int lmx_probes_read_filtered(LmxProbeBaker* pb, float* out, uint64_t cap_floats) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->has_filtered) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: no filter_run on this batch");
 	const size_t floats = 4 * filtered_texels(pb);
-	if (cap_floats < floats) return fail(ctx, LMX_ERR_CAPACITY, "probes: %zu filtered floats, cap %llu", floats, (unsigned long long)cap_floats);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const float*)pb->d_filtered.p, floats);
+	return read_out(ctx, out, (size_t)cap_floats, (const float*)pb->d_filtered.p, floats, floats, "filtered floats", NullOut::Refused);
 }
 
 int lmx_probes_read_rgbm(LmxProbeBaker* pb, uint8_t* out, uint64_t cap_bytes) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!pb->has_filtered) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: no filter_run on this batch");
 	const size_t bytes = 4 * filtered_texels(pb);
-	if (cap_bytes < bytes) return fail(ctx, LMX_ERR_CAPACITY, "probes: %zu RGBM bytes, cap %llu", bytes, (unsigned long long)cap_bytes);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const uint8_t*)pb->d_rgbm.p, bytes);
+	return read_out(ctx, out, (size_t)cap_bytes, (const uint8_t*)pb->d_rgbm.p, bytes, bytes, "RGBM bytes", NullOut::Refused);
 }
 
 int lmx_probes_device_outputs(LmxProbeBaker* pb, LmxProbesDevice* out) {
-	LMX_PROBES_ENTER(pb);
+	LMX_ENTER(pb);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (!pb->n) return fail(ctx, LMX_ERR_NOT_BUILT, "probes: no cubemaps");
 	out->d_cubemaps = pb->d_rgba.p;

@@ -35,11 +35,6 @@ namespace {
 
 constexpr size_t TC_GUARD_WORDS = 64; // behind the blocks of a run: filled, never written by a kernel (lmx_context.h, fill_guard)
 
-#define LMX_TEXCOMP_ENTER(tc)                          \
-	if (!(tc)) return LMX_ERR_INVALID_ARGUMENT;        \
-	LmxContext* ctx = (tc)->ctx;                       \
-	LMX_CHECK_CTX(ctx)
-
 uint32_t words_per_block(int format) { return format == LMX_TEX_BC1 || format == LMX_TEX_BC4 ? 2u : 4u; }
 bool format_ok(int format) { return format == LMX_TEX_BC1 || format == LMX_TEX_BC3 || format == LMX_TEX_BC4 || format == LMX_TEX_BC5; }
 
@@ -75,6 +70,18 @@ int lay_out(uint32_t n, const LmxTexImage* descs, std::vector<TcImage>* images, 
 		*blocks += (uint64_t)((descs[i].w + 3) >> 2) * ((descs[i].h + 3) >> 2); // (<= 2^28 pixels: at most 2^28 blocks)
 	}
 	return LMX_OK;
+}
+
+// the search tables and the mip filter's, built on the host once per compressor
+int upload_tables(LmxTexCompressor* tc) {
+	LmxContext* ctx = tc->ctx;
+	std::unique_ptr<TcTables> t(new (std::nothrow) TcTables());
+	if (!t) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "texcomp: host allocation failed");
+	tc_build_tables(t.get());
+	if (int rc = upload_settled(ctx, tc->d_tables, (const TcTables*)t.get(), (size_t)1)) return rc;
+	TmTables mip_tables;
+	tm_build_tables(&mip_tables);
+	return upload_settled(ctx, tc->d_mip_tables, (const TmTables*)&mip_tables, (size_t)1);
 }
 
 // the descriptors of a new batch go up on the stream, without a host wait unless the batch before is still being copied
@@ -266,31 +273,21 @@ int lmx_texcomp_encode_host(int format, uint32_t n_blocks, const uint8_t* rgba, 
 }
 
 int lmx_texcomp_create(LmxContext* ctx, LmxTexCompressor** out) {
-	LMX_CHECK_CTX(ctx);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	*out = nullptr;
-	std::unique_ptr<LmxTexCompressor> tc(new (std::nothrow) LmxTexCompressor());
-	std::unique_ptr<TcTables> t(new (std::nothrow) TcTables());
-	if (!tc || !t) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "texcomp: host allocation failed");
-	tc->ctx = ctx;
-	tc_build_tables(t.get());
-	if (int rc = upload_settled(ctx, tc->d_tables, (const TcTables*)t.get(), (size_t)1)) return rc;
-	TmTables mip_tables;
-	tm_build_tables(&mip_tables);
-	if (int rc = upload_settled(ctx, tc->d_mip_tables, (const TmTables*)&mip_tables, (size_t)1)) return rc;
-	*out = tc.release();
-	return LMX_OK;
+	if (int rc = object_create(ctx, out, "texcomp")) return rc;
+	const int rc = upload_tables(*out);
+	if (rc) { // (no handle to an object without its tables)
+		object_destroy(*out);
+		*out = nullptr;
+	}
+	return rc;
 }
 
 void lmx_texcomp_destroy(LmxTexCompressor* tc) {
-	if (!tc) return;
-	(void)hipSetDevice(tc->ctx->device);
-	(void)hipStreamSynchronize(tc->ctx->stream);
-	delete tc;
+	if (tc) object_destroy(tc);
 }
 
 int lmx_texcomp_set_images(LmxTexCompressor* tc, uint32_t n, const LmxTexImage* descs, const uint8_t* rgba) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (n && descs && !rgba) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "texcomp: null pixels");
 	uint64_t pixels;
 	if (int rc = take_batch(tc, n, descs, &pixels)) return rc;
@@ -310,7 +307,7 @@ int lmx_texcomp_set_images(LmxTexCompressor* tc, uint32_t n, const LmxTexImage* 
 }
 
 int lmx_texcomp_set_images_device(LmxTexCompressor* tc, uint32_t n, const LmxTexImage* descs, const uint8_t* d_rgba) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (n && descs && !d_rgba) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "texcomp: null device pixels");
 	if ((uintptr_t)d_rgba & 3u) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "texcomp: device pixels are read as 32-bit words: the pointer must be a multiple of 4");
 	uint64_t pixels;
@@ -320,7 +317,7 @@ int lmx_texcomp_set_images_device(LmxTexCompressor* tc, uint32_t n, const LmxTex
 }
 
 int lmx_texcomp_set_from_probes(LmxTexCompressor* tc, LmxProbeBaker* pb) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (!pb) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "texcomp: null probe baker");
 	LmxProbesDevice dev;
 	if (int rc = lmx_probes_device_outputs(pb, &dev)) return rc == LMX_ERR_NOT_BUILT ? fail(ctx, rc, "texcomp: set_from_probes before filter_run") : rc;
@@ -342,16 +339,13 @@ int lmx_texcomp_set_from_probes(LmxTexCompressor* tc, LmxProbeBaker* pb) {
 }
 
 int lmx_texcomp_run(LmxTexCompressor* tc, int format) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (!format_ok(format)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "texcomp: unknown format %d", format);
 	if (!tc->n_images || !tc->d_rgba) return fail(ctx, LMX_ERR_NOT_BUILT, "texcomp: run before a batch was set");
 	if (tc->chains && !tc->mips_done) return fail(ctx, LMX_ERR_NOT_BUILT, "texcomp: run on chains before generate_mips");
 	const uint32_t stride = words_per_block(format);
 	const size_t words = (size_t)tc->n_blocks * stride;
-	if (tc->d_out.cap < words + TC_GUARD_WORDS) {
-		LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a queued kernel may still write the buffer a reserve frees)
-		LMX_HIP(ctx, tc->d_out.reserve(words + TC_GUARD_WORDS));
-	}
+	if (int rc = Grow{ctx}(tc->d_out, words + TC_GUARD_WORDS)) return rc;
 	tc->format = -1;
 	LMX_HIP(ctx, fill_guard(tc->d_out.p + words, TC_GUARD_WORDS, ctx->stream));
 	const TcBatch batch{tc->d_images.p, tc->d_rgba, tc->n_images, tc->n_blocks};
@@ -369,7 +363,7 @@ int lmx_texcomp_run(LmxTexCompressor* tc, int format) {
 }
 
 int lmx_texcomp_read(LmxTexCompressor* tc, uint8_t* out, uint64_t cap_bytes) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (tc->format < 0) return fail(ctx, LMX_ERR_NOT_BUILT, "texcomp: no run on this batch");
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	const size_t used = (size_t)tc->n_blocks * words_per_block(tc->format) * 4;
@@ -379,7 +373,7 @@ int lmx_texcomp_read(LmxTexCompressor* tc, uint8_t* out, uint64_t cap_bytes) {
 }
 
 int lmx_texcomp_device_outputs(LmxTexCompressor* tc, LmxTexCompDevice* out) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (!tc->n_images) return fail(ctx, LMX_ERR_NOT_BUILT, "texcomp: no batch");
 	out->d_rgba = reinterpret_cast<const uint8_t*>(tc->d_rgba);
@@ -405,17 +399,17 @@ int lmx_texcomp_chain_bytes(uint32_t n, uint32_t w, uint32_t h, uint64_t* out) {
 }
 
 int lmx_texcomp_set_chains(LmxTexCompressor* tc, uint32_t n, uint32_t w, uint32_t h, const uint8_t* rgba) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	return set_chains(tc, n, w, h, rgba, false);
 }
 
 int lmx_texcomp_set_chains_device(LmxTexCompressor* tc, uint32_t n, uint32_t w, uint32_t h, const uint8_t* d_rgba) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	return set_chains(tc, n, w, h, d_rgba, true);
 }
 
 int lmx_texcomp_generate_mips(LmxTexCompressor* tc, const LmxTexMipOptions* options) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (!options) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "texcomp: null options");
 	if (!mode_ok(options->mode)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "texcomp: unknown mip mode %d", options->mode);
 	if (!tc->chains) return fail(ctx, LMX_ERR_NOT_BUILT, "texcomp: generate_mips without set_chains");
@@ -431,11 +425,9 @@ int lmx_texcomp_generate_mips(LmxTexCompressor* tc, const LmxTexMipOptions* opti
 	uint32_t* d_count = nullptr;
 	if (coverage) {
 		const size_t bins = (size_t)first_small * n * 256; // of levels 1 .. first_small; the tail keeps its bins in LDS
-		if (tc->d_hist.cap < bins + 1) {
-			LMX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a queued kernel may still use the buffer a reserve frees)
-			tc->images_in_flight = false;
-			LMX_HIP(ctx, tc->d_hist.reserve(bins + 1));
-		}
+		Grow grow{ctx};
+		if (int rc = grow(tc->d_hist, bins + 1)) return rc;
+		if (grow.drained) tc->images_in_flight = false;
 		LMX_HIP(ctx, hipMemsetAsync(tc->d_hist.p, 0, (bins + 1) * sizeof(uint32_t), ctx->stream));
 		d_count = tc->d_hist.p + bins;
 		LMX_HIP(ctx, launch_mip_coverage(ctx->stream, tc->d_own.p, w * h, tm_coverage_ref(options->scale_coverage_ref), d_count)); // image (face 0, slice 0, mip 0) alone
@@ -481,7 +473,7 @@ int lmx_texcomp_generate_mips(LmxTexCompressor* tc, const LmxTexMipOptions* opti
 }
 
 int lmx_texcomp_read_pixels(LmxTexCompressor* tc, uint8_t* out, uint64_t cap_bytes) {
-	LMX_TEXCOMP_ENTER(tc);
+	LMX_ENTER(tc);
 	if (!tc->chains || !tc->mips_done) return fail(ctx, LMX_ERR_NOT_BUILT, "texcomp: read_pixels before set_chains and generate_mips");
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	const size_t used = 4 * (size_t)tm_chain_pixels(tc->chain_w, tc->chain_h) * tc->chain_n;

@@ -101,17 +101,13 @@ int raster_mesh(LmxVoxels* vox, const LmxVoxelsMesh& m) {
 int run_sample(LmxVoxels* vox, int mode, const float* packed_xyz, uint32_t n, float min_ao) {
 	LmxContext* ctx = vox->ctx;
 	if (int rc = upload_settled(ctx, vox->d_points, packed_xyz, 3 * (size_t)n)) return rc;
+	// (the stream has drained: nothing reads the buffers a reserve frees)
 	LMX_HIP(ctx, vox->d_out_u8.reserve(std::max<size_t>(n, 1)));
 	LMX_HIP(ctx, vox->d_out_f.reserve(std::max<size_t>(n, 1)));
 	LMX_HIP(ctx, vox->d_inside.reserve(std::max<size_t>(n, 1)));
 	LMX_HIP(ctx, launch_voxel_sample(ctx->stream, vox->g, mode, vox->d_voxels.p, vox->d_ao.p, vox->d_points.p, n, min_ao, vox->d_out_u8.p, vox->d_out_f.p, vox->d_inside.p));
 	return LMX_OK;
 }
-
-#define LMX_VOXELS_ENTER(vox)                          \
-	if (!(vox)) return LMX_ERR_INVALID_ARGUMENT;       \
-	LmxContext* ctx = (vox)->ctx;                      \
-	LMX_CHECK_CTX(ctx)
 
 } // namespace
 
@@ -139,25 +135,14 @@ int lmx_voxels_rng_skip(uint32_t u, uint32_t v, uint64_t n, uint32_t* u_out, uin
 	return LMX_OK;
 }
 
-int lmx_voxels_create(LmxContext* ctx, LmxVoxels** out) {
-	LMX_CHECK_CTX(ctx);
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	LmxVoxels* vox = new (std::nothrow) LmxVoxels();
-	if (!vox) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "voxels: host allocation failed");
-	vox->ctx = ctx;
-	*out = vox;
-	return LMX_OK;
-}
+int lmx_voxels_create(LmxContext* ctx, LmxVoxels** out) { return object_create(ctx, out, "voxels"); }
 
 void lmx_voxels_destroy(LmxVoxels* vox) {
-	if (!vox) return;
-	(void)hipSetDevice(vox->ctx->device);
-	(void)hipStreamSynchronize(vox->ctx->stream);
-	delete vox;
+	if (vox) object_destroy(vox);
 }
 
 int lmx_voxels_set(LmxVoxels* dst, const LmxVoxels* src) {
-	LMX_VOXELS_ENTER(dst);
+	LMX_ENTER(dst);
 	if (!src || src->ctx != ctx) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: the source is null or of another context");
 	if (dst == src) return LMX_OK;
 	if (!src->rastered) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: the source holds no grid");
@@ -176,19 +161,19 @@ int lmx_voxels_set(LmxVoxels* dst, const LmxVoxels* src) {
 }
 
 int lmx_voxels_begin_raster(LmxVoxels* vox, const float aabb_min[3], const float aabb_max[3], uint32_t max_res) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	return begin_raster(vox, aabb_min, aabb_max, max_res);
 }
 
 int lmx_voxels_raster(LmxVoxels* vox, const void* positions, uint32_t stride_bytes, uint32_t n_vertices, const void* indices, uint32_t index_bytes, uint32_t index_count) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->rastered) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: raster before begin_raster");
 	const LmxVoxelsMesh m = {positions, stride_bytes, n_vertices, indices, index_bytes, index_count};
 	return raster_mesh(vox, m);
 }
 
 int lmx_voxels_voxelize(LmxVoxels* vox, const LmxVoxelsMesh* meshes, uint32_t n_meshes, uint32_t max_res) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (n_meshes && !meshes) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: null meshes");
 	// the AABB over the vertices the indices reference, in index order (voxels.cpp:234-247): minimum(min, p) keeps `min` unless it is greater
 	float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
@@ -210,7 +195,7 @@ int lmx_voxels_voxelize(LmxVoxels* vox, const LmxVoxelsMesh* meshes, uint32_t n_
 }
 
 int lmx_voxels_compute_ao(LmxVoxels* vox, uint32_t ray_count, uint32_t seed_u, uint32_t seed_v) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->rastered) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: compute_ao before a raster");
 	if (ray_count == 0) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: ray_count is 0");
 	if (seed_u == 0 || seed_v == 0) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: a generator half is 0 (RandomGenerator asserts both are not)");
@@ -226,14 +211,14 @@ int lmx_voxels_compute_ao(LmxVoxels* vox, uint32_t ray_count, uint32_t seed_u, u
 }
 
 int lmx_voxels_set_option(LmxVoxels* vox, int option, int value) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (option != LMX_VOXELS_OPT_AO_LDS || (value != 0 && value != 1)) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: option %d = %d", option, value);
 	vox->ao_lds = value != 0;
 	return LMX_OK;
 }
 
 int lmx_voxels_rng_state(LmxVoxels* vox, uint32_t* u, uint32_t* v) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!u || !v) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (!vox->has_rng) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: no compute_ao has run");
 	*u = vox->rng.u;
@@ -242,7 +227,7 @@ int lmx_voxels_rng_state(LmxVoxels* vox, uint32_t* u, uint32_t* v) {
 }
 
 int lmx_voxels_blur_ao(LmxVoxels* vox) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->has_ao) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: blur_ao before compute_ao");
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	LMX_HIP(ctx, vox->d_ao_alt.reserve(std::max<size_t>(vox->n_cells, 1)));
@@ -252,7 +237,7 @@ int lmx_voxels_blur_ao(LmxVoxels* vox) {
 }
 
 int lmx_voxels_sample(LmxVoxels* vox, const float* points_xyz, uint32_t n, uint8_t* out_u8, uint8_t* out_inside) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->rastered) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: sample before a raster");
 	if (!n) return LMX_OK;
 	if (!points_xyz || !out_u8 || !out_inside) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: null points / outputs");
@@ -266,7 +251,7 @@ int lmx_voxels_sample(LmxVoxels* vox, const float* points_xyz, uint32_t n, uint8
 }
 
 int lmx_voxels_sample_ao(LmxVoxels* vox, const float* points_xyz, uint32_t n, float* out_ao, uint8_t* out_inside) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->has_ao) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: sample_ao before compute_ao");
 	if (!n) return LMX_OK;
 	if (!points_xyz || !out_ao || !out_inside) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: null points / outputs");
@@ -280,7 +265,7 @@ int lmx_voxels_sample_ao(LmxVoxels* vox, const float* points_xyz, uint32_t n, fl
 }
 
 int lmx_voxels_bake_vertex_ao(LmxVoxels* vox, const void* positions, uint32_t stride_bytes, uint32_t n, float min_ao, uint8_t* out_u8) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->has_ao) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: bake_vertex_ao before compute_ao");
 	if (!n) return LMX_OK;
 	if (!positions || !out_u8) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "voxels: null positions / output");
@@ -297,7 +282,7 @@ int lmx_voxels_bake_vertex_ao(LmxVoxels* vox, const void* positions, uint32_t st
 }
 
 int lmx_voxels_info(LmxVoxels* vox, LmxVoxelsInfo* out) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (!vox->rastered) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: no grid");
 	for (int k = 0; k < 3; ++k) {
@@ -310,25 +295,19 @@ int lmx_voxels_info(LmxVoxels* vox, LmxVoxelsInfo* out) {
 }
 
 int lmx_voxels_read(LmxVoxels* vox, uint8_t* out, uint32_t cap) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->rastered) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: no grid");
-	if (cap < vox->n_cells) return fail(ctx, LMX_ERR_CAPACITY, "voxels: %u cells, cap %u", vox->n_cells, cap);
-	if (!vox->n_cells) return LMX_OK;
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const uint8_t*)vox->d_voxels.p, vox->n_cells);
+	return read_out(ctx, out, cap, (const uint8_t*)vox->d_voxels.p, vox->n_cells, vox->n_cells, "cells", NullOut::Refused);
 }
 
 int lmx_voxels_read_ao(LmxVoxels* vox, float* out, uint32_t cap) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!vox->has_ao) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: no AO");
-	if (cap < vox->n_cells) return fail(ctx, LMX_ERR_CAPACITY, "voxels: %u cells, cap %u", vox->n_cells, cap);
-	if (!vox->n_cells) return LMX_OK;
-	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
-	return read_now(ctx, out, (const float*)vox->d_ao.p, vox->n_cells);
+	return read_out(ctx, out, cap, (const float*)vox->d_ao.p, vox->n_cells, vox->n_cells, "cells of AO", NullOut::Refused);
 }
 
 int lmx_voxels_device_outputs(LmxVoxels* vox, LmxVoxelsDevice* out) {
-	LMX_VOXELS_ENTER(vox);
+	LMX_ENTER(vox);
 	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
 	if (!vox->rastered) return fail(ctx, LMX_ERR_NOT_BUILT, "voxels: no grid");
 	out->d_voxels = vox->d_voxels.p;

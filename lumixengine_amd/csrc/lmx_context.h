@@ -12,6 +12,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
+#include <new>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -770,10 +771,18 @@ template <typename T> int read_now(LmxContext* ctx, T* dst, const T* src, size_t
 }
 
 // The read-out of a run's output: `used` elements are what the run left, `room` what the buffer holds - used again, or with a guard behind
-// it n + guard, and a larger array then also gets what lies behind the run's output up to the end of the guard.
-template <typename T> int read_out(LmxContext* ctx, T* out, size_t cap, const T* src, size_t used, size_t room, const char* what) {
+// it n + guard, and a larger array then also gets what lies behind the run's output up to the end of the guard. A null array is the
+// call site's choice: skipped (read_now's guard; the stream still drains), or refused behind the capacity check where there is something
+// to read - and an empty read of that kind returns without a call. A unit that refuses null FIRST checks in front, as before.
+enum class NullOut { Skipped, Refused };
+template <typename T> int read_out(LmxContext* ctx, T* out, size_t cap, const T* src, size_t used, size_t room, const char* what, NullOut null_out = NullOut::Skipped) {
 	if (cap < used) return fail(ctx, LMX_ERR_CAPACITY, "need room for %zu %s", used, what);
-	return read_now(ctx, out, src, std::min(cap, room));
+	const size_t n = std::min(cap, room);
+	if (null_out == NullOut::Refused) {
+		if (!n) return LMX_OK;
+		if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
+	}
+	return read_now(ctx, out, src, n);
 }
 
 // A guarded output holds `guard` elements behind the n a kernel may write: reserved with them (n + guard), filled here, never written by
@@ -808,6 +817,52 @@ inline int upload_list(LmxContext* ctx, DevBuf<int32_t>& d_list, const int32_t* 
 	LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return LMX_OK;
 }
+
+// ---- an object beside the context (lmx_*_create(ctx, &obj): a struct with a member `LmxContext* ctx`): the object's half of §4.20 ---------
+
+// The head of every entry point of such an object: a null object is refused without a message (there is no context to hold one), the
+// object's context becomes `ctx` and its device the current one.
+#define LMX_ENTER(obj)                                 \
+	if (!(obj)) return LMX_ERR_INVALID_ARGUMENT;       \
+	LmxContext* ctx = (obj)->ctx;                      \
+	LMX_CHECK_CTX(ctx)
+
+// lmx_*_create's common body. `*out` is null from here until the create has succeeded: a failed one leaves no handle behind. What a unit
+// does beyond this (tables that go up with the object) stands behind the call; where that fails it destroys the object and nulls `*out` again.
+template <typename T> int object_create(LmxContext* ctx, T** out, const char* what) {
+	LMX_CHECK_CTX(ctx);
+	if (!out) return fail(ctx, LMX_ERR_INVALID_ARGUMENT, "null out");
+	*out = nullptr;
+	T* obj = new (std::nothrow) T();
+	if (!obj) return fail(ctx, LMX_ERR_OUT_OF_MEMORY, "%s: host allocation failed", what);
+	obj->ctx = ctx;
+	*out = obj;
+	return LMX_OK;
+}
+
+// lmx_*_destroy's: the stream drains (a queued kernel may still use the object's buffers), then the buffers go. Null is the caller's to
+// refuse; unlinking the object from the context stands in front of the call.
+template <typename T> void object_destroy(T* obj) {
+	(void)hipSetDevice(obj->ctx->device);
+	(void)hipStreamSynchronize(obj->ctx->stream);
+	delete obj;
+}
+
+// The growing reserve: a buffer that already holds n elements costs no call; the first one that has to grow drains the stream in front
+// of its reserve (a queued kernel may still use the allocation a reserve frees), the ones behind it find the stream drained. One Grow
+// covers the reserves of one entry point up to its next launch or on-stream copy: behind those the stream is busy again, and the
+// reserves there take a Grow of their own. `drained` tells a unit that keeps state about the stream (texcomp's images_in_flight).
+struct Grow {
+	LmxContext* ctx;
+	bool drained = false;
+	template <typename T> int operator()(DevBuf<T>& buf, size_t n) {
+		if (n <= buf.cap) return LMX_OK;
+		if (!drained) LMX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		drained = true;
+		LMX_HIP(ctx, buf.reserve(n));
+		return LMX_OK;
+	}
+};
 
 struct ProfScope { // records HIP events around one launch on the launch stream when profiling is enabled
 	LmxContext* ctx;

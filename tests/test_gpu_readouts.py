@@ -2,11 +2,15 @@
 
   * a capacity one short of what the run left is refused with the code the table states, and the caller's array is left as it was;
   * the exact capacity succeeds and gives what a generous capacity gives, nothing behind it is written;
-  * a guard reader (pose buffer, light records, light entities, map, ray candidates, particle channels and frame) given the buffer's whole
-    room returns the guard's fill bytes behind the payload, and given more than that leaves what lies behind the room alone;
+  * a guard reader (pose buffer, light records, light entities, map, ray candidates, particle channels and frame, compressed blocks, chain
+    pixels) given the buffer's whole room returns the guard's fill bytes behind the payload, and given more than that leaves what lies
+    behind the room alone;
   * a null array with something to read gives the code the table states. The units disagree about that - INVALID_ARGUMENT in the
-    instanced models, the grass and the Animators' exact-size readers, CAPACITY in the particles, silently skipped (OK) in draw, clusters,
-    rays, poses, keys and the optional outputs of the Animators - and the table records it.
+    instanced models, the grass, the voxels, the probes, the texture compressor and the Animators' exact-size readers, CAPACITY in the
+    particles, silently skipped (OK) in draw, clusters, rays, poses, keys, the animation compressor and the optional outputs of the
+    Animators - and the table records it. Where a null array is refused, the table also states the code of a null array
+    at a capacity one short: CAPACITY where the capacity is checked first, INVALID_ARGUMENT in the texture compressor, which looks at the
+    pointer first.
 
 Runs on the MI355X and under `pytest -m gpu --hostsim`."""
 import ctypes as C
@@ -32,12 +36,13 @@ class Reader:
     """One read-out: call(cap, *pointers) -> code. `used`: what the run left, in the units of cap; dtypes / counts(cap): the element type
     and count of every output array; short: the code of cap = used - 1; null[i]: the code of a null output i at a generous cap;
     exact: the entry point takes the count itself, not a capacity (anything else is `short`). A guard reader has room (the buffer with its
-    guard, in the units of cap) and guard, the [first, end) element ranges of output 0 that hold the fill byte."""
+    guard, in the units of cap) and guard, the [first, end) element ranges of output 0 that hold the fill byte. null_short, where given: the
+    code of a null output 0 at cap = used - 1, which pins the order of the two refusals."""
 
-    def __init__(self, call, dtypes, used, null, counts=None, short=CAPACITY, exact=False, room=None, guard=()):
+    def __init__(self, call, dtypes, used, null, counts=None, short=CAPACITY, exact=False, room=None, guard=(), null_short=None):
         self.call, self.dtypes, self.used, self.null, self.short, self.exact = call, [np.dtype(d) for d in dtypes], int(used), null, short, exact
         self.counts = counts or (lambda cap: (cap,) * len(dtypes))
-        self.room, self.guard = room, guard
+        self.room, self.guard, self.null_short = room, guard, null_short
 
     def run(self, cap, null=None):
         """-> (code, the outputs' bytes with PAD bytes behind each)"""
@@ -77,6 +82,11 @@ def check(r: Reader, name):
             continue
         rc, got = r.run(generous, null=i)
         assert rc == code, f"{name}: a null output {i} gives {rc}, the table says {code}"
+    if r.null_short is not None:
+        assert r.used, name
+        rc, got = r.run(r.used - 1, null=0)
+        assert rc == r.null_short, f"{name}: a null output at cap = used - 1 gives {rc}, the table says {r.null_short}"
+        assert all((g == FILL).all() for g in got), f"{name}: a refused call wrote to the caller's array"
 
 
 # ---- scenes -----------------------------------------------------------------------------------------------------------------------
@@ -228,9 +238,9 @@ def im_scene(ctx, R, N):
     assert total == 5 and len(im.readIndirect()) == 1
     lib, h = ctx.lib, im.h
     R["im_read_instances"] = Reader(lambda cap, p: lib.lmx_im_read_instances(h, m, p, cap), [api.IM_INSTANCE], 5, [INVALID_ARGUMENT])
-    R["im_counts"] = Reader(lambda cap, p: lib.lmx_im_counts(h, 0, p, cap), [api.IM_COUNTS], 1, [INVALID_ARGUMENT])
-    R["im_read_records"] = Reader(lambda cap, p: lib.lmx_im_read_records(h, 0, p, cap, C.byref(u32())), [api.IM_INSTANCE], total, [INVALID_ARGUMENT])
-    R["im_read_indirect"] = Reader(lambda cap, p: lib.lmx_im_read_indirect(h, 0, p, cap, C.byref(u32())), [api.IM_INDIRECT], 1, [INVALID_ARGUMENT])
+    R["im_counts"] = Reader(lambda cap, p: lib.lmx_im_counts(h, 0, p, cap), [api.IM_COUNTS], 1, [INVALID_ARGUMENT], null_short=CAPACITY)
+    R["im_read_records"] = Reader(lambda cap, p: lib.lmx_im_read_records(h, 0, p, cap, C.byref(u32())), [api.IM_INSTANCE], total, [INVALID_ARGUMENT], null_short=CAPACITY)
+    R["im_read_indirect"] = Reader(lambda cap, p: lib.lmx_im_read_indirect(h, 0, p, cap, C.byref(u32())), [api.IM_INDIRECT], 1, [INVALID_ARGUMENT], null_short=CAPACITY)
     N["im_read_grid"] = (lambda p: lib.lmx_im_read_grid(h, m, p), api.IM_GRID, INVALID_ARGUMENT)
 
 
@@ -248,9 +258,9 @@ def grass_scene(ctx, R, N):
     lib, h = ctx.lib, g.h
     S = api.GRASS_SLOT_INSTANCES
     R["grass_read_quads"] = Reader(lambda cap, p: lib.lmx_grass_read_quads(h, p, cap, C.byref(u32())), [api.GRASS_QUAD], 1, [INVALID_ARGUMENT])
-    R["grass_read_instances"] = Reader(lambda cap, p: lib.lmx_grass_read_instances(h, 0, p, cap), [api.GRASS_INSTANCE], S, [INVALID_ARGUMENT])
-    R["grass_read_draws"] = Reader(lambda cap, p: lib.lmx_grass_read_draws(h, 0, p, cap, C.byref(u32())), [api.GRASS_DRAW], 1, [INVALID_ARGUMENT])
-    R["grass_counts"] = Reader(lambda cap, p: lib.lmx_grass_counts(h, p, cap), [api.GRASS_COUNTS], 1, [INVALID_ARGUMENT])
+    R["grass_read_instances"] = Reader(lambda cap, p: lib.lmx_grass_read_instances(h, 0, p, cap), [api.GRASS_INSTANCE], S, [INVALID_ARGUMENT], null_short=CAPACITY)
+    R["grass_read_draws"] = Reader(lambda cap, p: lib.lmx_grass_read_draws(h, 0, p, cap, C.byref(u32())), [api.GRASS_DRAW], 1, [INVALID_ARGUMENT], null_short=CAPACITY)
+    R["grass_counts"] = Reader(lambda cap, p: lib.lmx_grass_counts(h, p, cap), [api.GRASS_COUNTS], 1, [INVALID_ARGUMENT], null_short=CAPACITY)
 
 
 def particles_scene(ctx, R, N):
@@ -306,8 +316,97 @@ def animators_scene(ctx, R, N):
     R["anim_read_pose"] = Reader(lambda cap, pos, rot: lib.lmx_anim_read_pose(h, 0, pos, rot, cap), [np.float32, np.float32], n_bones, [OK, OK], counts=lambda cap: (3 * cap, 4 * cap))
 
 
+def voxels_scene(ctx, R, N):
+    """one triangle in a grid of max_res 2, four rays of AO per cell"""
+    vx = api.Voxels(ctx)
+    vx.voxelize([(f32([[0, 0, 0], [1, 0, 0], [0, 1, 0.5]]), np.array([0, 1, 2], np.uint16))], 2)
+    vx.computeAO(4, 1, 2)
+    KEEP.append(vx)
+    cells = vx._cells()
+    assert 1 < cells <= 128 and vx.read().any(), cells
+    lib, h = ctx.lib, vx.h
+    R["voxels_read"] = Reader(lambda cap, p: lib.lmx_voxels_read(h, p, cap), [np.uint8], cells, [INVALID_ARGUMENT], null_short=CAPACITY)
+    R["voxels_read_ao"] = Reader(lambda cap, p: lib.lmx_voxels_read_ao(h, p, cap), [np.float32], cells, [INVALID_ARGUMENT], null_short=CAPACITY)
+    N["voxels_info"] = (lambda p: lib.lmx_voxels_info(h, p), api.VOXELS_INFO, INVALID_ARGUMENT)
+
+
+def probes_scene(ctx, R, N):
+    """one cubemap of size 16 (the smallest a mip run takes): its SH, its mips, its radiance levels and their RGBM bytes"""
+    pb = api.ProbeBaker(ctx)
+    pb.setCubemaps(np.random.default_rng(16).random((1, 6, 16, 16, 4), dtype=f32))
+    pb.shRun()
+    pb.filterRun()
+    KEEP.append(pb)
+    lib, h = ctx.lib, pb.h
+    mips, levels = 4 * api.probe_mip_texels(16), 4 * pb._level_texels()  # floats of the mips; floats of the levels = their RGBM bytes
+    rows = dict(null=[INVALID_ARGUMENT], null_short=CAPACITY)
+    R["probes_read_sh"] = Reader(lambda cap, p: lib.lmx_probes_read_sh(h, p, cap), [np.float32], 1, counts=lambda cap: (27 * cap,), **rows)  # (cap in probes)
+    R["probes_read_mips"] = Reader(lambda cap, p: lib.lmx_probes_read_mips(h, p, cap), [np.float32], mips, **rows)
+    R["probes_read_filtered"] = Reader(lambda cap, p: lib.lmx_probes_read_filtered(h, p, cap), [np.float32], levels, **rows)
+    R["probes_read_rgbm"] = Reader(lambda cap, p: lib.lmx_probes_read_rgbm(h, p, cap), [np.uint8], levels, **rows)
+
+
+def texcomp_scene(ctx, R, N):
+    """one 4 x 4 image as one BC1 block; one 4 x 4 chain and its two generated levels"""
+    px = np.random.default_rng(4).integers(0, 256, (1, 4, 4, 4), dtype=np.uint8)
+    blocks, chain = api.TexCompressor(ctx), api.TexCompressor(ctx)
+    blocks.setImages([px[0]])
+    blocks.run(api.TEX_BC1)
+    chain.setChains(px)
+    chain.generateMips(api.TEXMIP_LINEAR)
+    KEEP.append((blocks, chain))
+    lib, G = ctx.lib, api.TEXCOMP_GUARD_BYTES
+    n_blocks, n_pixels = api.TEX_BLOCK_BYTES[api.TEX_BC1], api.texcomp_chain_bytes(1, 4, 4)
+    assert n_blocks == 8 and n_pixels == 4 * (16 + 4 + 1)
+    # both refuse a null array first, then a short one; both hold a guard behind what they read
+    R["texcomp_read"] = Reader(lambda cap, p: lib.lmx_texcomp_read(blocks.h, p, cap), [np.uint8], n_blocks, [INVALID_ARGUMENT], room=n_blocks + G, guard=[(n_blocks, n_blocks + G)],
+                               null_short=INVALID_ARGUMENT)
+    R["texcomp_read_pixels"] = Reader(lambda cap, p: lib.lmx_texcomp_read_pixels(chain.h, p, cap), [np.uint8], n_pixels, [INVALID_ARGUMENT], room=n_pixels + G,
+                                      guard=[(n_pixels, n_pixels + G)], null_short=INVALID_ARGUMENT)
+
+
+def animcomp_scene(ctx, R, N):
+    """one clip of two bones and two samples, every track of it animated"""
+    from tests import animcomp_cases as AC
+
+    k = np.zeros((2, 2, 7), f32)
+    k[0, :, 3:] = [0, 0, 0, 1]
+    k[1, :, 3:] = [0.6, 0, 0, 0.8]
+    k[1, :, :3] = [[5, 0, 0], [0, -7, 3]]
+    ac = api.AnimCompressor(ctx)
+    ac.setClips([AC.clip("two bones, two samples", k, np.zeros((2, 3), f32))])
+    ac.run()
+    KEEP.append(ac)
+    info = ac.clipInfo(0)
+    assert info["status"] == 0 and info["translation_stream_size"] and info["rotation_stream_size"], info
+    most = max(info[f] for f in ("n_const_translations", "n_translations", "n_const_rotations", "n_rotations"))
+    used = {"tracks": most, "translation_stream": info["translation_stream_size"], "rotation_stream": info["rotation_stream_size"]}
+    lib, h = ctx.lib, ac.h
+    tables = [api.ANIM_CONST_TRANSLATION, api.ANIM_TRANSLATION_TRACK, api.ANIM_CONST_ROTATION, api.ANIM_ROTATION_TRACK]
+
+    def row(which):
+        """the capacity `which` is the reader's cap, the other two are generous; every array has the room its own capacity states, or more"""
+        def call(cap, *arrays):
+            caps = {f: n + 5 for f, n in used.items()}
+            caps[which] = cap
+            out = api.LmxAnimCompOutput(*arrays, caps["tracks"], 0, caps["translation_stream"], caps["rotation_stream"])
+            return lib.lmx_animcomp_read_clip(h, 0, C.byref(out))
+
+        def counts(cap):
+            n = dict(used)
+            n[which] = cap
+            return (n["tracks"],) * 4 + (n["translation_stream"], n["rotation_stream"])
+
+        return Reader(call, tables + [np.uint8, np.uint8], used[which], [OK] * 6, counts=counts, null_short=CAPACITY)
+
+    for which in used:
+        R["animcomp_read_clip." + which] = row(which)
+    N["animcomp_clip_info"] = (lambda p: lib.lmx_animcomp_clip_info(h, 0, p), np.dtype((np.uint8, C.sizeof(api.LmxAnimCompInfo))), INVALID_ARGUMENT)
+
+
 SCENES = {"draw": draw_scene, "keys": keys_scene, "clusters": clusters_scene, "poses": poses_scene, "rays": rays_scene, "im": im_scene, "grass": grass_scene,
-          "particles": particles_scene, "animators": animators_scene}
+          "particles": particles_scene, "animators": animators_scene, "voxels": voxels_scene, "probes": probes_scene, "texcomp": texcomp_scene,
+          "animcomp": animcomp_scene}
 READERS = {
     "draw": ["draw_read_runs", "draw_read_instance_data", "draw_read_group_data"],
     "keys": ["keys_read_pairs", "keys_read_instancer", "keys_read_poses", "keys_read_dirty", "keys_read_state"],
@@ -318,10 +417,15 @@ READERS = {
     "grass": ["grass_read_quads", "grass_read_instances", "grass_read_draws", "grass_counts"],
     "particles": ["particles_counts", "particles_read_channels", "particles_read_slices.slices", "particles_read_slices.frame"],
     "animators": ["animators_read_root_motion", "animators_read_state", "animators_read_instrs", "anim_read_times", "anim_read_pose"],
+    "voxels": ["voxels_read", "voxels_read_ao"],
+    "probes": ["probes_read_sh", "probes_read_mips", "probes_read_filtered", "probes_read_rgbm"],
+    "texcomp": ["texcomp_read", "texcomp_read_pixels"],
+    "animcomp": ["animcomp_read_clip.tracks", "animcomp_read_clip.translation_stream", "animcomp_read_clip.rotation_stream"],
 }
 # the readers of fixed size: a record the caller always has room for, so only the null rule applies
 NULL_ONLY = {"draw": ["draw_counts"], "keys": ["keys_counts"], "clusters": ["clusters_counts"], "poses": ["poses_counts"],
-             "rays": ["rays_counts", "rays_im_counts", "rays_scene_counts"], "im": ["im_read_grid"], "grass": [], "particles": [], "animators": []}
+             "rays": ["rays_counts", "rays_im_counts", "rays_scene_counts"], "im": ["im_read_grid"], "grass": [], "particles": [], "animators": [], "voxels": ["voxels_info"], "probes": [],
+             "texcomp": [], "animcomp": ["animcomp_clip_info"]}
 
 
 @pytest.fixture(scope="module")
